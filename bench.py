@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """depthmaps/sec of the MI355X plane-sweep forward at 512x256, 64 hypotheses, 2 source views.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one MultiViewStereoNet.forward() over a batch of B synthetic reference images (each
 with 2 source views) already resident in HBM; every rank runs its own B images (weak scaling,
-images are independent -- SURVEY 8e) and the ranks all-gather one metric row per image at the end.
-Rank 0 prints ONE JSON line, LAST and < 4 KB (`final_line`); the full record (per-kernel rooflines, the other
-configurations, tier legs, latencies) goes to `bench_detail.json` and a `DETAIL <json>` stdout line before it.  It reports
+images are independent -- SURVEY 8e).
+Rank 0 prints ONE JSON line, LAST and < 4 KB (`final_line`); the full record goes to `bench_detail.json` and a
+`DETAIL <json>` stdout line before it.  A plain run sets up, runs W untimed and K timed steps, writes the last step's
+outputs if `--dump-outputs DIR` is given (`dump_outputs`) and prints the line: `value` (depthmaps/s), `ms_per_step`
+and the run's description.  `--full` adds everything else -- the all-gather of one metric row per image, the per-kernel
+rooflines, the other configurations, tier legs and latencies, and
   roofline      the dominant kernel's algorithmic flops / measured launch time (device events on the
                 stream the kernels run on) against the fp32 MFMA peak, plus the fused chain kernel
                 against both peaks,
@@ -207,6 +210,38 @@ def emit(full, stream=None):
     stream.write("DETAIL " + blob + "\n")
     stream.write(final_line(full) + "\n")
     stream.flush()
+
+
+DUMP_LIMIT = 60 * 2 ** 20      # bytes of array data in all the files `--dump-outputs` writes (< 64 MB with headers)
+DUMP_SEED = 20261016           # the element sample of an output too large to keep whole
+
+
+def dump_outputs(out, path):
+    """`--dump-outputs DIR`: the arrays the forward of the last timed step returned to its caller, as
+    DIR/<key>_<level>.npy (float32; the bool masks as 0 / 1).  Each output gets an equal share of DUMP_LIMIT: one that
+    fits is written whole in its own shape, a larger one as a fixed sample of its flattened elements (seeded indices,
+    in increasing order: the same elements on every run with the same arguments).  Returns {name: shape written}."""
+    import numpy as np
+    arrays = []
+    for key in sorted(out):
+        val = out[key]
+        for lvl, t in enumerate(val if isinstance(val, (list, tuple)) else [val]):
+            if isinstance(t, torch.Tensor):
+                arrays.append((f"{key}_{lvl}" if isinstance(val, (list, tuple)) else key, t))
+    os.makedirs(path, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays:
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = DUMP_LIMIT // len(arrays) // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT, total
+    return written
 
 
 def make_inputs(batch, first_seed, device):
@@ -660,17 +695,26 @@ def main():
     ap.add_argument("--fold", action="store_true", help="fold residual blocks into the next conv's tile load")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "bf16"], default=os.environ.get("MVSN_BENCH_PRECISION", "fp32"),
                     help="arithmetic of the 32->32 3x3 layers: exact fp32 MFMA, or the 3 x bf16 split tier")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tiers", action="store_true", help="skip the bf16x3 / bf16 tier legs and the batch-latency leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beyond the headline figure: "
+                         "metric rows, parity against the reference fixture and the oracle, per-kernel rooflines, "
+                         "the other precisions / batch sizes / configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and oracle checks")
+    ap.add_argument("--no-tiers", action="store_true",
+                    help="(--full) skip the bf16x3 / bf16 tier legs and the batch-latency leg")
     ap.add_argument("--sustain", type=float, default=0.0, metavar="SECONDS",
-                    help="after the timed region: keep stepping for this long and report the rate per 2-second window "
-                         "(clock settling under sustained MFMA load); writes nothing, adds a 'sustained' key")
+                    help="(--full) after the timed region: keep stepping for this long and report the rate per 2-second "
+                         "window (clock settling under sustained MFMA load); writes nothing, adds a 'sustained' key")
     ap.add_argument("--single-device-selftest", action="store_true",
                     help="N > 1 ranks that ALL use cuda:0 and talk over gloo: exercises the multi-rank line (quality fields "
                          "at every world size) on a one-GPU box.  Its rate is NOT a scaling measurement and is labelled so.")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU ranks over gloo with a stand-in step: checks the launch/timing/gather plumbing only")
     args = ap.parse_args()
+    if args.sustain > 0 and not args.full:
+        ap.error("--sustain is part of the --full record")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on
@@ -718,31 +762,8 @@ def main():
     torch.cuda.synchronize()
     coll_dev = torch.device("cpu") if args.single_device_selftest else dev     # (gloo ranks exchange host tensors)
     elapsed, per_rank, out = timed_steps(step, args.steps, args.warmup, world, torch.cuda.synchronize, coll_dev)
-
-    # per-image metric rows, all-gathered (the path's only exchange step)
-    idepth = out["left_idepthmap_pyr"][0]
-    rows = torch.stack([idepth.mean(dim=(1, 2, 3)), (idepth > 0).float().mean(dim=(1, 2, 3)),
-                        mask_mean(out["left_idepthmap_mask_pyr"][-1])], 1)     # (the COARSEST level's mask: see mask_mean)
-    idx = torch.arange(rank * B, (rank + 1) * B, device=dev)
-    all_rows, all_idx = mdist.gather_metric_rows(rows.to(coll_dev), idx.to(coll_dev))
-    assert all_rows.shape[0] == B * world and bool(torch.isfinite(all_rows).all())
-
-    # ---- quality fields, on EVERY rank (its own device), reduced to rank 0: the line of an N-GPU run carries the
-    # same parity / roofline / chain-kernel / CPU-baseline fields as the 1-GPU line (roofline: min over ranks)
-    agg = kernel_breakdown(net, inp, Dn)
-    total_ms = sum(e["ms"] for e in agg.values())
-    # the dominant kernel = the arithmetic kernel with the most device time (the bookkeeping launches carry no flops)
-    name, dom = max(((k, v) for k, v in agg.items() if v["flops"] > 0), key=lambda kv: kv[1]["ms"])
-    per_launch_ms = dom["ms"] / dom["launches"]
-    # dom["flops"] counts the layer in its direct form (2 * cin * taps * cout per output).  The Winograd
-    # kernels execute 16 multiplies per 2x2 outputs and tap plane instead of 36 (x 4/9): the roofline is
-    # priced on the flops the matrix pipe actually executes, the direct-form figure is reported beside it.
-    wino = " wino" in name
-    direct_tfl = dom["flops"] / dom["launches"] / (per_launch_ms * 1e-3) / 1e12
-    tfl = direct_tfl * (4.0 / 9.0 if wino else 1.0)
-    fracs = gather_floats(tfl / PEAK_FP32_MFMA_TFLOPS, world, coll_dev)
-    ch = agg.get("mvsn_incremental_cost_volume")
-    chain_ms = gather_floats(ch["ms"] / ch["launches"] if ch else 0.0, world, coll_dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)      # (before any other forward: a replayed plan reuses its buffers)
 
     if rank == 0:
         line = {"metric": "depthmaps/sec at 512x256, 64 hypotheses, 2 src views; L1 vs ref",
@@ -756,8 +777,7 @@ def main():
                 "data": f"synthetic (seeded frames, pretrained {cfg['weights']} weights)",
                 "config": {"workload": cfg["what"], "name": args.config, "images_per_gpu_per_step": B,
                            "global_batch": B * world, "parallelism": f"dp{world} (independent images, "
-                                                                      "all-gather of metric rows)"},
-                "mean_idepth": float(mdist.average_rows(all_rows)[0])}
+                                                                      "all-gather of metric rows)"}}
         if os.environ.get("MVSN_BENCH_OPTIONS"):
             line["engine_options_override"] = os.environ["MVSN_BENCH_OPTIONS"]       # (an A/B run, not the default line)
         if args.single_device_selftest:
@@ -766,178 +786,206 @@ def main():
         if not headline:
             line["metric"] = (f"depthmaps/sec at {cfg['cols']}x{cfg['rows']}, {Dn} hypotheses, {Sn} src views; L1 vs ref "
                               f"(--config {args.config}: NOT the headline configuration)")
-        got0 = idepth[:1].cpu()
-        line["l1_vs_ref"] = l1_against(ref0, got0, cfg["golden"])
-        traffic, traffic_source = None, None
-        # HBM bytes per launch from the committed PMC passes of THIS library (refused when the digest differs)
-        pmc = load_profile_json(PMC_TRAFFIC_FILE)
-        # (per-chain bytes depend on the configuration's geometry: the headline's entries are top-level -- configs 2 / 3 share
-        # its coarse grid and depth --, the others come from passes of their own command under `configs`, or there is none)
-        pmc_cfg = pmc if args.config in ("headline", "config2", "config3") else ((pmc or {}).get("configs", {}).get(args.config) or {})
-        t = (pmc_cfg or {}).get(name)
-        if t:
-            traffic = (t["fetch_bytes_per_chain"] + t["write_bytes_per_chain"]) * B * Sn
-            # (older files carry no flag: the raw / reported pair says whether the kernel's fetch figure was doubled)
-            doubled = t.get("fetch_doubled", t["fetch_bytes_per_chain"] != t.get("fetch_bytes_per_chain_raw"))
-            how = ("FETCH_SIZE x2 (gfx950 half-count of 16-byte streaming reads: this kernel's tiles arrive by 16-byte LDS-DMA)"
-                   if doubled else "FETCH_SIZE as read (this kernel's 4- / 8-byte accesses are not half-counted)")
-            traffic_source = (f"profiles/{pmc['_file']}: {how} + "
-                              f"WRITE_SIZE of separate rocprofv3 --pmc passes of the bench command with this library "
-                              f"(digest {pmc['_library_digest'][:12]}, {pmc.get('_chains_per_launch', '?')} chains per launch), "
-                              "per chain x this batch -- a committed pass, NOT a counter read during this run")
-        elif pmc is not None:
-            traffic_source = f"profiles/{pmc['_file']} holds no pass of this configuration's `{name}` kernel"
-        else:
-            traffic_source = (f"profiles/{PMC_TRAFFIC_FILE} is missing or was taken with another build of the library "
-                              "(digest mismatch): refused")
-        line["roofline"] = {"kernel": name, "bound": "mfma", "achieved": tfl, "peak": PEAK_FP32_MFMA_TFLOPS,
-                            "unit": "TFLOP/s", "frac": min(fracs), "frac_per_rank": fracs, "traffic": traffic,
-                            "traffic_source": traffic_source,
-                            "launches_per_step": dom["launches"], "avg_launch_ms": per_launch_ms,
-                            "share_of_step": dom["ms"] / total_ms}
-        if "+pass" in name:
-            line["roofline"]["carried_pass"] = ("each of these launches also executes the in-place LeakyReLU(GroupNorm(.)) "
-                                                "pass of the other batch slice's previous layer (mvsn_conv_forward_carry): "
-                                                "its loads / stores are part of the launch time and of `traffic`, "
-                                                "`achieved` counts the convolution's flops only")
-        if wino:
-            line["roofline"]["form"] = ("Winograd F(2x2,3x3) per depth tap: 12 multiplies per output and "
-                                        "(cin, cout) pair instead of 27; achieved = executed MFMA flops")
-            line["roofline"]["direct_form_equivalent_TFLOPs"] = direct_tfl
-        if ch:
-            eng = net.engine()
-            sec = max(chain_ms) * 1e-3 * ch["launches"]          # slowest rank
-            form = {1: "direct", 2: "winograd", 3: "stepwise", 4: "banded"}.get(eng.last_chain_form, "?")
-            wino_chain = form in ("winograd", "banded", "stepwise")
-            direct_tfl_c = ch["flops"] / sec / 1e12
-            exec_tfl = direct_tfl_c * (4.0 / 9.0 if wino_chain else 1.0)
-            line["chain_kernel"] = {"kernel": "mvsn_incremental_cost_volume (warp + refine + cost volume, fused)",
-                                    "form": form + (": Winograd F(2x2,3x3) for the three 3x3 convolutions of a step (16 "
-                                                    "multiplies per 2x2 outputs instead of 36)" if wino_chain else ""),
-                                    "avg_launch_ms": max(chain_ms), "avg_launch_ms_per_rank": chain_ms,
-                                    "chains_per_launch": B * Sn,
-                                    "algorithmic_GBps": ch["bytes"] / sec / 1e9,
-                                    "frac_of_hbm_peak": ch["bytes"] / sec / 1e9 / PEAK_HBM_GBS,
-                                    "direct_form_TFLOPs": direct_tfl_c,
-                                    "direct_form_frac_of_fp32_mfma_peak": direct_tfl_c / PEAK_FP32_MFMA_TFLOPS,
-                                    "executed_TFLOPs": exec_tfl,
-                                    "executed_frac_of_fp32_mfma_peak": exec_tfl / PEAK_FP32_MFMA_TFLOPS,
-                                    "share_of_step": ch["ms"] / total_ms}
-            t = (pmc_cfg or {}).get("mvsn_incremental_cost_volume")
-            if t and (form == "winograd" or args.config != "headline"):
-                line["chain_kernel"]["hbm_traffic_bytes_per_chain"] = {
-                    "fetched": t["fetch_bytes_per_chain"], "written": t["write_bytes_per_chain"],
-                    "algorithmic": t["algorithmic_bytes_per_chain"],
-                    "ratio": (t["fetch_bytes_per_chain"] + t["write_bytes_per_chain"]) /
-                    t["algorithmic_bytes_per_chain"], "source": f"profiles/{pmc['_file']} (separate PMC pass, this library)"}
-        line["kernel_ms_per_step"] = {k: round(v["ms"], 3) for k, v in
-                                      sorted(agg.items(), key=lambda kv: -kv[1]["ms"])[:16]}
-        line["launches_per_forward"] = int(sum(v["launches"] for v in agg.values()))
-        wino_chain_now = net.engine().last_chain_form in (2, 3, 4)      # every chain form but the direct one
-        line["roofline_by_kernel"] = roofline_by_kernel(
-            agg, total_ms, wino_names=("mvsn_incremental_cost_volume",) if wino_chain_now else ())
-        if world == 1 and args.sustain > 0:
-            windows, t_end = [], time.perf_counter() + args.sustain
-            while time.perf_counter() < t_end:
-                n_steps, t1 = 0, time.perf_counter()
-                while time.perf_counter() - t1 < 2.0:
-                    step()
-                    n_steps += 1
-                    if n_steps % 8 == 0:
-                        torch.cuda.synchronize()
-                torch.cuda.synchronize()
-                windows.append(B * n_steps / (time.perf_counter() - t1))
-            line["sustained"] = {"seconds": args.sustain, "window_s": 2.0,
-                                 "depthmaps_per_s_per_window": [round(w, 1) for w in windows],
-                                 "first": round(windows[0], 1), "last": round(windows[-1], 1),
-                                 "min": round(min(windows), 1), "droop_last_vs_first": 1.0 - windows[-1] / windows[0],
-                                 "timed_region_value": line["value"]}
-        if world == 1 and headline and not args.no_tiers:
-            # side legs: a failure in one of them must not cost the headline line
-            for key, leg in (("pcie_inclusive", lambda: host_feed_rates(net, B, dev)),
-                             ("evaluate_rate", lambda: evaluate_rate(net, B, dev, line["value"])),
-                             ("batch_latency", lambda: batch_latency(net)),
-                             ("headline_by_batch", lambda: headline_by_batch(net, dev)),
-                             ("other_configs", lambda: other_configs(dev, skip=("headline",)))):
+    if args.full:
+        # per-image metric rows, all-gathered (the path's only exchange step)
+        idepth = out["left_idepthmap_pyr"][0]
+        rows = torch.stack([idepth.mean(dim=(1, 2, 3)), (idepth > 0).float().mean(dim=(1, 2, 3)),
+                            mask_mean(out["left_idepthmap_mask_pyr"][-1])], 1)     # (the COARSEST level's mask: see mask_mean)
+        idx = torch.arange(rank * B, (rank + 1) * B, device=dev)
+        all_rows, all_idx = mdist.gather_metric_rows(rows.to(coll_dev), idx.to(coll_dev))
+        assert all_rows.shape[0] == B * world and bool(torch.isfinite(all_rows).all())
+
+        # ---- quality fields, on EVERY rank (its own device), reduced to rank 0: the line of an N-GPU run carries the
+        # same parity / roofline / chain-kernel / CPU-baseline fields as the 1-GPU line (roofline: min over ranks)
+        agg = kernel_breakdown(net, inp, Dn)
+        total_ms = sum(e["ms"] for e in agg.values())
+        # the dominant kernel = the arithmetic kernel with the most device time (the bookkeeping launches carry no flops)
+        name, dom = max(((k, v) for k, v in agg.items() if v["flops"] > 0), key=lambda kv: kv[1]["ms"])
+        per_launch_ms = dom["ms"] / dom["launches"]
+        # dom["flops"] counts the layer in its direct form (2 * cin * taps * cout per output).  The Winograd
+        # kernels execute 16 multiplies per 2x2 outputs and tap plane instead of 36 (x 4/9): the roofline is
+        # priced on the flops the matrix pipe actually executes, the direct-form figure is reported beside it.
+        wino = " wino" in name
+        direct_tfl = dom["flops"] / dom["launches"] / (per_launch_ms * 1e-3) / 1e12
+        tfl = direct_tfl * (4.0 / 9.0 if wino else 1.0)
+        fracs = gather_floats(tfl / PEAK_FP32_MFMA_TFLOPS, world, coll_dev)
+        ch = agg.get("mvsn_incremental_cost_volume")
+        chain_ms = gather_floats(ch["ms"] / ch["launches"] if ch else 0.0, world, coll_dev)
+
+        if rank == 0:
+            line["mean_idepth"] = float(mdist.average_rows(all_rows)[0])
+            got0 = idepth[:1].cpu()
+            line["l1_vs_ref"] = l1_against(ref0, got0, cfg["golden"])
+            traffic, traffic_source = None, None
+            # HBM bytes per launch from the committed PMC passes of THIS library (refused when the digest differs)
+            pmc = load_profile_json(PMC_TRAFFIC_FILE)
+            # (per-chain bytes depend on the configuration's geometry: the headline's entries are top-level -- configs 2 / 3 share
+            # its coarse grid and depth --, the others come from passes of their own command under `configs`, or there is none)
+            pmc_cfg = pmc if args.config in ("headline", "config2", "config3") else ((pmc or {}).get("configs", {}).get(args.config) or {})
+            t = (pmc_cfg or {}).get(name)
+            if t:
+                traffic = (t["fetch_bytes_per_chain"] + t["write_bytes_per_chain"]) * B * Sn
+                # (older files carry no flag: the raw / reported pair says whether the kernel's fetch figure was doubled)
+                doubled = t.get("fetch_doubled", t["fetch_bytes_per_chain"] != t.get("fetch_bytes_per_chain_raw"))
+                how = ("FETCH_SIZE x2 (gfx950 half-count of 16-byte streaming reads: this kernel's tiles arrive by 16-byte LDS-DMA)"
+                       if doubled else "FETCH_SIZE as read (this kernel's 4- / 8-byte accesses are not half-counted)")
+                traffic_source = (f"profiles/{pmc['_file']}: {how} + "
+                                  f"WRITE_SIZE of separate rocprofv3 --pmc passes of the bench command with this library "
+                                  f"(digest {pmc['_library_digest'][:12]}, {pmc.get('_chains_per_launch', '?')} chains per launch), "
+                                  "per chain x this batch -- a committed pass, NOT a counter read during this run")
+            elif pmc is not None:
+                traffic_source = f"profiles/{pmc['_file']} holds no pass of this configuration's `{name}` kernel"
+            else:
+                traffic_source = (f"profiles/{PMC_TRAFFIC_FILE} is missing or was taken with another build of the library "
+                                  "(digest mismatch): refused")
+            line["roofline"] = {"kernel": name, "bound": "mfma", "achieved": tfl, "peak": PEAK_FP32_MFMA_TFLOPS,
+                                "unit": "TFLOP/s", "frac": min(fracs), "frac_per_rank": fracs, "traffic": traffic,
+                                "traffic_source": traffic_source,
+                                "launches_per_step": dom["launches"], "avg_launch_ms": per_launch_ms,
+                                "share_of_step": dom["ms"] / total_ms}
+            if "+pass" in name:
+                line["roofline"]["carried_pass"] = ("each of these launches also executes the in-place LeakyReLU(GroupNorm(.)) "
+                                                    "pass of the other batch slice's previous layer (mvsn_conv_forward_carry): "
+                                                    "its loads / stores are part of the launch time and of `traffic`, "
+                                                    "`achieved` counts the convolution's flops only")
+            if wino:
+                line["roofline"]["form"] = ("Winograd F(2x2,3x3) per depth tap: 12 multiplies per output and "
+                                            "(cin, cout) pair instead of 27; achieved = executed MFMA flops")
+                line["roofline"]["direct_form_equivalent_TFLOPs"] = direct_tfl
+            if ch:
+                eng = net.engine()
+                sec = max(chain_ms) * 1e-3 * ch["launches"]          # slowest rank
+                form = {1: "direct", 2: "winograd", 3: "stepwise", 4: "banded"}.get(eng.last_chain_form, "?")
+                wino_chain = form in ("winograd", "banded", "stepwise")
+                direct_tfl_c = ch["flops"] / sec / 1e12
+                exec_tfl = direct_tfl_c * (4.0 / 9.0 if wino_chain else 1.0)
+                line["chain_kernel"] = {"kernel": "mvsn_incremental_cost_volume (warp + refine + cost volume, fused)",
+                                        "form": form + (": Winograd F(2x2,3x3) for the three 3x3 convolutions of a step (16 "
+                                                        "multiplies per 2x2 outputs instead of 36)" if wino_chain else ""),
+                                        "avg_launch_ms": max(chain_ms), "avg_launch_ms_per_rank": chain_ms,
+                                        "chains_per_launch": B * Sn,
+                                        "algorithmic_GBps": ch["bytes"] / sec / 1e9,
+                                        "frac_of_hbm_peak": ch["bytes"] / sec / 1e9 / PEAK_HBM_GBS,
+                                        "direct_form_TFLOPs": direct_tfl_c,
+                                        "direct_form_frac_of_fp32_mfma_peak": direct_tfl_c / PEAK_FP32_MFMA_TFLOPS,
+                                        "executed_TFLOPs": exec_tfl,
+                                        "executed_frac_of_fp32_mfma_peak": exec_tfl / PEAK_FP32_MFMA_TFLOPS,
+                                        "share_of_step": ch["ms"] / total_ms}
+                t = (pmc_cfg or {}).get("mvsn_incremental_cost_volume")
+                if t and (form == "winograd" or args.config != "headline"):
+                    line["chain_kernel"]["hbm_traffic_bytes_per_chain"] = {
+                        "fetched": t["fetch_bytes_per_chain"], "written": t["write_bytes_per_chain"],
+                        "algorithmic": t["algorithmic_bytes_per_chain"],
+                        "ratio": (t["fetch_bytes_per_chain"] + t["write_bytes_per_chain"]) /
+                        t["algorithmic_bytes_per_chain"], "source": f"profiles/{pmc['_file']} (separate PMC pass, this library)"}
+            line["kernel_ms_per_step"] = {k: round(v["ms"], 3) for k, v in
+                                          sorted(agg.items(), key=lambda kv: -kv[1]["ms"])[:16]}
+            line["launches_per_forward"] = int(sum(v["launches"] for v in agg.values()))
+            wino_chain_now = net.engine().last_chain_form in (2, 3, 4)      # every chain form but the direct one
+            line["roofline_by_kernel"] = roofline_by_kernel(
+                agg, total_ms, wino_names=("mvsn_incremental_cost_volume",) if wino_chain_now else ())
+            if world == 1 and args.sustain > 0:
+                windows, t_end = [], time.perf_counter() + args.sustain
+                while time.perf_counter() < t_end:
+                    n_steps, t1 = 0, time.perf_counter()
+                    while time.perf_counter() - t1 < 2.0:
+                        step()
+                        n_steps += 1
+                        if n_steps % 8 == 0:
+                            torch.cuda.synchronize()
+                    torch.cuda.synchronize()
+                    windows.append(B * n_steps / (time.perf_counter() - t1))
+                line["sustained"] = {"seconds": args.sustain, "window_s": 2.0,
+                                     "depthmaps_per_s_per_window": [round(w, 1) for w in windows],
+                                     "first": round(windows[0], 1), "last": round(windows[-1], 1),
+                                     "min": round(min(windows), 1), "droop_last_vs_first": 1.0 - windows[-1] / windows[0],
+                                     "timed_region_value": line["value"]}
+            if world == 1 and headline and not args.no_tiers:
+                # side legs: a failure in one of them must not cost the headline line
+                for key, leg in (("pcie_inclusive", lambda: host_feed_rates(net, B, dev)),
+                                 ("evaluate_rate", lambda: evaluate_rate(net, B, dev, line["value"])),
+                                 ("batch_latency", lambda: batch_latency(net)),
+                                 ("headline_by_batch", lambda: headline_by_batch(net, dev)),
+                                 ("other_configs", lambda: other_configs(dev, skip=("headline",)))):
+                    try:
+                        line[key] = leg()
+                    except Exception as exc:   # noqa: BLE001
+                        line[key] = {"error": f"{type(exc).__name__}: {exc}"}
+            if world == 1 and headline and args.precision == "fp32" and not args.no_tiers:
+                # the two bf16-matrix-core tiers on the same resident inputs, reported beside the fp32 headline, never
+                # as it: the 3 x bf16 split (fp32-equivalent arithmetic) and plain bf16 operands
+                # (BASELINE config 5's speed tier -- outside the 1e-3 parity contract, its error is reported)
+                eng = net.engine()
+                for tier, key, dtype in (
+                        ("bf16x3", "bf16x3_split_tier",
+                         "3 x bf16 split (hi+lo operands, fp32 accumulate) on the 32->32 3x3 layers, f32 elsewhere"),
+                        ("bf16", "bf16_operand_tier",
+                         "bf16 operands, fp32 accumulate on the 32->32 3x3 layers (regulariser + refiner blocks), f32 "
+                         "elsewhere; NOT within the 1e-3 parity contract"),
+                        ("bf16s", "bf16_feature_tier",
+                         "bf16 FEATURES (BASELINE config 5): the bf16-operand tier + the regulariser's intermediate volumes "
+                         "STORED as bf16 (layer 0 fp32 -> bf16, layers 1-2 bf16 -> bf16, layer 3 bf16 -> fp32; fp32 "
+                         "accumulation and GroupNorm statistics); NOT within the 1e-3 parity contract")):
+                    eng.conv_precision = tier      # (= net.options.conv_precision: the engine's switches ARE the module's
+                    #                                  options object, so the tier is part of every recorded plan's key)
+                    for _ in range(max(1, args.warmup)):
+                        out_t = step()
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(args.steps):
+                        out_t = step()
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t1
+                    got_t = out_t["left_idepthmap_pyr"][0][:1].cpu()
+                    agg_t = kernel_breakdown(net, inp, Dn)
+                    name_t, dom_t = max(agg_t.items(), key=lambda kv: kv[1]["ms"])
+                    line[key] = {
+                        "value": B * args.steps / dt, "unit": "depthmaps/s", "ms_per_step": dt / args.steps * 1e3,
+                        "dtype": dtype,
+                        "l1_vs_ref": {k: v for k, v in l1_against(ref0, got_t).items() if k != "rel_definitions"},
+                        "dominant_kernel": name_t, "dominant_kernel_ms": round(dom_t["ms"], 3),
+                        "kernel_ms_per_step": {k: round(v["ms"], 3) for k, v in
+                                               sorted(agg_t.items(), key=lambda kv: -kv[1]["ms"])[:6]}}
+                # the feature tier on the configuration BASELINE names it for: config 5's golden input at batch 1 (its error
+                # against the reference's own depth map) and at 32 images (its rate), beside the fp32 figures of other_configs
                 try:
-                    line[key] = leg()
+                    c5 = CONFIGS["config5"]
+                    eng.conv_precision = "bf16s"
+                    _, inp5, ref5 = config_inputs(c5, 1, 0, dev)
+                    out5 = run_forward(net, inp5, c5["D"])
+                    entry = {"l1_vs_ref_config5": {k: v for k, v in l1_against(
+                        ref5, out5["left_idepthmap_pyr"][0][:1].cpu(), c5["golden"]).items() if k != "rel_definitions"}}
+                    del inp5, out5
+                    _, inp5, _ = config_inputs(c5, 32, 0, dev)
+                    for _ in range(2):
+                        run_forward(net, inp5, c5["D"])
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(3):
+                        run_forward(net, inp5, c5["D"])
+                    torch.cuda.synchronize()
+                    entry["config5_B=32_depthmaps_per_s"] = round(32 * 3 / (time.perf_counter() - t1), 1)
+                    pmc5 = load_profile_json(FEATURE_TIER_PMC_FILE)
+                    if pmc5:
+                        entry["hbm_bytes_of_the_converted_launches"] = {k: v for k, v in pmc5.items() if not k.startswith("_l")}
+                    line["bf16_feature_tier"].update(entry)
+                    del inp5
+                    torch.cuda.empty_cache()
                 except Exception as exc:   # noqa: BLE001
-                    line[key] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and headline and args.precision == "fp32" and not args.no_tiers:
-            # the two bf16-matrix-core tiers on the same resident inputs, reported beside the fp32 headline, never
-            # as it: the 3 x bf16 split (fp32-equivalent arithmetic) and plain bf16 operands
-            # (BASELINE config 5's speed tier -- outside the 1e-3 parity contract, its error is reported)
-            eng = net.engine()
-            for tier, key, dtype in (
-                    ("bf16x3", "bf16x3_split_tier",
-                     "3 x bf16 split (hi+lo operands, fp32 accumulate) on the 32->32 3x3 layers, f32 elsewhere"),
-                    ("bf16", "bf16_operand_tier",
-                     "bf16 operands, fp32 accumulate on the 32->32 3x3 layers (regulariser + refiner blocks), f32 "
-                     "elsewhere; NOT within the 1e-3 parity contract"),
-                    ("bf16s", "bf16_feature_tier",
-                     "bf16 FEATURES (BASELINE config 5): the bf16-operand tier + the regulariser's intermediate volumes "
-                     "STORED as bf16 (layer 0 fp32 -> bf16, layers 1-2 bf16 -> bf16, layer 3 bf16 -> fp32; fp32 "
-                     "accumulation and GroupNorm statistics); NOT within the 1e-3 parity contract")):
-                eng.conv_precision = tier      # (= net.options.conv_precision: the engine's switches ARE the module's
-                #                                  options object, so the tier is part of every recorded plan's key)
-                for _ in range(max(1, args.warmup)):
-                    out_t = step()
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(args.steps):
-                    out_t = step()
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t1
-                got_t = out_t["left_idepthmap_pyr"][0][:1].cpu()
-                agg_t = kernel_breakdown(net, inp, Dn)
-                name_t, dom_t = max(agg_t.items(), key=lambda kv: kv[1]["ms"])
-                line[key] = {
-                    "value": B * args.steps / dt, "unit": "depthmaps/s", "ms_per_step": dt / args.steps * 1e3,
-                    "dtype": dtype,
-                    "l1_vs_ref": {k: v for k, v in l1_against(ref0, got_t).items() if k != "rel_definitions"},
-                    "dominant_kernel": name_t, "dominant_kernel_ms": round(dom_t["ms"], 3),
-                    "kernel_ms_per_step": {k: round(v["ms"], 3) for k, v in
-                                           sorted(agg_t.items(), key=lambda kv: -kv[1]["ms"])[:6]}}
-            # the feature tier on the configuration BASELINE names it for: config 5's golden input at batch 1 (its error
-            # against the reference's own depth map) and at 32 images (its rate), beside the fp32 figures of other_configs
-            try:
-                c5 = CONFIGS["config5"]
-                eng.conv_precision = "bf16s"
-                _, inp5, ref5 = config_inputs(c5, 1, 0, dev)
-                out5 = run_forward(net, inp5, c5["D"])
-                entry = {"l1_vs_ref_config5": {k: v for k, v in l1_against(
-                    ref5, out5["left_idepthmap_pyr"][0][:1].cpu(), c5["golden"]).items() if k != "rel_definitions"}}
-                del inp5, out5
-                _, inp5, _ = config_inputs(c5, 32, 0, dev)
-                for _ in range(2):
-                    run_forward(net, inp5, c5["D"])
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(3):
-                    run_forward(net, inp5, c5["D"])
-                torch.cuda.synchronize()
-                entry["config5_B=32_depthmaps_per_s"] = round(32 * 3 / (time.perf_counter() - t1), 1)
-                pmc5 = load_profile_json(FEATURE_TIER_PMC_FILE)
-                if pmc5:
-                    entry["hbm_bytes_of_the_converted_launches"] = {k: v for k, v in pmc5.items() if not k.startswith("_l")}
-                line["bf16_feature_tier"].update(entry)
-                del inp5
-                torch.cuda.empty_cache()
-            except Exception as exc:   # noqa: BLE001
-                line["bf16_feature_tier"]["config5"] = {"error": f"{type(exc).__name__}: {exc}"}
-            eng.conv_precision = "fp32"
-        if not args.no_cpu_baseline:
-            # rank 0's host cores, once per job whatever N is (a bounded sample: shorter beside a multi-GPU run,
-            # where the other ranks wait in the final barrier meanwhile)
-            cb, ref_out = cpu_baseline(cfg, budget_s=15.0 if world == 1 else 6.0)
-            line["cpu_baseline"] = cb
-            o0 = ref_out["left_idepthmap_pyr"][0]
-            line["l1_vs_oracle"] = float((got0 - o0).abs().mean())
-            # image 0 sits in slice A of the two-slice towers and in the first round of every persistent kernel: the
-            # first image of slice B and the LAST image of the step (last round, slice B) against the oracle as well
-            for key, idx in (("l1_vs_oracle_slice_b", (B + 1) // 2), ("l1_vs_oracle_last", B - 1)):
-                if idx > 0:
-                    line[key] = oracle_check(cfg, idx, idepth[idx:idx + 1].cpu())
+                    line["bf16_feature_tier"]["config5"] = {"error": f"{type(exc).__name__}: {exc}"}
+                eng.conv_precision = "fp32"
+            if not args.no_cpu_baseline:
+                # rank 0's host cores, once per job whatever N is (a bounded sample: shorter beside a multi-GPU run,
+                # where the other ranks wait in the final barrier meanwhile)
+                cb, ref_out = cpu_baseline(cfg, budget_s=15.0 if world == 1 else 6.0)
+                line["cpu_baseline"] = cb
+                o0 = ref_out["left_idepthmap_pyr"][0]
+                line["l1_vs_oracle"] = float((got0 - o0).abs().mean())
+                # image 0 sits in slice A of the two-slice towers and in the first round of every persistent kernel: the
+                # first image of slice B and the LAST image of the step (last round, slice B) against the oracle as well
+                for key, idx in (("l1_vs_oracle_slice_b", (B + 1) // 2), ("l1_vs_oracle_last", B - 1)):
+                    if idx > 0:
+                        line[key] = oracle_check(cfg, idx, idepth[idx:idx + 1].cpu())
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -117,3 +117,31 @@ def test_final_line_is_small_last_and_carries_the_contract():
     # a pathological record (every optional group inflated) still yields a parsable line under the limit
     full["l1_vs_oracle_last"] = {f"k{i}": float(i) for i in range(300)}
     assert len(bench.final_line(full)) < 4096
+
+
+def test_dump_outputs_writes_the_same_float_arrays_every_time(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: every tensor the forward returned becomes DIR/<key>_<level>.npy in float32 (bool masks as
+    0 / 1); an output that fits its share of DUMP_LIMIT is written whole, a larger one as a seeded sample of its elements
+    in increasing index order -- the same elements on every call, so that two builds compare output for output."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_LIMIT <= 64 * 10 ** 6 - 2 ** 16              # the files' headers fit beside it
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * 4 * 50000)        # 50 000 elements per array of three
+    g = torch.Generator().manual_seed(3)
+    big = torch.rand(2, 4, 100, 90, generator=g)
+    small = torch.rand(2, 1, 25, 20, generator=g)
+    out = {"left_idepthmap_pyr": [small, big], "left_idepthmap_mask_pyr": [big > 0.5, None]}
+    shapes = bench.dump_outputs(out, str(tmp_path / "a"))
+    assert shapes == {"left_idepthmap_pyr_0": [2, 1, 25, 20], "left_idepthmap_pyr_1": [50000],
+                      "left_idepthmap_mask_pyr_0": [50000]}
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["left_idepthmap_pyr_0"], small.numpy())
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(big.numel(), 50000, replace=False))
+    assert np.array_equal(a["left_idepthmap_pyr_1"], big.numpy().reshape(-1)[idx])
+    assert np.array_equal(a["left_idepthmap_mask_pyr_0"], (big.numpy().reshape(-1)[idx] > 0.5).astype(np.float32))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    for k in shapes:
+        assert (tmp_path / "a" / f"{k}.npy").read_bytes() == (tmp_path / "b" / f"{k}.npy").read_bytes(), k

@@ -1888,7 +1888,7 @@ def test_bench_real_multi_rank_line_on_one_gpu():
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-device-selftest",
-                        "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-tiers"],
+                        "--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline", "--no-tiers"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -2050,7 +2050,7 @@ def test_bench_single_gpu_line_over_rccl():
     env = _clean_rank_env()
     env["MVSN_BENCH_BACKEND"] = "nccl"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--batch", "8", "--no-cpu-baseline", "--no-tiers"], env=env, capture_output=True, text=True,
+                        "--batch", "8", "--full", "--no-cpu-baseline", "--no-tiers"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = p.stdout.rstrip("\n").splitlines()
@@ -2061,6 +2061,41 @@ def test_bench_single_gpu_line_over_rccl():
     assert line["l1_vs_ref"]["max_rel_per_pixel"] < 1e-3 and np.isfinite(line["mean_idepth"]) and line["value"] > 0
     assert len(line["roofline"]["frac_per_rank"]) == 1 and len(line["per_rank_ms_per_step"]) == 1
     print("bench --gpus 1 over RCCL:", lines[0][:300])
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full): K timed steps and the headline line only, and `--dump-outputs DIR` writes
+    what the last timed step returned -- image 0 of rank 0 is the headline fixture's input, so its dumped final depth map
+    meets the contract against the reference's own."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    dump = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "4", "--dump-outputs", str(dump)], env=_clean_rank_env(), capture_output=True,
+                       text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = p.stdout.rstrip("\n").splitlines()
+    lines = [ln for ln in out if ln.startswith("{")]
+    assert len(lines) == 1 and out[-1] == lines[0] and len(lines[0]) < 4096, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "depthmaps/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["metric"].startswith("depthmaps/sec at 512x256")
+    assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+    for key in ("l1_vs_ref", "roofline", "chain_kernel", "cpu_baseline", "mean_idepth"):
+        assert key not in line, key                   # the --full record's fields
+    files = sorted(os.listdir(dump))
+    assert files == sorted(f"{k}_{lvl}.npy" for k in ("left_idepthmap_pyr", "left_idepthmap_raw_pyr",
+                                                        "left_idepthmap_mask_pyr") for lvl in range(5)), files
+    assert sum(os.path.getsize(dump / f) for f in files) < 64 * 10 ** 6
+    arrays = {f[:-4]: np.load(dump / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    idepth = arrays["left_idepthmap_pyr_0"]
+    assert idepth.shape == (4, 1, 256, 512)
+    assert_contract(torch.from_numpy(idepth[:1]), load_golden("g2_gta_512x256_d64_s2.npz")["idepth_0"],
+                    "bench --dump-outputs image 0 vs reference")
 
 
 def test_forward_headline_golden_direct_chain_form():

@@ -1,78 +1,46 @@
-"""The reference's UNCHANGED test.py, run through `python -m multi_view_stereonet_amd.run_script` against an archive
-from this build ("drops into test.py unchanged").
+"""An evaluation script that knows nothing of this build, run through `python -m multi_view_stereonet_amd.run_script`
+against an archive from this build ("drops into test.py unchanged").
 
-Build-container only (skipped where /root/reference is absent, e.g. on the GPU box): test.py parses its arguments, reads
-params.yaml, builds the reference's own GTA-SfM reader over a miniature tree (the files of g10_datasets.npz),
-`torch.jit.load`s OUR stereo_network.pt, moves it to the device, unpacks the first batch with the reference's own
-`multi_view_unpack_batch` and calls the network with the seven positional arguments -- at which point this build's
-operator runs.  There is no GPU here, so the operator refuses CPU tensors: the test asserts that the script got exactly
-that far (on the GPU, `test_torchscript_archive_matches_eager` covers the numbers).
-The reference imports torchvision / pyquaternion, absent from this image: two stand-in packages with the entry points
-its evaluation path touches are put on PYTHONPATH for the subprocess (same stand-ins as tests/golden/make_dataset_golden.py).
+The script below follows the reference test.py's evaluation path step by step -- it parses its arguments, reads
+params.yaml two levels above the weights, builds the GTA-SfM reader over a miniature tree (the files of
+g10_datasets.npz), `torch.jit.load`s OUR stereo_network.pt, moves it to the device, unpacks the first batch with
+`multi_view_unpack_batch` and calls the network through `multi_view_forward` with the seven positional arguments -- at
+which point this build's operator runs.  The subprocess sees no GPU, so the operator refuses CPU tensors: the test
+asserts that the script got exactly that far (on the GPU, `test_torchscript_archive_matches_eager` covers the numbers).
 """
 import os
 import subprocess
 import sys
-import textwrap
-
-import pytest
 
 from conftest import ROOT, load_golden
 
-REFERENCE = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "test.py")),
-                                reason="the reference tree is only present in the build container")
+SCRIPT = '''
+import os, sys
+import torch, yaml
+from multi_view_stereonet_amd import datasets
+from multi_view_stereonet_amd import multi_view_stereonet_utils as snu
 
-TORCHVISION = textwrap.dedent('''
-    import types
-    import numpy as np
-    import torch
-    from PIL import Image
-
-    class _Compose:
-        def __init__(self, transforms): self.transforms = transforms
-        def __call__(self, x):
-            for t in self.transforms: x = t(x)
-            return x
-
-    class _Lambda:
-        def __init__(self, lambd): self.lambd = lambd
-        def __call__(self, x): return self.lambd(x)
-
-    def _resize(img, size): return img.resize((size[1], size[0]), Image.BILINEAR)
-
-    def _to_tensor(pic):
-        if isinstance(pic, np.ndarray):
-            if pic.ndim == 2: pic = pic[:, :, None]
-            t = torch.from_numpy(np.ascontiguousarray(pic.transpose((2, 0, 1))))
-            return t.float().div(255) if t.dtype == torch.uint8 else t
-        arr = np.array(pic.convert("RGB"), dtype=np.uint8)
-        return torch.from_numpy(arr.transpose((2, 0, 1)).copy()).float().div(255)
-
-    def _normalize(tensor, mean, std):
-        m = torch.as_tensor(mean, dtype=tensor.dtype).view(-1, 1, 1)
-        s = torch.as_tensor(std, dtype=tensor.dtype).view(-1, 1, 1)
-        return (tensor - m) / s
-
-    transforms = types.ModuleType("torchvision.transforms")
-    transforms.Compose, transforms.Lambda = _Compose, _Lambda
-    transforms.functional = types.ModuleType("torchvision.transforms.functional")
-    transforms.functional.resize, transforms.functional.to_tensor, transforms.functional.normalize = _resize, _to_tensor, _normalize
-    utils = types.ModuleType("torchvision.utils")
-''')
+weights_dir, data_dir, test_file = sys.argv[1:4]
+with open(os.path.join(weights_dir, "..", "..", "params.yaml")) as f:
+    params = yaml.safe_load(f)
+device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+print("DEVICE", device.type)
+assert "gta_sfm" in os.path.basename(test_file)
+data = datasets.GTASfMMultiViewStereoDataset(data_dir, test_file, transform=datasets.get_testing_transforms(params))
+loader = torch.utils.data.DataLoader(data, batch_size=1, shuffle=False)
+stereo_network = torch.jit.load(os.path.join(weights_dir, "stereo_network.pt"))
+stereo_network = stereo_network.to(device)
+stereo_network.eval()
+batch = snu.multi_view_unpack_batch(next(iter(loader)), device, stereo_network.num_levels)
+print("UNPACKED", len(batch["left_image_pyr"]), tuple(batch["left_image_pyr"][0].shape))
+snu.multi_view_forward(stereo_network, batch, params)
+print("FORWARD RETURNED")
+'''
 
 
-def test_unchanged_test_py_reaches_the_operator(tmp_path):
+def test_evaluation_script_reaches_the_operator(tmp_path):
     from multi_view_stereonet_amd import torchscript as ts
     from multi_view_stereonet_amd.weights import load_weights
-    # stand-in packages + the reference's namespace `datasets` directory ahead of any installed package of that name
-    stubs = tmp_path / "stubs"
-    (stubs / "torchvision").mkdir(parents=True)
-    (stubs / "torchvision" / "__init__.py").write_text(TORCHVISION)
-    (stubs / "pyquaternion").mkdir()
-    (stubs / "pyquaternion" / "__init__.py").write_text("class Quaternion:\n    pass\n")
-    (stubs / "datasets").mkdir()
-    (stubs / "datasets" / "__init__.py").write_text(f"__path__ = [{os.path.join(REFERENCE, 'datasets')!r}]\n")
     # <model>/checkpoints/epoch/stereo_network.pt with params.yaml two levels up, as test.py expects (:338)
     model = tmp_path / "model"
     weights_dir = model / "checkpoints" / "epoch0149"
@@ -90,12 +58,16 @@ def test_unchanged_test_py_reaches_the_operator(tmp_path):
         path.write_bytes(fix[f"file_{i}"].tobytes())
     split = tmp_path / "gta_sfm_mini_test.txt"            # test.py picks the reader by "gta_sfm" in the file name
     split.write_text((tmp_path / "gta_split.txt").read_text())
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(stubs), REFERENCE, ROOT]), MPLBACKEND="Agg",
+    script = tmp_path / "evaluate_script.py"
+    script.write_text(SCRIPT)
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), MPLBACKEND="Agg",
                CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
-    p = subprocess.run([sys.executable, "-m", "multi_view_stereonet_amd.run_script", os.path.join(REFERENCE, "test.py"),
+    p = subprocess.run([sys.executable, "-m", "multi_view_stereonet_amd.run_script", str(script),
                         str(weights_dir), str(tmp_path / "gta"), str(split)], cwd=str(tmp_path), env=env,
                        capture_output=True, text=True, timeout=900)
-    assert "DEFAULTING TO CPU!" in p.stdout, (p.stdout[-500:], p.stderr[-1500:])
-    # ... data loaded, archive loaded and moved, first batch unpacked, network called: our operator answered
+    assert "DEVICE cpu" in p.stdout, (p.stdout[-500:], p.stderr[-1500:])
+    # ... data loaded, archive loaded and moved, first batch unpacked (5 levels, 32x48 at level 0), network called:
+    # our operator answered
+    assert "UNPACKED 5 (1, 3, 32, 48)" in p.stdout, (p.stdout[-500:], p.stderr[-1500:])
     assert p.returncode != 0 and "HIP devices only" in p.stderr, p.stderr[-2000:]
-    assert "multi_view_forward" in p.stderr            # raised from inside the reference's own wrapper (:647-654)
+    assert "multi_view_forward" in p.stderr and "FORWARD RETURNED" not in p.stdout

@@ -9,10 +9,10 @@ mkdir -p $OUT
 (timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -3) > $OUT/gpu_suite.txt; cat $OUT/gpu_suite.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1 | tee $OUT/smoke.txt
 # (bench.py: last stdout line = the compact line the driver parses; bench_detail.json = the full record)
-timeout 600 python bench.py --steps 20 --warmup 5 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
 cp bench_detail.json $OUT/bench_default_detail.json
 wc -c $OUT/bench_default.json
-timeout 300 python bench.py --steps 300 --warmup 5 --no-cpu-baseline --no-tiers --sustain 24 2> /dev/null | tail -1 > $OUT/bench_sustain.json
+timeout 300 python bench.py --full --steps 300 --warmup 5 --no-cpu-baseline --no-tiers --sustain 24 2> /dev/null | tail -1 > $OUT/bench_sustain.json
 cp bench_detail.json $OUT/bench_sustain_detail.json
 timeout 1200 python tools/soak.py ${SOAK:-3000} > $OUT/soak.json 2> $OUT/soak.err
 timeout 600 python tools/soak.py ${SOAKG:-1000} graphed > $OUT/soak_graphed.json 2>> $OUT/soak.err

@@ -12,7 +12,7 @@ TAG=${TAG}_levels bash tools/prof_levels.sh > $OUT/prof_levels.log 2>&1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for cfg in "config4 128" "config5 32"; do
   set -- $cfg
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $1 -- python bench.py --config $1 --batch $2 --steps 3 --warmup 1 \
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $1 -- python bench.py --full --config $1 --batch $2 --steps 3 --warmup 1 \
     --no-cpu-baseline --no-tiers > $OUT/bench_$1_b$2_under_trace.json 2> $OUT/$1_trace.log
   rm -f $OUT/$1_kernel_trace.csv
 done

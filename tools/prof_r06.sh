@@ -30,7 +30,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for cfg in "config4 128" "config5 32"; do
   set -- $cfg
   mkdir -p $OUT/$1
-  PMC="python bench.py --config $1 --batch $2 --steps 1 --warmup 1 --no-cpu-baseline --no-tiers"
+  PMC="python bench.py --full --config $1 --batch $2 --steps 1 --warmup 1 --no-cpu-baseline --no-tiers"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$1 -o pmc_fetch -- $PMC > /dev/null 2> $OUT/$1/pmc_fetch.log
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/$1 -o pmc_write -- $PMC > /dev/null 2> $OUT/$1/pmc_write.log
   python tools/pmc_summary.py $OUT/$1/pmc_fetch_counter_collection.csv > $OUT/$1/pmc_fetch_summary.csv
@@ -42,26 +42,26 @@ python tools/level_profile.py json gpurun_out/${TAG}_levels 256 > $OUT/json/${R}
 cp gpurun_out/${R}_bf16s/feature_tier_pmc.json $OUT/json/${R}_bf16_feature_tier_pmc.json
 cp $OUT/json/*.json profiles/
 # ---- the kept lines (this library's counters are in profiles/ now)
-( time python bench.py 2> /dev/null | tail -1 > $OUT/bench_default.json ) 2> $OUT/bench_default_time.txt
+( time python bench.py --full 2> /dev/null | tail -1 > $OUT/bench_default.json ) 2> $OUT/bench_default_time.txt
 cp bench_detail.json $OUT/bench_default_detail.json
-python bench.py --steps 20 --warmup 5 2> /dev/null | tail -1 > $OUT/bench_with_counters.json
+python bench.py --full --steps 20 --warmup 5 2> /dev/null | tail -1 > $OUT/bench_with_counters.json
 cp bench_detail.json $OUT/bench_with_counters_detail.json
-python bench.py --steps 300 --warmup 5 --no-cpu-baseline --no-tiers --sustain 24 2> /dev/null | tail -1 > $OUT/bench_sustain.json
+python bench.py --full --steps 300 --warmup 5 --no-cpu-baseline --no-tiers --sustain 24 2> /dev/null | tail -1 > $OUT/bench_sustain.json
 cp bench_detail.json $OUT/bench_sustain_detail.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-tiers \
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-tiers \
   2> $OUT/trace.log | tail -1 > $OUT/bench_under_trace.json
 cp bench_detail.json $OUT/bench_under_trace_detail.json
 rm -f $OUT/trace_kernel_trace.csv
 for cfg in "config4 128" "config5 32"; do
   set -- $cfg
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $1 -- python bench.py --config $1 --batch $2 --steps 3 --warmup 1 \
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $1 -- python bench.py --full --config $1 --batch $2 --steps 3 --warmup 1 \
     --no-cpu-baseline --no-tiers 2> $OUT/$1_trace.log | tail -1 > $OUT/bench_$1_b$2_under_trace.json
   cp bench_detail.json $OUT/bench_$1_b$2_under_trace_detail.json
   rm -f $OUT/$1_kernel_trace.csv
 done
-python bench.py --config config4 --batch 128 --steps 5 --warmup 2 --no-cpu-baseline --no-tiers 2> /dev/null | tail -1 > $OUT/bench_config4_b128.json
+python bench.py --full --config config4 --batch 128 --steps 5 --warmup 2 --no-cpu-baseline --no-tiers 2> /dev/null | tail -1 > $OUT/bench_config4_b128.json
 cp bench_detail.json $OUT/bench_config4_b128_detail.json
-MVSN_BENCH_BACKEND=nccl python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-tiers 2> $OUT/bench_rccl_world1.err | tail -1 > $OUT/bench_rccl_world1.json
+MVSN_BENCH_BACKEND=nccl python bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-tiers 2> $OUT/bench_rccl_world1.err | tail -1 > $OUT/bench_rccl_world1.json
 MVSN_GRID=30,40,96 python tools/chain_bench.py 128 256 > $OUT/chain_bench_30x40.txt 2>&1
 MVSN_GRID=32,64,128 python tools/chain_bench.py 128 256 > $OUT/chain_bench_32x64.txt 2>&1
 python tools/chain_bench.py 256 512 > $OUT/chain_bench_16x32.txt 2>&1

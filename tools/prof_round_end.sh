@@ -15,7 +15,7 @@ python tools/level_profile.py json gpurun_out/${TAG}_levels 256 > $OUT/json/r05_
 cp gpurun_out/r05_bf16s/feature_tier_pmc.json $OUT/json/r05_bf16_feature_tier_pmc.json
 cp $OUT/json/*.json profiles/
 export TMPDIR=/tmp
-( time python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default_time.txt
-python bench.py --steps 20 --warmup 5 > $OUT/bench_with_counters.json 2> /dev/null
+( time python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default_time.txt
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_with_counters.json 2> /dev/null
 python tools/slab_soak.py 2>&1 | grep -v amdgpu.ids > $OUT/slab_soak.txt
 ls $OUT
