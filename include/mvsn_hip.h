@@ -533,6 +533,11 @@ int mvsn_gather_strided(const float *src, int count, long stride, float *dst, mv
  * half-split plan is compared with it bit for bit); set it before asking for the workspace size. */
 int mvsn_debug_set_band_flags(int flags);
 
+/* Test hook: which tiles the dilated 3x3 Winograd layers walk.  0 (default) = row-phase items wherever they take no
+ * more work items than the square tiles, 1 = row-phase items on every dilated 2-D layer, 2 = square tiles only.  The
+ * outputs and GroupNorm statistics are the same bits either way.  Returns the previous value. */
+int mvsn_debug_set_wino_rowphase(int mode);
+
 /* Device self-test of the MFMA fragment mapping the conv kernels rely on (A = 16x4, B = 4x16
  * fp32, asymmetric operands); returns 0 when the on-device result matches the scalar product. */
 int mvsn_selftest_mfma(mvsn_stream_t stream);

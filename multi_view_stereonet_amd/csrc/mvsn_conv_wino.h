@@ -15,10 +15,13 @@ struct WinoGeom {
   int wide;   // volume form on planes 32 < W <= 40 columns wide: 1 = tiles of 10 rows x the whole width, 2 = rolling strips
               // of six patch rows through the sample's planes (`tiles` = items per SAMPLE there; see conv_wino_kernel)
   int nty, ntx, tiles, nchunks;
+  int rpy;    // dilated 2-D layers on row-phase items: tile rows per row phase (0: square tiles; see conv_wino_kernel)
   size_t packed_floats;
 };
-// work items (one per workgroup visit, 32 GroupNorm records each) of a sample
+// GroupNorm record blocks (32 records each) of a sample: one per square tile (per plane), whatever items the launch walks
 inline long wino_items(const WinoGeom &g) { return g.wide == 2 ? (long)g.tiles : (long)g.D * g.tiles; }
+// work items (one per workgroup visit) of a sample: row-phase items (dil x rpy x ntx) or the record blocks
+inline long wino_work_items(const WinoGeom &g) { return g.rpy ? (long)g.dil * g.rpy * g.ntx : wino_items(g); }
 
 bool wino_geom(const mvsn_conv_desc *d, WinoGeom *g);
 int wino_pack(const mvsn_conv_desc *d, const float *weight, float *packed, hipStream_t stream);

@@ -52,10 +52,11 @@ constexpr int WN_TY = 16, WN_TX = 32;                  // output tile
 // 4 x 4 samples at stride DIL)
 constexpr int wn_pa(int dil) { return (dil + 3) / 4 * 4; }                 // halo rounded up to 16-byte columns
 constexpr int wn_xs(int dil) { return WN_TX + 2 * wn_pa(dil); }            // row stride: columns x0 - pa .. x0 + 31 + pa
-constexpr int wn_hy(int dil) { return WN_TY + 2 * dil; }                   // haloed rows
-constexpr int wn_groups(int dil) { return wn_hy(dil) * (wn_xs(dil) / 4); } // 16-byte groups per channel tile
-constexpr int wn_pieces(int dil) { return (wn_groups(dil) + 63) / 64; }    // DMA instructions per channel
-constexpr int wn_rcst(int dil) { return wn_hy(dil) * wn_xs(dil) + 16; }    // raw channel stride (floats)
+// (rp: row-phase items of a dilated layer, see conv_wino_kernel's RP -- 18 rows at stride dil)
+constexpr int wn_hy(int dil, bool rp = false) { return WN_TY + 2 * (rp ? 1 : dil); }                   // haloed rows
+constexpr int wn_groups(int dil, bool rp = false) { return wn_hy(dil, rp) * (wn_xs(dil) / 4); } // 16-byte groups per channel tile
+constexpr int wn_pieces(int dil, bool rp = false) { return (wn_groups(dil, rp) + 63) / 64; }    // DMA instructions per channel
+constexpr int wn_rcst(int dil, bool rp = false) { return wn_hy(dil, rp) * wn_xs(dil) + 16; }    // raw channel stride (floats)
 constexpr int WN_UFLOATS = 16 * 128;                   // U fragments per chunk: [xi][cout tile][lane]
 constexpr int WN_MAX_CHUNKS = 9;                       // resident U: up to 36 input channels (72 KB)
 
@@ -209,6 +210,7 @@ struct WinoArgs {
   int D;   // planes per sample (volume form; 1 for the 2-D layers)
   int pr;  // WIDE == 2: patch rows per plane, (H + 1) / 2 (there `tiles` = work items per SAMPLE, see conv_wino_kernel)
   WinoDiv fd_pr;
+  int nty, rpy;   // RP: square tile rows (the GroupNorm records' layout) / item rows per row phase
 };
 
 // A normalise / activate / add pass over ANOTHER tensor that this launch's waves carry along (template RIDE = 256-float
@@ -285,12 +287,24 @@ constexpr int WN_ROLL_PR = 6, WN_ROLL_NP = WN_ROLL_PR * WN_WIDE_PC, WN_ROLL_HY =
 //         stage's adds: 24 VALU instructions per patch and channel instead of 32, no extra instruction.  The edge lanes'
 //         missing neighbours are columns -1 and 32, i.e. the zero padding -- exactly what bound_ctrl:0 supplies -- which
 //         is why the form needs the tile to span the plane.  Same operands, same operations: bit-identical results.
+// TILE    the tile form: 0 = 16 x 32 tiles, 1 / 2 = WIDE 1 / 2 above, WN_TILE_RP = RP below
+// RP      (dilated 2-D layers) ROW-PHASE items: image rows y = rho + DIL i split into DIL row phases rho; an item is 16
+//         consecutive rows i0 .. i0 + 15 of ONE phase x 32 columns (item t of a sample: column tile t % ntx, phase
+//         (t / ntx) % DIL, phase tile row t / (ntx DIL)).  Vertically the layer becomes a dilation-1 problem on the phase:
+//         the raw tile is the 18 rows rho + DIL (i0 - 1 .. i0 + 16) (each a contiguous run of 16-byte groups: the DMA plan
+//         only strides its rows) x the 32 + 2 PA columns as before, 18 x 40 at dilations 2 and 4 -- dilation 1's geometry,
+//         3 pieces per channel instead of 4 -- and 18 x 48 at dilation 8 (4 instead of 6).  The smaller ring leaves room
+//         for two k-steps per step at every dilation.  Horizontally nothing changes.  Patch row w of an item holds the
+//         output rows rho + DIL (i0 + 2 w) and + DIL -- a pair of rows that one wave of a square tile holds too, for the
+//         same columns: its GroupNorm records carry the same values in the same order, and are written to the square
+//         tile's slots (bit-identical statistics; rows past the square tiles are past the image and write nothing).
 #ifndef MVSN_WN_NO_FULLW
 #define MVSN_WN_FULLW_OK 1
 #else
 #define MVSN_WN_FULLW_OK 0
 #endif
-template <int MODE, int KS, int NSTAGE, int DIL, bool VOL = false, int RIDE = 0, int WIDE = 0, bool FULLW = false>
+constexpr int WN_TILE_RP = 3;
+template <int MODE, int KS, int NSTAGE, int DIL, bool VOL = false, int RIDE = 0, int TILE = 0, bool FULLW = false>
 __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, const float *__restrict__ in,
                                                                   const float *__restrict__ upk,
                                                                   const float *__restrict__ bias,
@@ -312,14 +326,21 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   constexpr bool LDS_BARRIER = !VOL;               // see wn_barrier (r4: with the LDS-only barrier the volume form carrying a
                                                    // pass is no faster either: 14.6 vs 14.4 ms per step for the six carriers)
 #endif
+  constexpr bool RP = TILE == WN_TILE_RP;
+  constexpr int WIDE = RP ? 0 : TILE;
   static_assert(!WIDE || (VOL && DIL == 1 && MVSN_WN_TRANSPOSED), "wide tiles: volume form only (transposed epilogue)");
   constexpr bool ROLL = WIDE == 2;
   constexpr int TY = ROLL ? 2 * WN_ROLL_PR : (WIDE ? WN_WIDE_TY : WN_TY), TX = WIDE ? WN_WIDE_TX : WN_TX;
-  constexpr int HY = ROLL ? WN_ROLL_HY : TY + 2 * DIL;   // raw rows (ROLL: two parts around one shared zero row)
+  static_assert(!RP || (DIL > 1 && !VOL && !WIDE), "row-phase items: dilated 2-D layers");
+  constexpr int HY = ROLL ? WN_ROLL_HY : TY + 2 * (RP ? 1 : DIL);   // raw rows (ROLL: two parts around one shared zero row)
+  constexpr int VS = RP ? 1 : DIL;                       // raw rows between a patch's vertical taps
+  constexpr int YS = RP ? DIL : 1;                       // image rows between raw rows
+  // first output row of item row tq (RP: tq = phase tile row x DIL + phase; the item's rows follow at stride DIL)
+  auto item_y0 = [](int tq) { return RP ? (tq & (DIL - 1)) + (int)((unsigned)tq / DIL) * (TY * DIL) : tq * TY; };
   constexpr int NP = ROLL ? WN_ROLL_NP : WN_WIDE_NP;     // WIDE: patches among the tile's 128 slots
   constexpr int PA = wn_pa(DIL), XS = TX + 2 * PA, DQ = XS / 4, GROUPS = HY * DQ, PIECES = (GROUPS + 63) / 64;
   constexpr int RCST = HY * XS + 16;
-  static_assert(WIDE || (XS == wn_xs(DIL) && GROUPS == wn_groups(DIL) && PIECES == wn_pieces(DIL) && RCST == wn_rcst(DIL)), "");
+  static_assert(WIDE || (XS == wn_xs(DIL) && GROUPS == wn_groups(DIL, RP) && PIECES == wn_pieces(DIL, RP) && RCST == wn_rcst(DIL, RP)), "");
   constexpr int STAGE = KS * 4 * RCST;               // ring stage (floats)
   float *U = smem + NSTAGE * STAGE;                  // nchunks * WN_UFLOATS, resident (VOL: ring of NSTAGE steps)
   // dilation 1: raw tiles stored one float further (4-byte-aligned DMA destination), see tr_load
@@ -339,7 +360,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const size_t plane = (size_t)g.H * g.W;
-  const int ptiles = ROLL ? g.tiles : g.D * g.tiles; // work items per sample (VOL: planes x tiles; ROLL: rolling strips)
+  // work items per sample (VOL: planes x tiles; ROLL: rolling strips; RP: phase tile rows x phases x column tiles)
+  const int ptiles = ROLL ? g.tiles : (RP ? DIL * g.rpy * g.ntx : g.D * g.tiles);
   // ROLL: item t of a sample -> plane zA of its first patch row, that row prA0 inside the plane, rows s taken from zA
   auto roll_item = [&](int t, int &zA, int &prA0, int &sA) {
     const int R0 = t * WN_ROLL_PR;
@@ -404,7 +426,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
       tile -= pf_z * g.tiles;
     }
     const int tyi = ROLL ? 0 : wdiv(tile, g.fd_ntx), txi = tile - tyi * g.ntx;
-    const int y0 = ROLL ? 2 * r_pr0 : tyi * TY, x0 = txi * TX;
+    const int y0 = ROLL ? 2 * r_pr0 : item_y0(tyi), x0 = txi * TX;
     pf_n = n;
     // (the pieces' rows / columns are re-derived per tile from an opaque copy of the lane id: hoisted out of the tile
     // loop they occupy six registers for the whole launch -- spilled, and reloaded per step, in the carrying kernels)
@@ -414,7 +436,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
     for (int i = 0; i < PER; ++i) {
       const int e = (dp0 + i) * 64 + lo;
       const int row = e / DQ, q = e - row * DQ;
-      int gy = y0 - DIL + row;
+      int gy = y0 - DIL + YS * row;
       const int gx = x0 - PA + 4 * q;
       int zsh = 0;
       if constexpr (ROLL) {   // raw rows 0 .. 2 s: plane zA from its row y0 - 1; row 2 s + 1: zero; then plane zA + 1 from row 0
@@ -516,7 +538,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
 
   const int pcol = lane & 15, kc = lane >> 4;   // this lane's patch column / channel within the chunk; patch row = wave
   // first output row / column of patch row `wave` / patch column `pcol` inside the tile (the second is + DIL)
-  int ya = (wave / DIL) * 2 * DIL + wave % DIL, xa = (pcol / DIL) * 2 * DIL + pcol % DIL;
+  // (RP: ya counts raw rows -- the item's rows 2 wave, 2 wave + 1 of its phase)
+  int ya = RP ? 2 * wave : (wave / DIL) * 2 * DIL + wave % DIL, xa = (pcol / DIL) * 2 * DIL + pcol % DIL;
   int lane_pr = 0;        // WIDE: this lane's patch row inside the tile
   if constexpr (WIDE != 0) {   // slot q of the tile -> patch (q / 20, q % 20); idle slots read patch 0 (their outputs are never stored)
     const int q = wave * 16 + pcol, qq = q < NP ? q : 0;
@@ -579,7 +602,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
       }
       if (xf_chunk == 0) {
         const int tyi = ROLL ? 0 : wdiv(tile, g.fd_ntx), txi = tile - tyi * g.ntx;
-        const int y0 = ROLL ? 2 * r_pr0 : tyi * TY, x0 = txi * TX;
+        const int y0 = ROLL ? 2 * r_pr0 : item_y0(tyi), x0 = txi * TX;
         xf_mask = 0;
         xf_maska = xf_maskb = 0;
         int lo;
@@ -588,7 +611,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
         for (int i = 0; i < PER; ++i) {
           const int e = (dp0 + i) * 64 + lo;
           const int row = e / DQ, q = e - row * DQ;
-          int gy = y0 - DIL + row;
+          int gy = y0 - DIL + YS * row;
           const int gx = x0 - PA + 4 * q;
           bool isb = false;
           if constexpr (ROLL) {
@@ -705,8 +728,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          d[h][i][0] = raw[i * DIL * XS], d[h][i][1] = raw[i * DIL * XS + 2 * DIL];
-          d[h][i][2] = raw[i * DIL * XS + DIL], d[h][i][3] = raw[i * DIL * XS + 3 * DIL];
+          d[h][i][0] = raw[i * VS * XS], d[h][i][1] = raw[i * VS * XS + 2 * DIL];
+          d[h][i][2] = raw[i * VS * XS + DIL], d[h][i][3] = raw[i * VS * XS + 3 * DIL];
         }
       }
     }
@@ -864,7 +887,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
     constexpr int PSH = DIL <= 2 ? 1 : 0;   // DIL 1, 2: h = r >> 1; DIL 4, 8: h = second
     auto slot_h = [](int r, int sec) { return PSH ? (r >> 1) : sec; };
     auto slot_k = [](int r, int sec) { return DIL == 1 ? 2 * (r & 1) + sec : (DIL == 2 ? (r & 1) + 2 * sec : r); };
-    const int oy = y0 + ya;
+    const int oy = y0 + (RP ? DIL : 1) * ya;
     const int xg0 = DIL == 8 ? 16 * (gq >> 1) + 4 * (gq & 1) : 8 * gq;   // first column of group 0 inside the tile
     const int xg1 = xg0 + (DIL == 8 ? 8 : 4);
     const bool row0 = oy < g.H, row1 = oy + DIL < g.H;
@@ -946,8 +969,16 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
             }
 #pragma unroll
       for (int t = 0; t < 2; ++t) qv[t] = sum8(qv[t]);
-      if ((lq & 7) == 0) {   // lanes 0 and 8 of every row
-        float *rec = out_partials + (((size_t)n * ptiles + (size_t)z * g.tiles + tile_id) * WN_WAVES + wave) * 48;   // uniform
+      // RP: the slot of the square tile / wave that holds rows oy, oy + DIL (see RP; uniform)
+      int rtile = tile_id, rwave = wave;
+      bool rec_ok = true;
+      if constexpr (RP) {
+        const int yq = oy & (TY - 1);
+        rtile = (oy / TY) * g.ntx + x0 / TX, rwave = yq / (2 * DIL) * DIL + yq % DIL;
+        rec_ok = oy < g.nty * TY;
+      }
+      if ((lq & 7) == 0 && rec_ok) {   // lanes 0 and 8 of every row
+        float *rec = out_partials + (((size_t)n * (RP ? g.tiles : ptiles) + (size_t)z * g.tiles + rtile) * WN_WAVES + rwave) * 48;   // uniform
         rec += gq * 12 + hi * 3;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -1081,7 +1112,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
       tile_id -= z * g.tiles;
     }
     const int tyi = ROLL ? 0 : wdiv(tile_id, g.fd_ntx), txi = ROLL ? 0 : tile_id - tyi * g.ntx;
-    const int y0 = ROLL ? 2 * r_pr0 : tyi * TY, x0 = txi * TX;
+    const int y0 = ROLL ? 2 * r_pr0 : item_y0(tyi), x0 = txi * TX;
 
     // acc is first written by the tile's first 32 multiplies (C = 0): no zeroing pass.  The empty asm "defines"
     // the registers here, so the allocator does not carry 128 undefined values around the tile loop.
@@ -1462,8 +1493,15 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_s2_kernel(WinoS2Args 
   }
 }
 
+// test hook (mvsn_debug_set_wino_rowphase): 0 = row-phase items where they take no more items than square tiles, 1 = on
+// every dilated 2-D layer, 2 = never.  Unsynchronised, like mvsn_debug_set_band_flags: wino_geom reads it on every call
+// (the statistics' record count does not depend on it, the launch plan does), so it must not change while another thread
+// plans or launches layers, nor while a graph is being captured (a captured launch keeps the plan it was captured with).
+static int g_wn_rowphase = 0;
+
 bool wino_geom(const mvsn_conv_desc *d, WinoGeom *g) {
   if (!d || d->precision != MVSN_CONV_FP32_WINO) return false;
+  g->rpy = 0;
   if (d->n <= 0 || d->c_in <= 0 || d->c_out != 32 || d->depth < 1 || d->rows <= 0 || d->cols <= 0) return false;
   g->s2 = false;
   if (d->kd == 1 && d->kh == 5 && d->kw == 5 && d->stride == 2) {   // 5 x 5 stride 2 on the input's four phases (conv_wino_s2_kernel)
@@ -1520,6 +1558,14 @@ bool wino_geom(const mvsn_conv_desc *d, WinoGeom *g) {
   if (g->nchunks > 8 && d->dilation > 2) return false;   // ... next to the (larger) raw-tile ring of dilation 4 / 8
   if (g->nchunks == 1 && d->dilation != 1) return false;  // dilated 4-channel layers are not instantiated
   g->packed_floats = (size_t)g->nchunks * WN_UFLOATS;
+#ifndef MVSN_WN_NO_ROWPHASE
+  // dilated layers on row-phase items (conv_wino_kernel's RP) wherever the phases fill them as well as the square tiles
+  // (D x rpy <= nty: heights of 16 D rows or more; a shorter phase would leave most of an item's 16 rows empty)
+  if (d->dilation > 1 && g_wn_rowphase != 2) {
+    const int rpy = ((d->rows + d->dilation - 1) / d->dilation + WN_TY - 1) / WN_TY;
+    if (g_wn_rowphase == 1 || d->dilation * rpy <= g->nty) g->rpy = rpy;
+  }
+#endif
   return true;
 }
 
@@ -1544,14 +1590,34 @@ int wino_pack(const mvsn_conv_desc *d, const float *weight, float *packed, hipSt
   return check_launch("mvsn_conv_pack_weights(winograd)");
 }
 
+// (k-steps per step, ring depth) of the 2-D / volume layers by what fits next to the resident U: the raw tile grows with
+// the dilation
+//   square tiles -- dilation 1: 2 k-steps x 4 stages (94 KB); 2, 4: 2 x 3 (78 / 94 KB); 8: 1 x 3 (74 KB); 4-channel head:
+//   1 x 6; carrying a job: dilation 4 too on one k-step (its two-k-step ring, 94 KB next to 64 KB of U, leaves no room for
+//   the residual slots)
+//   row-phase items -- dilations 2, 4: dilation 1's 18 x 40 tile, 2 x 4 (92 KB), carrying 2 x 3; 8 (18 x 48): 2 x 3
+//   (83 KB), carrying 1 x 3 (2 x 3 and the 16 KB of residual slots would need 163 KB)
+//   volume form: 2 x 3 raw stages + 3 stages of U (118 KB)
+struct WinoPlan {
+  int ks, nstage;
+};
+static WinoPlan wino_plan(const WinoGeom &g, bool job) {
+  const bool head = g.nchunks == 1;
+  if (g.rpy) return WinoPlan{(job && g.dil == 8) ? 1 : 2, (g.dil <= 4 && g.nchunks <= 8 && !job) ? 4 : 3};
+  // (a carrying launch waits with one step of DMA in flight, see RideArgs: a fourth stage would never be used)
+  // ... except the rolling strips without a job: four stages (158 KB) measured 3.84-3.87 against 3.90-3.92 ms per 128
+  // samples of 96 x 30 x 40 (the 16 x 32 tiles: 0.992 either way, they stay at three)
+  return WinoPlan{(head || g.dil == 8 || (job && g.dil == 4)) ? 1 : 2,
+                  head ? 6 : (((g.dil == 1 && g.nchunks <= 8 && !job) || (g.vol && g.wide == 2 && !job)) ? 4 : 3)};
+}
+
 // RIDE units per wave and step of the instantiation a layer runs on (0: that kernel carries nothing)
 static int wino_ride_units(const WinoGeom &g) {
   if (g.s2) return 0;
   if (g.vol) return 1;         // 12 steps per (plane, tile): 96 units, of which a job of the layer's own size needs 64
   if (g.nchunks != 8) return 0;
-  // 4 steps of two k-steps / 8 steps of one: 64 units = 64 KB per tile either way.  Dilation 4 carries on the
-  // one-k-step form (its two-k-step ring, 94 KB next to 64 KB of U, leaves no room for the residual slots).
-  return g.dil >= 4 ? 1 : 2;
+  // 4 steps of two k-steps / 8 steps of one: 64 units = 64 KB per tile either way
+  return wino_plan(g, true).ks == 2 ? 2 : 1;
 }
 
 bool wino_can_carry(const WinoGeom &g, const mvsn_apply_job *job) {
@@ -1562,8 +1628,8 @@ bool wino_can_carry(const WinoGeom &g, const mvsn_apply_job *job) {
   if ((((size_t)job->x | (size_t)job->out | (size_t)job->residual) & 15) != 0) return false;
   const long units = (long)job->n * 32 * (job->spatial / 256);
   if (g.vol && job->residual) return false;   // (no residual slots next to the volume form's two rings)
-  const int nsteps = g.vol ? 12 : (g.dil >= 4 ? 8 : 4);
-  const long capacity = (long)g.n * wino_items(g) * nsteps * WN_WAVES * r;   // unit indices are 32-bit in the kernel
+  const int nsteps = g.vol ? 12 : 8 / wino_plan(g, true).ks;
+  const long capacity = (long)g.n * wino_work_items(g) * nsteps * WN_WAVES * r;   // unit indices are 32-bit in the kernel
   return units <= capacity && capacity < (1L << 31) && units < (1L << 30);
 }
 
@@ -1605,22 +1671,17 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
   a.cb0 = g.cin, a.cb1 = 0, a.in1 = a.in2 = in;
   a.D = g.D;
   a.pr = (g.H + 1) / 2, a.fd_pr = wino_div((unsigned)a.pr);
+  a.nty = g.nty, a.rpy = g.rpy;
   if (blocks) a.cb0 = blocks->cb0, a.cb1 = blocks->cb1, a.in1 = blocks->in1, a.in2 = blocks->in2;
   a.rev = (job && job->reverse == 1) ? 1 : 0;
   a.cs0 = (size_t)g.H * g.W, a.bs0 = (size_t)a.cb0 * a.cs0;
   if (blocks && blocks->cs0) a.cs0 = blocks->cs0, a.bs0 = blocks->bs0;
   const int cus = device_cus();
-  // (k-steps per step, ring depth) by what fits next to the resident U: the raw tile grows with the dilation
-  //   dilation 1: 2 k-steps x 4 stages (94 KB); 2, 4: 2 x 3 (78 / 94 KB); 8: 1 x 3 (74 KB); 4-channel head: 1 x 6
-  //   volume form: 2 x 3 raw stages + 3 stages of U (118 KB)
   const bool head = g.nchunks == 1;
-  const int ks = (head || g.dil == 8 || (job && g.dil == 4)) ? 1 : 2;
-  // (a carrying launch waits with one step of DMA in flight, see RideArgs: a fourth stage would never be used)
-  // ... except the rolling strips without a job: four stages (158 KB) measured 3.84-3.87 against 3.90-3.92 ms per 128
-  // samples of 96 x 30 x 40 (the 16 x 32 tiles: 0.992 either way, they stay at three)
-  const int nstage = head ? 6 : (((g.dil == 1 && g.nchunks <= 8 && !job) || (g.vol && g.wide == 2 && !job)) ? 4 : 3);
+  const WinoPlan plan = wino_plan(g, job != nullptr);
+  const int ks = plan.ks, nstage = plan.nstage;
   const size_t rcst = g.wide ? (size_t)(g.wide == 2 ? WN_ROLL_HY : WN_WIDE_TY + 2) * (WN_WIDE_TX + 2 * wn_pa(1)) + 16
-                             : (size_t)wn_rcst(g.dil);
+                             : (size_t)wn_rcst(g.dil, g.rpy > 0);
   size_t lds = ((size_t)nstage * ks * 4 * rcst +
                 (g.vol ? (size_t)nstage * ks : (size_t)((g.nchunks + ks - 1) / ks * ks)) * WN_UFLOATS) * sizeof(float);
   lds += 32 * sizeof(float);                                      // bias
@@ -1649,7 +1710,7 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
                        (const void *)rd.x, (const void *)rd.stats, (const void *)rd.res, (const void *)rd.r_stats,  \
                        (const void *)rd.out, (const void *)nullptr, (const void *)nullptr, (const void *)nullptr);  \
   } while (0)
-  const long total = (long)g.n * wino_items(g);
+  const long total = (long)g.n * wino_work_items(g);
   grid = dim3((unsigned)(total < cus ? total : cus));   // persistent: one workgroup per CU walks items grid-strided
   const bool xf = in_stats != nullptr;
   // volume form on planes one tile wide (the 16 x 32 coarse grid): neighbouring lanes share the input transform's column
@@ -1661,6 +1722,9 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
     else if (g.vol && fullw) { if (xf) WN_CASE(1, 2, 3, 1, true, 1, 0, true); else WN_CASE(0, 2, 3, 1, true, 1, 0, true); }
     else if (g.vol) { if (xf) WN_CASE(1, 2, 3, 1, true, 1); else WN_CASE(0, 2, 3, 1, true, 1); }
     else if (g.dil == 1) { if (xf) WN_CASE(1, 2, 3, 1, false, 2); else WN_CASE(0, 2, 3, 1, false, 2); }
+    else if (g.rpy && g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2, false, 2, WN_TILE_RP); else WN_CASE(0, 2, 3, 2, false, 2, WN_TILE_RP); }
+    else if (g.rpy && g.dil == 4) { if (xf) WN_CASE(1, 2, 3, 4, false, 2, WN_TILE_RP); else WN_CASE(0, 2, 3, 4, false, 2, WN_TILE_RP); }
+    else if (g.rpy) { if (xf) WN_CASE(1, 1, 3, 8, false, 1, WN_TILE_RP); else WN_CASE(0, 1, 3, 8, false, 1, WN_TILE_RP); }
     else if (g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2, false, 2); else WN_CASE(0, 2, 3, 2, false, 2); }
     else if (g.dil == 4) { if (xf) WN_CASE(1, 1, 3, 4, false, 1); else WN_CASE(0, 1, 3, 4, false, 1); }
     else { if (xf) WN_CASE(1, 1, 3, 8, false, 1); else WN_CASE(0, 1, 3, 8, false, 1); }
@@ -1672,6 +1736,10 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
   else if (head) { if (xf) WN_CASE(1, 1, 6, 1); else WN_CASE(0, 1, 6, 1); }
   else if (g.dil == 1 && g.nchunks > 8) { if (xf) WN_CASE(1, 2, 3, 1); else WN_CASE(0, 2, 3, 1); }
   else if (g.dil == 1) { if (xf) WN_CASE(1, 2, 4, 1); else WN_CASE(0, 2, 4, 1); }
+  else if (g.rpy && g.dil == 2 && nstage == 3) { if (xf) WN_CASE(1, 2, 3, 2, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 3, 2, false, 0, WN_TILE_RP); }
+  else if (g.rpy && g.dil == 2) { if (xf) WN_CASE(1, 2, 4, 2, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 4, 2, false, 0, WN_TILE_RP); }
+  else if (g.rpy && g.dil == 4) { if (xf) WN_CASE(1, 2, 4, 4, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 4, 4, false, 0, WN_TILE_RP); }
+  else if (g.rpy) { if (xf) WN_CASE(1, 2, 3, 8, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 3, 8, false, 0, WN_TILE_RP); }
   else if (g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2); else WN_CASE(0, 2, 3, 2); }
   else if (g.dil == 4) { if (xf) WN_CASE(1, 2, 3, 4); else WN_CASE(0, 2, 3, 4); }
   else { if (xf) WN_CASE(1, 1, 3, 8); else WN_CASE(0, 1, 3, 8); }
@@ -1680,6 +1748,12 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
 }
 
 }  // namespace mvsn
+
+extern "C" int mvsn_debug_set_wino_rowphase(int mode) {
+  const int old = mvsn::g_wn_rowphase;
+  mvsn::g_wn_rowphase = mode;
+  return old;
+}
 
 #ifdef MVSN_WN_STAMPS
 extern "C" int mvsn_debug_set_wino_stamps(void *buf) {
