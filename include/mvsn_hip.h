@@ -514,6 +514,35 @@ int mvsn_depth_metrics_blocks(long pixels);
 int mvsn_depth_metrics(const float *idepth_est, const float *depth_true, const float *baseline, int batch, long pixels,
                        float min_depth, float max_depth, double *partials, double *rows, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth-map fusion: the geometric-consistency filter that follows the network in an MVS pipeline, and the
+ * back-projection of the kept pixels into one world-space point cloud (multi_view_stereonet_amd/fusion.py; the
+ * semantics are DESIGN.md section 10).  Not part of the reference, which stops at the depth maps.
+ *   depth (V,rows,cols) in world units, <= 0 = no depth   valid (V,rows,cols) u8 or NULL (every depth > 0 valid)
+ *   K (V,4,4): the top-left 3x3 is used, its bottom row must be (0,0,1) (not checked)   T_cam_in_world (V,4,4)
+ *   ref_views (R) int32, neighbours (R,n_slots) int32 view indices or -1 (skip), 1 <= n_slots <= 32; both on the
+ *   device and validated by the caller (out-of-range entries are skipped, never dereferenced)
+ * mvsn_fusion_consistency: per reference pixel, every neighbour slot in order: lift, move, project, sample the
+ *   neighbour's depth bilinearly (all four taps inside, positive, valid), lift again, move back, project; the slot is
+ *   consistent when the pixel lands within max_reproj_px and the depth within max_rel_depth relative.
+ *   -> fused_depth (R,rows,cols): (depth + sum of consistent depths) / (count + 1) where count >= min_consistent, else 0
+ *      count (R,rows,cols) u8   total (1 int64): the number of kept pixels
+ *   workspace: mvsn_fusion_workspace_bytes(R, n_slots, rows, cols) bytes, handed on to mvsn_fusion_emit unchanged
+ * mvsn_fusion_emit: the kept pixels, ordered by reference then row-major pixel, at [0, total) of
+ *   points (total,3) fp32 world   colors (total,3) u8 from images (V,3,rows,cols) in [-1,1], or NULL   view, pixel (total)
+ *   capacity = the total read back to the host: that read is the one host synchronisation of a fusion; 0 = no launch.
+ * No atomics: every output is a deterministic function of the inputs.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_fusion_workspace_bytes(int n_ref, int n_slots, int rows, int cols);
+int mvsn_fusion_consistency(const float *depth, const uint8_t *valid, const float *K, const float *T_cam_in_world,
+                            const int *ref_views, const int *neighbours, int n_views, int n_ref, int n_slots, int rows,
+                            int cols, float max_reproj_px, float max_rel_depth, int min_consistent, float *fused_depth,
+                            uint8_t *count, int64_t *total, void *workspace, size_t workspace_bytes,
+                            mvsn_stream_t stream);
+int mvsn_fusion_emit(const float *fused_depth, const float *images, const int *ref_views, int n_ref, int rows, int cols,
+                     int n_slots, const void *workspace, size_t workspace_bytes, long capacity, float *points,
+                     uint8_t *colors, int *view, int *pixel, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

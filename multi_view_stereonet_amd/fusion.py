@@ -1,0 +1,208 @@
+"""Depth-map fusion: from per-view depth maps to one geometric-consistency-filtered, coloured point cloud.
+
+Each reference view's depth is checked against its neighbours' depths; the pixels enough neighbours confirm are
+averaged with the confirming depths and back-projected into world coordinates (DESIGN.md section 10 states the
+semantics; the kernels are csrc/mvsn_fusion.hip).  ``fuse_depthmaps`` runs that on depth maps already on the device,
+``reconstruct`` runs the network over posed frames first, and ``write_ply`` saves the result.
+
+Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
+coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
+"""
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native
+
+MAX_NEIGHBOURS = 32
+
+
+class FusionResult(NamedTuple):
+    points: torch.Tensor             # (M,3) fp32 world coordinates
+    colors: Optional[torch.Tensor]   # (M,3) uint8, or None without images
+    view: torch.Tensor               # (M,) int32: the reference view each point comes from
+    pixel: torch.Tensor              # (M,) int32: its row-major pixel index
+    depth: torch.Tensor              # (R,1,H,W) fp32: fused depth, 0 where not kept
+    count: torch.Tensor              # (R,1,H,W) uint8: consistent neighbours per pixel
+
+
+def _host_index_array(a, name) -> np.ndarray:
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold integers, got {a.dtype}")
+    return a.astype(np.int64)
+
+
+def _check_frames(name, t, V, H, W, channels, dtypes, device):
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name} must be a tensor")
+    if tuple(t.shape) != (V, channels, H, W):
+        raise ValueError(f"{name} must be ({V},{channels},{H},{W}), got {tuple(t.shape)}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, depth on {device}")
+
+
+def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
+                   images: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                   ref_views: Optional[Sequence[int]] = None, max_reproj_px: float = 1.0,
+                   max_rel_depth: float = 0.01, min_consistent: int = 2) -> FusionResult:
+    """Fuse ``depth`` (V,1,H,W) into a point cloud.
+
+    ``neighbours`` is a host (R,M) integer array, 1 <= M <= 32: row i lists the views that check ``ref_views[i]``
+    (default ``range(V)``), -1 skips a slot.  A pixel of a reference view is kept when at least ``min_consistent``
+    neighbours confirm it (reprojection error < ``max_reproj_px`` pixels and relative depth difference <
+    ``max_rel_depth``).  Points come ordered by position in ``ref_views``, then row-major pixel.  Everything is validated
+    here, before any launch; the one host synchronisation is the read of the number of kept pixels (to size the
+    outputs)."""
+    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError("depth must be a (V,1,H,W) tensor")
+    V, _, H, W = depth.shape
+    dev = depth.device
+    if V < 1 or H * W < 1:
+        raise ValueError("depth must hold at least one view of at least one pixel")
+    if depth.dtype != torch.float32:
+        raise ValueError(f"depth must be float32, got {depth.dtype}")
+    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
+            raise ValueError(f"{name} must be a ({V},4,4) tensor")
+        if m.device != dev:
+            raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+    if images is not None:
+        _check_frames("images", images, V, H, W, 3, (torch.float32,), dev)
+    if valid is not None:
+        _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
+    nb = _host_index_array(neighbours, "neighbours")
+    if nb.ndim != 2:
+        raise ValueError(f"neighbours must be (R, M), got shape {nb.shape}")
+    R, M = nb.shape
+    if not 1 <= M <= MAX_NEIGHBOURS:
+        raise ValueError(f"neighbours must have 1..{MAX_NEIGHBOURS} slots per reference view, got {M}")
+    refs = np.arange(V, dtype=np.int64) if ref_views is None else _host_index_array(ref_views, "ref_views").reshape(-1)
+    if refs.shape[0] != R:
+        raise ValueError(f"neighbours has {R} rows for {refs.shape[0]} reference views")
+    if R < 1 or R > 65535:
+        raise ValueError(f"1..65535 reference views, got {R}")
+    if ((refs < 0) | (refs >= V)).any():
+        raise ValueError(f"ref_views must lie in [0, {V})")
+    if ((nb < -1) | (nb >= V)).any():
+        raise ValueError(f"neighbour indices must lie in [-1, {V})")
+    if (nb == refs[:, None]).any():
+        raise ValueError("a view cannot be its own neighbour")
+    if not (max_reproj_px >= 0 and max_rel_depth >= 0 and min_consistent >= 0):
+        raise ValueError("thresholds must be non-negative")
+
+    if not depth.is_cuda:
+        raise RuntimeError("fuse_depthmaps runs on HIP devices only: move the depth maps to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+    depth_c, K_c, T_c = f32(depth), f32(K), f32(T_cam_in_world)
+    valid_c = valid.detach().contiguous().view(torch.uint8) if valid is not None else None
+    refs_d = torch.from_numpy(refs.astype(np.int32)).to(dev)
+    nb_d = torch.from_numpy(np.ascontiguousarray(nb.astype(np.int32))).to(dev)
+    ws_bytes = lib.mvsn_fusion_workspace_bytes(R, M, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    fused = torch.empty((R, 1, H, W), dtype=torch.float32, device=dev)
+    count = torch.empty((R, 1, H, W), dtype=torch.uint8, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_fusion_consistency(
+            _native.ptr(depth_c), _native.ptr(valid_c), _native.ptr(K_c), _native.ptr(T_c), _native.ptr(refs_d),
+            _native.ptr(nb_d), V, R, M, H, W, float(max_reproj_px), float(max_rel_depth), int(min_consistent),
+            _native.ptr(fused), _native.ptr(count), _native.ptr(total), _native.ptr(ws), ws_bytes, st),
+            "mvsn_fusion_consistency")
+        n = int(total.item())          # the one host synchronisation: sizes the outputs
+        points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        colors = torch.empty((n, 3), dtype=torch.uint8, device=dev) if images is not None else None
+        view = torch.empty((n,), dtype=torch.int32, device=dev)
+        pixel = torch.empty((n,), dtype=torch.int32, device=dev)
+        images_c = f32(images) if images is not None else None
+        _native.check(lib.mvsn_fusion_emit(
+            _native.ptr(fused), _native.ptr(images_c), _native.ptr(refs_d), R, H, W, M, _native.ptr(ws), ws_bytes, n,
+            _native.ptr(points), _native.ptr(colors), _native.ptr(view), _native.ptr(pixel), st), "mvsn_fusion_emit")
+    return FusionResult(points, colors, view, pixel, fused, count)
+
+
+def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:
+    """T_right_in_left = T_left_in_world^-1 T_right_in_world for every (ref[i], src[i]): (len(ref),1,4,4) fp32, formed
+    in fp64 on the host (a handful of 4x4s: the DataLoader-side pose arithmetic)."""
+    T = T_cam_in_world.detach().to("cpu", torch.float64)
+    ref, src = list(ref), list(src)
+    return (torch.linalg.inv(T[ref]) @ T[src]).to(torch.float32).unsqueeze(1).contiguous()
+
+
+def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
+                num_idepth_samples: int = 64, batch: int = 8, cost_volume_filter: bool = True,
+                refiners: Sequence[bool] = (True,) * 5, **fusion_kwargs):
+    """Posed frames -> point cloud: the network's depth map for every view, then ``fuse_depthmaps`` over all of them.
+
+    ``images`` (V,3,H,W) fp32 in [-1,1] on the network's device, ``K`` / ``T_cam_in_world`` (V,4,4), ``neighbours`` (V,S)
+    without -1: the S source views of each reference view, the first of which sets the baseline (a zero baseline
+    raises, as ``multi_view_unpack_batch`` does).  The network runs over the reference views ``batch`` at a time; its
+    finest idepth map is converted to depth in the units of the poses (``metrics.idepth_to_depth``).  The same
+    ``neighbours`` (and ``fusion_kwargs``) drive the fusion.  Returns ``(FusionResult, depth (V,1,H,W))``."""
+    from . import metrics
+    from . import multi_view_stereonet_utils as snu
+
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError("images must be a (V,3,H,W) tensor")
+    V = images.shape[0]
+    nb = _host_index_array(neighbours, "neighbours")
+    if nb.ndim != 2 or nb.shape[0] != V or nb.shape[1] < 1:
+        raise ValueError(f"neighbours must be ({V}, S) with S >= 1")
+    if ((nb < 0) | (nb >= V)).any():
+        raise ValueError(f"the network needs S real source views per reference view: indices in [0, {V})")
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    # checked on the camera centres, before any launch (T_right_in_left of two coincident cameras can keep a rounding
+    # residue in its translation)
+    centres = T_cam_in_world.detach().to("cpu", torch.float64)[:, :3, 3]
+    if ((centres - centres[nb[:, 0]]).norm(dim=1) <= 0).any():
+        raise AssertionError("baseline to the first source view must be positive")
+    dev = images.device
+    Kc = K.detach().to("cpu", torch.float32)
+    params = {"num_idepth_samples": int(num_idepth_samples), "cost_volume_filter": bool(cost_volume_filter),
+              "refiners": list(refiners)}
+    depths = []
+    with torch.no_grad():
+        for lo in range(0, V, batch):
+            ref = list(range(lo, min(lo + batch, V)))
+            frames = {"left_image": images[ref],
+                      "right_image": [images[nb[ref, s].tolist()] for s in range(nb.shape[1])],
+                      "K": Kc[ref].unsqueeze(1).contiguous(),
+                      "T_right_in_left": [frame_pair_poses(T_cam_in_world, ref, nb[ref, s]) for s in range(nb.shape[1])]}
+            inputs = snu.multi_view_unpack_batch(frames, dev, net.num_levels)
+            out = snu.multi_view_forward(net, inputs, params)
+            depths.append(metrics.idepth_to_depth(out["left_idepthmap_pyr"][0], inputs["baseline"]))
+        depth = torch.cat(depths, 0)
+        result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, **fusion_kwargs)
+    return result, depth
+
+
+def write_ply(path: str, points, colors=None) -> None:
+    """Binary little-endian PLY: float x, y, z per vertex, plus uchar red, green, blue when ``colors`` is given."""
+    pts = (points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)).astype("<f4")
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N,3)")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        col = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
+        if col.shape != pts.shape:
+            raise ValueError("colors must be (N,3) like points")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.empty(pts.shape[0], dtype=fields)
+    rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if colors is not None:
+        col = col.astype(np.uint8)
+        rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    props = "".join(f"property {'float' if t == '<f4' else 'uchar'} {n}\n" for n, t in fields)
+    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\n{props}end_header\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())

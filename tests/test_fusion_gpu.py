@@ -1,0 +1,150 @@
+"""Depth-map fusion on the device (csrc/mvsn_fusion.hip) against the float64 restatement (tests/fusion_reference.py),
+and reconstruct() against its own composition."""
+import numpy as np
+import pytest
+import torch
+
+from fusion_reference import fuse_reference, nearest_neighbours
+from multi_view_stereonet_amd import synthetic
+from multi_view_stereonet_amd.fusion import FusionResult, frame_pair_poses, fuse_depthmaps, reconstruct
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+def _compare(got: FusionResult, ref, images, T_cam_in_world, views, max_margin):
+    count = got.count.cpu().numpy().astype(np.int64)
+    margin = ref["margin"]
+    diff = count != ref["count"]
+    assert not (diff & ~margin).any(), np.argwhere(diff & ~margin)[:10]
+    # margin pixels: a decision of the restatement within 1e-4 (relative) of flipping
+    assert margin.sum() <= max_margin * margin.size, margin.sum()
+    same = ~diff & ref["keep"]
+    fused = got.depth.cpu().numpy().astype(np.float64)
+    assert (fused[~ref["keep"] & ~diff] == 0).all()
+    rel = np.abs(fused[same] - ref["fused"][same]) / ref["fused"][same]
+    assert rel.max() < 1e-5, rel.max()
+    # points by their (view, pixel) key: the key lists agree but for margin pixels, in the same order
+    H, W = count.shape[-2:]
+    key_g = got.view.cpu().numpy().astype(np.int64) * H * W + got.pixel.cpu().numpy()
+    key_r = ref["view"] * H * W + ref["pixel"]
+    shared, ig, ir = np.intersect1d(key_g, key_r, return_indices=True)
+    order_g, order_r = np.argsort(ig, kind="stable"), np.argsort(ir, kind="stable")
+    assert (order_g == order_r).all()                       # the shared entries come in the same order
+    extra = np.setdiff1d(np.union1d(key_g, key_r), shared)
+    row = {v: i for i, v in enumerate(views)}
+    for k in extra:
+        v, p = divmod(int(k), H * W)
+        assert margin[row[v], 0].reshape(-1)[p], (v, p)
+    # (points of margin pixels whose count differs are left out: one more or one fewer depth in their average)
+    rows_ = np.array([row[int(v)] for v in ref["view"][ir]], np.int64)
+    agree = ~diff.reshape(len(views), -1)[rows_, ref["pixel"][ir]]
+    ig, ir = ig[agree], ir[agree]
+    pts = got.points.cpu().numpy().astype(np.float64)[ig]
+    # within 1e-5 of the point's distance from its camera (= depth times the ray's length: the fused depth's 1e-5)
+    centres = np.stack([cam[:3, 3] for cam in T_cam_in_world.double().numpy()])[ref["view"][ir]]
+    err = np.linalg.norm(pts - ref["points"][ir], axis=1) / np.linalg.norm(ref["points"][ir] - centres, axis=1)
+    assert err.max() < 1e-5, err.max()
+    if images is not None:
+        np.testing.assert_array_equal(got.colors.cpu().numpy()[ig], ref["colors"][ir])
+    else:
+        assert got.colors is None
+    return len(shared)
+
+
+def test_fusion_matches_the_restatement_on_the_analytic_scene():
+    sc = synthetic.fusion_scene(6, 96, 128)
+    nb = nearest_neighbours(6, 5)
+    ref = fuse_reference(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    got = fuse_depthmaps(sc["depth"].to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb,
+                         images=sc["images"].to(DEV))
+    # (59 margin pixels of 73728 here: projections within 1e-4 * u of an integer column next to the image edge)
+    assert _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3) > 0.8 * 6 * 96 * 128
+
+
+def test_fusion_odd_size_padding_valid_mask_and_ref_subset():
+    V, H, W = 6, 97, 131
+    sc = synthetic.fusion_scene(V, H, W)
+    gen = torch.Generator().manual_seed(7)
+    valid = torch.rand(V, 1, H, W, generator=gen) > 0.05
+    depth = sc["depth"].clone()
+    depth[1, :, 40:50, 60:80] = 0.0                               # a hole: taps with no depth
+    refs = [4, 1, 3]
+    nb = np.array([[3, 5, -1, 2], [-1, 0, 2, 3], [2, -1, 4, -1]])
+    ref = fuse_reference(depth, sc["K"], sc["T_cam_in_world"], nb, images=sc["images"], valid=valid, ref_views=refs)
+    got = fuse_depthmaps(depth.to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb, images=sc["images"].to(DEV),
+                         valid=valid.to(DEV), ref_views=refs)
+    assert got.depth.shape == (3, 1, H, W) and got.count.dtype == torch.uint8
+    # (444 margin pixels of 38121: with 5 % of the pixels invalid, most integer crossings of (u, v) change whether
+    # all four taps are valid)
+    assert _compare(got, ref, sc["images"], sc["T_cam_in_world"], refs, 0.02) > 0.3 * 3 * H * W
+    # without images: no colours, the same points
+    bare = fuse_depthmaps(depth.to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb, valid=valid.to(DEV),
+                          ref_views=refs)
+    assert bare.colors is None and torch.equal(bare.points, got.points)
+
+
+def test_fusion_is_deterministic():
+    sc = synthetic.fusion_scene(6, 96, 128, device=DEV)
+    nb = nearest_neighbours(6, 4)
+    a = fuse_depthmaps(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    b = fuse_depthmaps(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    for x, y in zip(a, b):
+        assert torch.equal(x, y)
+
+
+def test_fusion_empty_result():
+    sc = synthetic.fusion_scene(4, 64, 96, device=DEV)
+    nb = nearest_neighbours(4, 2)
+    got = fuse_depthmaps(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"], min_consistent=3)
+    torch.cuda.synchronize()
+    assert got.points.shape == (0, 3) and got.colors.shape == (0, 3)
+    assert got.view.shape == (0,) and got.pixel.shape == (0,)
+    assert float(got.depth.abs().sum()) == 0.0 and int(got.count.max()) <= 2
+
+
+@pytest.fixture(scope="module")
+def net():
+    from multi_view_stereonet_amd import MultiViewStereoNet
+    from multi_view_stereonet_amd.weights import load_weights
+    torch.set_grad_enabled(False)
+    m = MultiViewStereoNet()
+    m.load_state_dict(load_weights("gta_sfm_150epochs"), strict=True)
+    return m.to(DEV).eval()
+
+
+@pytest.mark.parametrize("batch", [2, 6])     # 2 x 3 sources: recorded plans; 6 x 3 = 18 chains: eager forward
+def test_reconstruct_is_its_composition(net, batch):
+    from multi_view_stereonet_amd import metrics
+    from multi_view_stereonet_amd import multi_view_stereonet_utils as snu
+    V, S, D = 6, 3, 16
+    sc = synthetic.fusion_scene(V, 64, 128, device=DEV)
+    nb = nearest_neighbours(V, S)
+    res, depth = reconstruct(net, sc["images"], sc["K"], sc["T_cam_in_world"], nb, num_idepth_samples=D, batch=batch,
+                             max_rel_depth=0.05, min_consistent=1)
+    # by hand: DataLoader-style batches, unpack, the 7-argument forward, idepth -> depth, one fusion
+    depths = []
+    for lo in range(0, V, batch):
+        ref = list(range(lo, min(lo + batch, V)))
+        frames = {"left_image": sc["images"][ref], "right_image": [sc["images"][nb[ref, s].tolist()] for s in range(S)],
+                  "K": sc["K"].cpu()[ref].unsqueeze(1).contiguous(),
+                  "T_right_in_left": [frame_pair_poses(sc["T_cam_in_world"], ref, nb[ref, s]) for s in range(S)]}
+        inputs = snu.multi_view_unpack_batch(frames, DEV, net.num_levels)
+        out = net(inputs["left_image_pyr"], inputs["K_pyr"], inputs["T_right_in_left"], inputs["right_image_pyr"], D,
+                  True, [True] * 5)
+        depths.append(metrics.idepth_to_depth(out["left_idepthmap_pyr"][0], inputs["baseline"]))
+    want_depth = torch.cat(depths, 0)
+    assert torch.equal(depth, want_depth)
+    want = fuse_depthmaps(want_depth, sc["K"], sc["T_cam_in_world"], nb, images=sc["images"], max_rel_depth=0.05,
+                          min_consistent=1)
+    for x, y in zip(res, want):
+        assert torch.equal(x, y)
+    assert res.points.shape[0] > 0
+
+
+def test_reconstruct_rejects_a_zero_baseline(net):
+    sc = synthetic.fusion_scene(3, 64, 128, device=DEV)
+    T = sc["T_cam_in_world"].clone()
+    T[1] = T[0]                                   # view 1 sits on view 0: zero baseline for view 0's first source
+    with pytest.raises(AssertionError, match="baseline"):
+        reconstruct(net, sc["images"], sc["K"], T, np.array([[1, 2], [0, 2], [1, 0]]), num_idepth_samples=8)

@@ -1,0 +1,68 @@
+"""Time fuse_depthmaps (multi_view_stereonet_amd/fusion.py) on two synthetic analytic scenes (synthetic.fusion_scene):
+V = 64 at 512x256 with M = 4 neighbours, and V = 16 at 1024x512 with M = 8.
+
+Per call: ms between two device events around the whole call (four launches and the one host read of the kept-point
+count), warm-up excluded, and the bytes each kernel must move: the consistency kernel reads the reference depth and
+writes the fused depth and the count map (its neighbour taps are gathered through L2 / MALL and listed separately as
+the logical gather volume), the emit kernel reads the fused depth and writes the points, colours, view and pixel
+arrays.  Prints one JSON line per scene.  The kernel split comes from a rocprofv3 --kernel-trace --stats run of this
+tool."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from multi_view_stereonet_amd import synthetic  # noqa: E402
+from multi_view_stereonet_amd.fusion import fuse_depthmaps  # noqa: E402
+
+SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
+
+
+def neighbours(views, slots):
+    return np.array([sorted((w for w in range(views) if w != v), key=lambda w: (abs(w - v), w))[:slots]
+                     for v in range(views)])
+
+
+def run(V, H, W, M, steps, warmup):
+    dev = torch.device("cuda:0")
+    sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
+    nb = neighbours(V, M)
+    args = (sc["depth"], sc["K"], sc["T_cam_in_world"], nb)
+    for _ in range(warmup):
+        res = fuse_depthmaps(*args, images=sc["images"])
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        res = fuse_depthmaps(*args, images=sc["images"])
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    P, N = H * W, int(res.points.shape[0])
+    return {"scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+            "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
+            "kept_fraction": N / (V * P),
+            "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
+                      "consistency_gather_logical": 16 * V * P * M,
+                      "emit_fused_read": 4 * V * P, "emit_points_written": N * (12 + 3 + 4 + 4)}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    torch.set_grad_enabled(False)
+    for V, H, W, M in SCENES:
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
