@@ -567,6 +567,14 @@ int mvsn_debug_set_band_flags(int flags);
  * outputs and GroupNorm statistics are the same bits either way.  Returns the previous value. */
 int mvsn_debug_set_wino_rowphase(int mode);
 
+/* Host only, no device call: the kernel form a Winograd layer (desc->precision = MVSN_CONV_FP32_WINO) runs on, as the
+ * launch itself selects it -- `carrying` != 0: for a launch that carries a job (mvsn_conv_forward_carry).  out =
+ * { k-steps per step, ring stages, carried units per wave and step, tile form (0 = 16 x 32 tiles, 1 = 10 x 40, 2 =
+ * rolling strips, 3 = row-phase items), full-width input transform, bytes of LDS, work items per sample, steps per item }.
+ * Returns 1, or 0 when no form of the 3x3 / 3x3x3 kernel runs the layer (the 5x5 stride-2 layer has a fixed plan of its
+ * own) or, with `carrying`, when none carries. */
+int mvsn_debug_wino_plan(const mvsn_conv_desc *desc, int carrying, int out[8]);
+
 /* Device self-test of the MFMA fragment mapping the conv kernels rely on (A = 16x4, B = 4x16
  * fp32, asymmetric operands); returns 0 when the on-device result matches the scalar product. */
 int mvsn_selftest_mfma(mvsn_stream_t stream);

@@ -39,6 +39,7 @@
 // GroupNorm partials are one record per (wave, 16-lane row), reduced with DPP adds.  DESIGN.md sections 3.2b / 3.2c
 // have the measurements behind each of these choices, section 3.6 the variants that lost.
 #include <type_traits>
+#include <utility>
 
 #include "mvsn_common.h"
 #include "mvsn_conv_wino.h"
@@ -47,18 +48,17 @@ namespace mvsn {
 
 constexpr int WN_THREADS = 512, WN_WAVES = 8;
 constexpr int WN_TY = 16, WN_TX = 32;                  // output tile
+// the volume form's wide tiles and rolling strips (conv_wino_kernel's WIDE 1 / 2)
+constexpr int WN_WIDE_TY = 10, WN_WIDE_TX = 40, WN_WIDE_PC = WN_WIDE_TX / 2, WN_WIDE_NP = (WN_WIDE_TY / 2) * WN_WIDE_PC;
+constexpr int WN_ROLL_PR = 6, WN_ROLL_NP = WN_ROLL_PR * WN_WIDE_PC, WN_ROLL_HY = 2 * WN_ROLL_PR + 3;
+constexpr int WN_TILE_RP = 3;                          // TILE value of the row-phase items (conv_wino_kernel's RP)
 // haloed raw tile of a layer with dilation DIL (a dilated layer is DIL x DIL interleaved dilation-1 problems:
 // a "2 x 2 patch" is the outputs (y, x), (y, x + DIL), (y + DIL, x), (y + DIL, x + DIL), its input window the
 // 4 x 4 samples at stride DIL)
 constexpr int wn_pa(int dil) { return (dil + 3) / 4 * 4; }                 // halo rounded up to 16-byte columns
-constexpr int wn_xs(int dil) { return WN_TX + 2 * wn_pa(dil); }            // row stride: columns x0 - pa .. x0 + 31 + pa
-// (rp: row-phase items of a dilated layer, see conv_wino_kernel's RP -- 18 rows at stride dil)
-constexpr int wn_hy(int dil, bool rp = false) { return WN_TY + 2 * (rp ? 1 : dil); }                   // haloed rows
-constexpr int wn_groups(int dil, bool rp = false) { return wn_hy(dil, rp) * (wn_xs(dil) / 4); } // 16-byte groups per channel tile
-constexpr int wn_pieces(int dil, bool rp = false) { return (wn_groups(dil, rp) + 63) / 64; }    // DMA instructions per channel
-constexpr int wn_rcst(int dil, bool rp = false) { return wn_hy(dil, rp) * wn_xs(dil) + 16; }    // raw channel stride (floats)
 constexpr int WN_UFLOATS = 16 * 128;                   // U fragments per chunk: [xi][cout tile][lane]
 constexpr int WN_MAX_CHUNKS = 9;                       // resident U: up to 36 input channels (72 KB)
+constexpr int WN_LDS_MAX = 160 * 1024;                 // bytes of LDS a workgroup can have
 
 __device__ floatx4 g_wn_zero16 = {0.f, 0.f, 0.f, 0.f};
 #define WN_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
@@ -104,9 +104,92 @@ __device__ floatx4 g_wn_zero16 = {0.f, 0.f, 0.f, 0.f};
 __device__ unsigned long long *g_wn_stamps = nullptr;
 // (kept in LDS and copied out at the end: a global store per stamp would sit in the vmcnt queue the kernel waits on)
 #define WN_STAMP() do { if (dbg && dbg_on && dbg_i < 120) dbg_lds[dbg_i++] = __builtin_readcyclecounter(); } while (0)
+constexpr int WN_STAMP_BYTES = 1024;
 #else
 #define WN_STAMP() do { } while (0)
+constexpr int WN_STAMP_BYTES = 0;
 #endif
+
+// The kernel forms: one row per instantiation of conv_wino_kernel (template parameters KS .. FULLW as described there;
+// each row exists with and without the input transform, MODE).  wino_select maps a layer to its row, wino_launch
+// instantiates and launches the kernels from the rows.  A row is also the form's LDS plan, in floats from the start of
+// the dynamic LDS: the raw-tile ring (NSTAGE stages of KS x 4 channel tiles), U (resident, in whole steps of the layer's
+// `nchunks` chunks -- an odd count gets a zero chunk; VOL: a ring of NSTAGE steps), the bias, the carried job's residual
+// slots (1 KB per wave and RIDE unit; the volume form carries no residual), the stamp area.  The kernel carves its LDS by
+// it and wino_launch asks for bytes() of it; the build fails if a row, at the most chunks wino_select gives it, does not
+// fit the CU's LDS.  (k-steps per step, ring depth) is what fits next to U -- the raw tile grows with the dilation:
+//   square tiles -- dilation 1: 2 k-steps x 4 stages; 2, 4: 2 x 3; 8: 1 x 3; 4-channel head: 1 x 6; carrying a job:
+//   dilation 4 too on one k-step (its two-k-step ring next to 64 KB of U leaves no room for the residual slots)
+//   row-phase items -- dilations 2, 4: dilation 1's 18 x 40 tile, 2 x 4, carrying 2 x 3; 8 (18 x 48): 2 x 3, carrying
+//   1 x 3 (2 x 3 with the 16 KB of residual slots does not fit: that row does not compile)
+//   volume form: 2 x 3 raw stages + 3 stages of U
+//   (a carrying launch waits with one step of DMA in flight, see RideArgs: a fourth stage would never be used)
+//   ... except the rolling strips without a job: four stages measured 3.84-3.87 against 3.90-3.92 ms per 128 samples of
+//   96 x 30 x 40 (the 16 x 32 tiles: 0.992 either way, they stay at three)
+struct WinoForm {
+  int ks, nstage, dil;
+  bool vol;
+  int ride, tile;
+  bool fullw;
+  int chunks;   // the most input chunks wino_select gives the form (36 channels: 9; volume form: 3 taps x 8)
+  constexpr bool wide() const { return tile == 1 || tile == 2; }
+  // raw rows (rolling strips: two parts around one shared zero row; row-phase items: 18 rows at stride dil)
+  constexpr int hy() const { return tile == 2 ? WN_ROLL_HY : (wide() ? WN_WIDE_TY : WN_TY) + 2 * (tile == WN_TILE_RP ? 1 : dil); }
+  constexpr int xs() const { return (wide() ? WN_WIDE_TX : WN_TX) + 2 * wn_pa(dil); }   // row stride: columns x0 - pa .. x0 + 31 + pa
+  constexpr int rcst() const { return hy() * xs() + 16; }                              // raw channel stride
+  constexpr int stage() const { return ks * 4 * rcst(); }                              // ring stage
+  constexpr int u() const { return nstage * stage(); }                                 // U, behind the ring
+  constexpr int nsteps(int nchunks) const { return (nchunks + ks - 1) / ks; }          // steps per work item
+  constexpr int uchunks(int nchunks) const { return vol ? nstage * ks : nsteps(nchunks) * ks; }   // chunks of U in LDS
+  // what follows U, counted from U (the kernel addresses it from that pointer), given the chunks U holds
+  constexpr int bias(int uch) const { return uch * WN_UFLOATS; }
+  constexpr int res(int uch) const { return bias(uch) + 32; }
+  constexpr int stamps(int uch) const { return res(uch) + (ride > 0 && !vol ? WN_WAVES * ride * 256 : 0); }
+  constexpr size_t bytes(int nchunks) const { return (size_t)(u() + stamps(uchunks(nchunks))) * sizeof(float) + WN_STAMP_BYTES; }
+  constexpr bool same(const WinoForm &o) const {
+    return ks == o.ks && nstage == o.nstage && dil == o.dil && vol == o.vol && ride == o.ride && tile == o.tile && fullw == o.fullw;
+  }
+};
+constexpr WinoForm WN_FORMS[] = {
+    // ks nstage dil vol ride tile fullw chunks
+    {1, 6, 1, false, 0, 0, false, 1},            // the 4-channel head
+    {2, 4, 1, false, 0, 0, false, 8},            // dilation 1
+    {2, 3, 1, false, 0, 0, false, 9},            // ... 36 channels
+    {2, 3, 1, false, 2, 0, false, 8},            // ... carrying
+    {2, 3, 2, false, 0, 0, false, 9},            // square tiles, dilation 2
+    {2, 3, 2, false, 2, 0, false, 8},
+    {2, 3, 4, false, 0, 0, false, 8},            // ... 4
+    {1, 3, 4, false, 1, 0, false, 8},
+    {1, 3, 8, false, 0, 0, false, 8},            // ... 8
+    {1, 3, 8, false, 1, 0, false, 8},
+    {2, 4, 2, false, 0, WN_TILE_RP, false, 8},   // row-phase items, dilation 2
+    {2, 3, 2, false, 0, WN_TILE_RP, false, 9},   // ... 36 channels
+    {2, 3, 2, false, 2, WN_TILE_RP, false, 8},
+    {2, 4, 4, false, 0, WN_TILE_RP, false, 8},   // ... 4
+    {2, 3, 4, false, 2, WN_TILE_RP, false, 8},
+    {2, 3, 8, false, 0, WN_TILE_RP, false, 8},   // ... 8
+    {1, 3, 8, false, 1, WN_TILE_RP, false, 8},
+    {2, 3, 1, true, 0, 0, false, 24},            // volume form, 16 x 32 tiles
+    {2, 3, 1, true, 1, 0, false, 24},
+    {2, 3, 1, true, 0, 0, true, 24},             // ... planes one tile wide (FULLW)
+    {2, 3, 1, true, 1, 0, true, 24},
+    {2, 3, 1, true, 0, 1, false, 24},            // ... 10 x 40 tiles
+    {2, 3, 1, true, 1, 1, false, 24},
+    {2, 4, 1, true, 0, 2, false, 24},            // ... rolling strips
+    {2, 3, 1, true, 1, 2, false, 24},
+};
+constexpr int WN_NFORMS = sizeof(WN_FORMS) / sizeof(WN_FORMS[0]);
+constexpr int wn_find_form(const WinoForm &f, int from = 0) {
+  for (int i = from; i < WN_NFORMS; ++i)
+    if (WN_FORMS[i].same(f)) return i;
+  return -1;
+}
+constexpr bool wn_forms_ok() {   // every row fits the LDS and names a kernel of its own
+  for (int i = 0; i < WN_NFORMS; ++i)
+    if (WN_FORMS[i].bytes(WN_FORMS[i].chunks) > WN_LDS_MAX || wn_find_form(WN_FORMS[i], i + 1) >= 0) return false;
+  return true;
+}
+static_assert(wn_forms_ok(), "a kernel form needs more than 160 KB of LDS, or is listed twice");
 
 // Workgroup barrier that publishes LDS traffic only (LDSONLY): __syncthreads() is a release fence and the compiler puts
 // s_waitcnt vmcnt(0) in front of it -- every step waits for ALL DMA pieces and output stores in flight.  A wave's own
@@ -278,8 +361,6 @@ __global__ void wino_pack_kernel(const float *__restrict__ w, int cin, int cout,
 //         descriptor that starts at plane zA + kz - 1 (planes are contiguous), a B lane's offset being one plane further.
 //         Per item only s changes: the lane's first raw row (ya: one row further down for B patches), the DMA plan
 //         and the epilogue's per-lane plane / row.  Items never span samples (a sample's last item may be short).
-constexpr int WN_WIDE_TY = 10, WN_WIDE_TX = 40, WN_WIDE_PC = WN_WIDE_TX / 2, WN_WIDE_NP = (WN_WIDE_TY / 2) * WN_WIDE_PC;
-constexpr int WN_ROLL_PR = 6, WN_ROLL_NP = WN_ROLL_PR * WN_WIDE_PC, WN_ROLL_HY = 2 * WN_ROLL_PR + 3;
 // FULLW   (round 6) the tile spans the WHOLE plane width (W = 32: the 16 x 32 coarse grid's regulariser): neighbouring
 //         patches overlap by two columns, so lane p forms the column sums t[.][1], t[.][2] of ITS OWN two image columns
 //         2p, 2p + 1 only (8 adds instead of 16, half the raw-tile reads: one 8-byte read per row) and takes t[.][0] /
@@ -303,7 +384,6 @@ constexpr int WN_ROLL_PR = 6, WN_ROLL_NP = WN_ROLL_PR * WN_WIDE_PC, WN_ROLL_HY =
 #else
 #define MVSN_WN_FULLW_OK 0
 #endif
-constexpr int WN_TILE_RP = 3;
 template <int MODE, int KS, int NSTAGE, int DIL, bool VOL = false, int RIDE = 0, int TILE = 0, bool FULLW = false>
 __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, const float *__restrict__ in,
                                                                   const float *__restrict__ upk,
@@ -332,17 +412,18 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   constexpr bool ROLL = WIDE == 2;
   constexpr int TY = ROLL ? 2 * WN_ROLL_PR : (WIDE ? WN_WIDE_TY : WN_TY), TX = WIDE ? WN_WIDE_TX : WN_TX;
   static_assert(!RP || (DIL > 1 && !VOL && !WIDE), "row-phase items: dilated 2-D layers");
-  constexpr int HY = ROLL ? WN_ROLL_HY : TY + 2 * (RP ? 1 : DIL);   // raw rows (ROLL: two parts around one shared zero row)
+  constexpr WinoForm L{KS, NSTAGE, DIL, VOL, RIDE, TILE, FULLW};   // (as an LDS plan)
+  constexpr int HY = L.hy(), XS = L.xs();                // raw rows (ROLL: two parts around one shared zero row), row stride
   constexpr int VS = RP ? 1 : DIL;                       // raw rows between a patch's vertical taps
   constexpr int YS = RP ? DIL : 1;                       // image rows between raw rows
   // first output row of item row tq (RP: tq = phase tile row x DIL + phase; the item's rows follow at stride DIL)
   auto item_y0 = [](int tq) { return RP ? (tq & (DIL - 1)) + (int)((unsigned)tq / DIL) * (TY * DIL) : tq * TY; };
   constexpr int NP = ROLL ? WN_ROLL_NP : WN_WIDE_NP;     // WIDE: patches among the tile's 128 slots
-  constexpr int PA = wn_pa(DIL), XS = TX + 2 * PA, DQ = XS / 4, GROUPS = HY * DQ, PIECES = (GROUPS + 63) / 64;
-  constexpr int RCST = HY * XS + 16;
-  static_assert(WIDE || (XS == wn_xs(DIL) && GROUPS == wn_groups(DIL, RP) && PIECES == wn_pieces(DIL, RP) && RCST == wn_rcst(DIL, RP)), "");
-  constexpr int STAGE = KS * 4 * RCST;               // ring stage (floats)
-  float *U = smem + NSTAGE * STAGE;                  // nchunks * WN_UFLOATS, resident (VOL: ring of NSTAGE steps)
+  // 16-byte groups per channel tile, DMA instructions per channel
+  constexpr int PA = wn_pa(DIL), DQ = XS / 4, GROUPS = HY * DQ, PIECES = (GROUPS + 63) / 64;
+  static_assert(XS == TX + 2 * PA && HY == (ROLL ? WN_ROLL_HY : TY + 2 * VS), "the LDS plan's raw tile is this kernel's tile plus its halo");
+  constexpr int RCST = L.rcst(), STAGE = L.stage();  // raw channel stride, ring stage (floats)
+  float *U = smem + L.u();                           // nchunks * WN_UFLOATS, resident (VOL: ring of NSTAGE steps)
   // dilation 1: raw tiles stored one float further (4-byte-aligned DMA destination), see tr_load
   // (FULLW: no shift -- a lane reads its OWN two columns, which then start at an even float)
   static_assert(!FULLW || (DIL == 1 && WIDE == 0 && MVSN_WN_XF == 2 && MVSN_WN_TRANSPOSED), "full-width form: 16 x 32 tiles, burst + block");
@@ -355,7 +436,8 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   constexpr bool TR = DIL == 1 && MVSN_WN_TRANSPOSED;
   static_assert(!VOL || (KS == 2 && DIL == 1), "volume form: 32 channels in steps of 8, dilation 1");
   const int nsteps = (g.nchunks + KS - 1) / KS;      // steps per tile
-  const int uchunks = nsteps * KS;                   // chunks of U in LDS: whole steps (an odd count gets a zero chunk)
+  // chunks of U in LDS: whole steps (an odd count gets a zero chunk); VOL: the ring's
+  const int uchunks = VOL ? NSTAGE * KS : nsteps * KS;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -375,8 +457,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   const int slot = xcd_tile_index(blockIdx.x, G);
 #ifdef MVSN_WN_STAMPS
   unsigned long long *dbg = (blockIdx.x == gridDim.x / 3 && tid == 0) ? g_wn_stamps : nullptr;
-  unsigned long long *dbg_lds = reinterpret_cast<unsigned long long *>(
-      U + (VOL ? NSTAGE * UST : uchunks * WN_UFLOATS) + 32 + (RIDE > 0 ? WN_WAVES * RIDE * 256 : 0));
+  unsigned long long *dbg_lds = reinterpret_cast<unsigned long long *>(U + L.stamps(uchunks));
   int dbg_i = 0;
   bool dbg_on = true;
 #endif
@@ -393,7 +474,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
 
   // the bias is read from LDS in the tile epilogue: as a global load its s_waitcnt vmcnt(0) would drain the DMA ring
   // (which runs ahead into the next tile) once per tile
-  float *bias_lds = U + (VOL ? NSTAGE * UST : uchunks * WN_UFLOATS);
+  float *bias_lds = U + L.bias(uchunks);
   if (tid < 32) bias_lds[tid] = bias ? bias[tid] : 0.0f;   // published by the first barrier
 
   // ---- prefetcher state: DMA of (item, chunk) steps runs two steps ahead of the multiplies
@@ -796,7 +877,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv_wino_kernel(WinoArgs g, co
   float rd_sc = 0.f, rd_sh = 0.f, rd_rsc = 0.f, rd_rsh = 0.f;   // wave-uniform
   int rd_u = 0;                                                 // first unit in flight
   bool rd_ok = false;                                           // ... is one of the job's
-  float *rds = U + (VOL ? NSTAGE * UST : uchunks * WN_UFLOATS) + 32 + wave * (RN * 256);
+  float *rds = U + L.res(uchunks) + wave * (RN * 256);
   auto rd_issue = [&](int flat, int chunk) {   // flat < 0: nothing to fetch (the set-up's and the last step's)
     if constexpr (RIDE > 0) {
       const int u = ((flat * nsteps + chunk) * WN_WAVES + wave) * RN;
@@ -1590,47 +1671,47 @@ int wino_pack(const mvsn_conv_desc *d, const float *weight, float *packed, hipSt
   return check_launch("mvsn_conv_pack_weights(winograd)");
 }
 
-// (k-steps per step, ring depth) of the 2-D / volume layers by what fits next to the resident U: the raw tile grows with
-// the dilation
-//   square tiles -- dilation 1: 2 k-steps x 4 stages (94 KB); 2, 4: 2 x 3 (78 / 94 KB); 8: 1 x 3 (74 KB); 4-channel head:
-//   1 x 6; carrying a job: dilation 4 too on one k-step (its two-k-step ring, 94 KB next to 64 KB of U, leaves no room for
-//   the residual slots)
-//   row-phase items -- dilations 2, 4: dilation 1's 18 x 40 tile, 2 x 4 (92 KB), carrying 2 x 3; 8 (18 x 48): 2 x 3
-//   (83 KB), carrying 1 x 3 (2 x 3 and the 16 KB of residual slots would need 163 KB)
-//   volume form: 2 x 3 raw stages + 3 stages of U (118 KB)
-struct WinoPlan {
-  int ks, nstage;
-};
-static WinoPlan wino_plan(const WinoGeom &g, bool job) {
-  const bool head = g.nchunks == 1;
-  if (g.rpy) return WinoPlan{(job && g.dil == 8) ? 1 : 2, (g.dil <= 4 && g.nchunks <= 8 && !job) ? 4 : 3};
-  // (a carrying launch waits with one step of DMA in flight, see RideArgs: a fourth stage would never be used)
-  // ... except the rolling strips without a job: four stages (158 KB) measured 3.84-3.87 against 3.90-3.92 ms per 128
-  // samples of 96 x 30 x 40 (the 16 x 32 tiles: 0.992 either way, they stay at three)
-  return WinoPlan{(head || g.dil == 8 || (job && g.dil == 4)) ? 1 : 2,
-                  head ? 6 : (((g.dil == 1 && g.nchunks <= 8 && !job) || (g.vol && g.wide == 2 && !job)) ? 4 : 3)};
-}
-
-// RIDE units per wave and step of the instantiation a layer runs on (0: that kernel carries nothing)
-static int wino_ride_units(const WinoGeom &g) {
-  if (g.s2) return 0;
-  if (g.vol) return 1;         // 12 steps per (plane, tile): 96 units, of which a job of the layer's own size needs 64
-  if (g.nchunks != 8) return 0;
-  // 4 steps of two k-steps / 8 steps of one: 64 units = 64 KB per tile either way
-  return wino_plan(g, true).ks == 2 ? 2 : 1;
+// The form a layer runs on (its row of WN_FORMS; -1: none), `job`: for a launch that carries a job.  The only place that
+// knows which geometry maps to which form.
+static int wino_select(const WinoGeom &g, bool job) {
+  if (g.s2) return -1;   // (conv_wino_s2_kernel has its own static plan)
+  const bool head = g.nchunks == 1, rp = g.rpy > 0;
+  WinoForm f = {};
+  f.dil = g.dil, f.vol = g.vol, f.tile = rp ? WN_TILE_RP : g.wide;
+  // volume form on planes one tile wide (the 16 x 32 coarse grid): neighbouring lanes share the input transform's column
+  // sums (FULLW, see conv_wino_kernel)
+  f.fullw = MVSN_WN_FULLW_OK && g.vol && !g.wide && g.ntx == 1 && g.W <= WN_TX;
+  f.ks = (head || (rp ? job && g.dil == 8 : g.dil == 8 || (job && g.dil == 4))) ? 1 : 2;
+  const bool four = !job && ((!g.vol && g.nchunks <= 8 && (rp ? g.dil <= 4 : g.dil == 1)) || g.wide == 2);
+  f.nstage = head ? 6 : (four ? 4 : 3);
+  // RIDE units per wave and step.  Volume form: 12 steps per (plane, tile) = 96 units, of which a job of the layer's own
+  // size needs 64; 32 channels: 4 steps of two k-steps / 8 steps of one, 64 units = 64 KB per tile either way; no other
+  // layer carries
+  f.ride = !job ? 0 : (g.vol ? 1 : (g.nchunks == 8 ? f.ks : 0));
+  if (job && !f.ride) return -1;
+  const int row = wn_find_form(f);   // (dilated 4-channel layers are not instantiated)
+  return row >= 0 && g.nchunks <= WN_FORMS[row].chunks ? row : -1;
 }
 
 bool wino_can_carry(const WinoGeom &g, const mvsn_apply_job *job) {
-  const int r = wino_ride_units(g);
-  if (!r || !job || !job->x || !job->stats || !job->gamma || !job->beta || !job->out || job->n <= 0) return false;
+  const int row = wino_select(g, true);
+  if (row < 0 || !job || !job->x || !job->stats || !job->gamma || !job->beta || !job->out || job->n <= 0) return false;
+  const int r = WN_FORMS[row].ride;
   if (job->spatial <= 0 || job->spatial % (256 * r) != 0) return false;   // a step's units lie in one plane
   if (job->r_stats && !(job->residual && job->r_gamma && job->r_beta)) return false;
   if ((((size_t)job->x | (size_t)job->out | (size_t)job->residual) & 15) != 0) return false;
   const long units = (long)job->n * 32 * (job->spatial / 256);
   if (g.vol && job->residual) return false;   // (no residual slots next to the volume form's two rings)
-  const int nsteps = g.vol ? 12 : 8 / wino_plan(g, true).ks;
-  const long capacity = (long)g.n * wino_work_items(g) * nsteps * WN_WAVES * r;   // unit indices are 32-bit in the kernel
+  const long capacity = (long)g.n * wino_work_items(g) * WN_FORMS[row].nsteps(g.nchunks) * WN_WAVES * r;   // unit indices are 32-bit in the kernel
   return units <= capacity && capacity < (1L << 31) && units < (1L << 30);
+}
+
+// f(integral_constant<I>) for the row I == row: the fold that turns the run-time row into a compile-time one
+template <class F, size_t... I>
+static int wn_with_row(int row, std::index_sequence<I...>, F &&f) {
+  int rc = MVSN_E_BADARG;
+  (void)((row == (int)I && ((rc = f(std::integral_constant<int, (int)I>{})), true)) || ...);
+  return rc;
 }
 
 int wino_launch(const WinoGeom &g, const float *in, const float *upk, const float *bias, const float *in_stats,
@@ -1676,74 +1757,32 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
   a.rev = (job && job->reverse == 1) ? 1 : 0;
   a.cs0 = (size_t)g.H * g.W, a.bs0 = (size_t)a.cb0 * a.cs0;
   if (blocks && blocks->cs0) a.cs0 = blocks->cs0, a.bs0 = blocks->bs0;
-  const int cus = device_cus();
-  const bool head = g.nchunks == 1;
-  const WinoPlan plan = wino_plan(g, job != nullptr);
-  const int ks = plan.ks, nstage = plan.nstage;
-  const size_t rcst = g.wide ? (size_t)(g.wide == 2 ? WN_ROLL_HY : WN_WIDE_TY + 2) * (WN_WIDE_TX + 2 * wn_pa(1)) + 16
-                             : (size_t)wn_rcst(g.dil, g.rpy > 0);
-  size_t lds = ((size_t)nstage * ks * 4 * rcst +
-                (g.vol ? (size_t)nstage * ks : (size_t)((g.nchunks + ks - 1) / ks * ks)) * WN_UFLOATS) * sizeof(float);
-  lds += 32 * sizeof(float);                                      // bias
-  if (job && !g.vol) lds += (size_t)WN_WAVES * wino_ride_units(g) * 1024;   // the carried job's residual slots
-#ifdef MVSN_WN_STAMPS
-  lds += 1024;   // stamp area
-#endif
-  if (head && g.dil != 1) {
-    set_error("mvsn_conv_forward(winograd): dilated 4-channel layers are not instantiated");
+  const int row = wino_select(g, job != nullptr);
+  if (row < 0) {
+    set_error("mvsn_conv_forward(winograd): no kernel form for this layer");
     return MVSN_E_BADARG;
   }
-  if (lds > 160 * 1024) {
-    set_error("mvsn_conv_forward(winograd): %zu bytes of LDS needed", lds);
-    return MVSN_E_TOOLARGE;
-  }
-  dim3 grid(1);
-#define WN_CASE(M, K, N, D, ...)                                                                                   \
-  do {                                                                                                             \
-    static LdsOptIn opt;                                                                                           \
-    if (int rc = ensure_lds(opt, (const void *)conv_wino_kernel<M, K, N, D, ##__VA_ARGS__>, lds,                   \
-                            "mvsn_conv_forward(winograd)"))                                                        \
-      return rc;                                                                                                   \
-    hipLaunchKernelGGL((conv_wino_kernel<M, K, N, D, ##__VA_ARGS__>), grid, dim3(WN_THREADS), lds, stream, a, in,  \
-                       upk, bias,                                                                                  \
-                       in_stats, in_gamma, in_beta, out, out_partials, rd, (const void *)a.in1, (const void *)a.in2, \
-                       (const void *)rd.x, (const void *)rd.stats, (const void *)rd.res, (const void *)rd.r_stats,  \
-                       (const void *)rd.out, (const void *)nullptr, (const void *)nullptr, (const void *)nullptr);  \
-  } while (0)
+  const size_t lds = WN_FORMS[row].bytes(g.nchunks);
+  const int cus = device_cus();
   const long total = (long)g.n * wino_work_items(g);
-  grid = dim3((unsigned)(total < cus ? total : cus));   // persistent: one workgroup per CU walks items grid-strided
+  const dim3 grid((unsigned)(total < cus ? total : cus));   // persistent: one workgroup per CU walks items grid-strided
+  // the kernel of (MODE, row I): instantiated here, once per row and mode, with its own LdsOptIn
+  auto launch = [&](auto mode, auto I) -> int {
+    constexpr WinoForm F = WN_FORMS[decltype(I)::value];
+    const auto kernel = conv_wino_kernel<decltype(mode)::value, F.ks, F.nstage, F.dil, F.vol, F.ride, F.tile, F.fullw>;
+    static LdsOptIn opt;
+    if (int rc = ensure_lds(opt, (const void *)kernel, lds, "mvsn_conv_forward(winograd)")) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(WN_THREADS), lds, stream, a, in, upk, bias, in_stats, in_gamma, in_beta, out,
+                       out_partials, rd, (const void *)a.in1, (const void *)a.in2, (const void *)rd.x,
+                       (const void *)rd.stats, (const void *)rd.res, (const void *)rd.r_stats, (const void *)rd.out,
+                       (const void *)nullptr, (const void *)nullptr, (const void *)nullptr);
+    return 0;
+  };
   const bool xf = in_stats != nullptr;
-  // volume form on planes one tile wide (the 16 x 32 coarse grid): neighbouring lanes share the input transform's column
-  // sums (FULLW, see conv_wino_kernel)
-  const bool fullw = MVSN_WN_FULLW_OK && g.vol && !g.wide && g.ntx == 1 && g.W <= WN_TX;
-  if (job) {   // the same kernels with the carried job's loads / stores in their steps
-    if (g.vol && g.wide == 2) { if (xf) WN_CASE(1, 2, 3, 1, true, 1, 2); else WN_CASE(0, 2, 3, 1, true, 1, 2); }
-    else if (g.vol && g.wide) { if (xf) WN_CASE(1, 2, 3, 1, true, 1, 1); else WN_CASE(0, 2, 3, 1, true, 1, 1); }
-    else if (g.vol && fullw) { if (xf) WN_CASE(1, 2, 3, 1, true, 1, 0, true); else WN_CASE(0, 2, 3, 1, true, 1, 0, true); }
-    else if (g.vol) { if (xf) WN_CASE(1, 2, 3, 1, true, 1); else WN_CASE(0, 2, 3, 1, true, 1); }
-    else if (g.dil == 1) { if (xf) WN_CASE(1, 2, 3, 1, false, 2); else WN_CASE(0, 2, 3, 1, false, 2); }
-    else if (g.rpy && g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2, false, 2, WN_TILE_RP); else WN_CASE(0, 2, 3, 2, false, 2, WN_TILE_RP); }
-    else if (g.rpy && g.dil == 4) { if (xf) WN_CASE(1, 2, 3, 4, false, 2, WN_TILE_RP); else WN_CASE(0, 2, 3, 4, false, 2, WN_TILE_RP); }
-    else if (g.rpy) { if (xf) WN_CASE(1, 1, 3, 8, false, 1, WN_TILE_RP); else WN_CASE(0, 1, 3, 8, false, 1, WN_TILE_RP); }
-    else if (g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2, false, 2); else WN_CASE(0, 2, 3, 2, false, 2); }
-    else if (g.dil == 4) { if (xf) WN_CASE(1, 1, 3, 4, false, 1); else WN_CASE(0, 1, 3, 4, false, 1); }
-    else { if (xf) WN_CASE(1, 1, 3, 8, false, 1); else WN_CASE(0, 1, 3, 8, false, 1); }
-  } else
-  if (g.vol && g.wide == 2) { if (xf) WN_CASE(1, 2, 4, 1, true, 0, 2); else WN_CASE(0, 2, 4, 1, true, 0, 2); }
-  else if (g.vol && g.wide) { if (xf) WN_CASE(1, 2, 3, 1, true, 0, 1); else WN_CASE(0, 2, 3, 1, true, 0, 1); }
-  else if (g.vol && fullw) { if (xf) WN_CASE(1, 2, 3, 1, true, 0, 0, true); else WN_CASE(0, 2, 3, 1, true, 0, 0, true); }
-  else if (g.vol) { if (xf) WN_CASE(1, 2, 3, 1, true); else WN_CASE(0, 2, 3, 1, true); }
-  else if (head) { if (xf) WN_CASE(1, 1, 6, 1); else WN_CASE(0, 1, 6, 1); }
-  else if (g.dil == 1 && g.nchunks > 8) { if (xf) WN_CASE(1, 2, 3, 1); else WN_CASE(0, 2, 3, 1); }
-  else if (g.dil == 1) { if (xf) WN_CASE(1, 2, 4, 1); else WN_CASE(0, 2, 4, 1); }
-  else if (g.rpy && g.dil == 2 && nstage == 3) { if (xf) WN_CASE(1, 2, 3, 2, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 3, 2, false, 0, WN_TILE_RP); }
-  else if (g.rpy && g.dil == 2) { if (xf) WN_CASE(1, 2, 4, 2, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 4, 2, false, 0, WN_TILE_RP); }
-  else if (g.rpy && g.dil == 4) { if (xf) WN_CASE(1, 2, 4, 4, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 4, 4, false, 0, WN_TILE_RP); }
-  else if (g.rpy) { if (xf) WN_CASE(1, 2, 3, 8, false, 0, WN_TILE_RP); else WN_CASE(0, 2, 3, 8, false, 0, WN_TILE_RP); }
-  else if (g.dil == 2) { if (xf) WN_CASE(1, 2, 3, 2); else WN_CASE(0, 2, 3, 2); }
-  else if (g.dil == 4) { if (xf) WN_CASE(1, 2, 3, 4); else WN_CASE(0, 2, 3, 4); }
-  else { if (xf) WN_CASE(1, 1, 3, 8); else WN_CASE(0, 1, 3, 8); }
-#undef WN_CASE
+  if (int rc = wn_with_row(row, std::make_index_sequence<WN_NFORMS>{}, [&](auto I) {
+        return xf ? launch(std::integral_constant<int, 1>{}, I) : launch(std::integral_constant<int, 0>{}, I);
+      }))
+    return rc;
   return check_launch("mvsn_conv_forward(winograd)");
 }
 
@@ -1753,6 +1792,18 @@ extern "C" int mvsn_debug_set_wino_rowphase(int mode) {
   const int old = mvsn::g_wn_rowphase;
   mvsn::g_wn_rowphase = mode;
   return old;
+}
+
+// host only: what wino_select and the form's LDS plan say about a layer (no logic of its own)
+extern "C" int mvsn_debug_wino_plan(const mvsn_conv_desc *desc, int carrying, int out[8]) {
+  mvsn::WinoGeom g;
+  if (!out || !mvsn::wino_geom(desc, &g)) return 0;
+  const int row = mvsn::wino_select(g, carrying != 0);
+  if (row < 0) return 0;
+  const mvsn::WinoForm &f = mvsn::WN_FORMS[row];
+  out[0] = f.ks, out[1] = f.nstage, out[2] = f.ride, out[3] = f.tile, out[4] = f.fullw;
+  out[5] = (int)f.bytes(g.nchunks), out[6] = (int)mvsn::wino_work_items(g), out[7] = f.nsteps(g.nchunks);
+  return 1;
 }
 
 #ifdef MVSN_WN_STAMPS

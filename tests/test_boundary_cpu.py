@@ -91,6 +91,57 @@ def test_conv_planning_is_host_side_and_validates():
     assert lib.mvsn_incremental_cost_volume_workspace_bytes(1, 32, 64) > 0        # config 5 grid
 
 
+def test_winograd_form_selection_is_pinned_host_side():
+    """Which kernel form every Winograd layer runs on -- (k-steps, ring stages, carried units, tile form, full-width
+    transform) -- its LDS bytes, work items per sample and steps per item, through mvsn_debug_wino_plan (host only).  The
+    expected rows are the plans and launch branches of the code before the forms became one table."""
+    lib = _native.load()
+    RP = 3
+
+    def plan(cin, rows, cols, dil=1, depth=1, kd=1, carrying=0, k=3, stride=1):
+        d = _native.ConvDesc(1, cin, 32, depth, rows, cols, kd, k, k, stride, dil, _native.CONV_FP32_WINO)
+        out = (ctypes.c_int * 8)()
+        return list(out) if lib.mvsn_debug_wino_plan(ctypes.byref(d), carrying, ctypes.byref(out)) else None
+
+    def forms(*a, **kw):
+        return tuple(p and tuple(p[:5]) for p in (plan(*a, **kw), plan(*a, carrying=1, **kw)))
+
+    old = lib.mvsn_debug_set_wino_rowphase(0)
+    try:
+        # 2-D layers on 256 x 512
+        assert forms(32, 256, 512) == ((2, 4, 0, 0, 0), (2, 3, 2, 0, 0))
+        assert plan(32, 256, 512)[5:] == [4 * 2 * 4 * 736 * 4 + 8 * 2048 * 4 + 128, 16 * 16, 4] and 159872 == 4 * 2 * 4 * 736 * 4 + 8 * 2048 * 4 + 128
+        assert plan(32, 256, 512, carrying=1)[5:] == [3 * 2 * 4 * 736 * 4 + 8 * 2048 * 4 + 128 + 8 * 2 * 1024, 16 * 16, 4]
+        assert forms(36, 256, 512) == ((2, 3, 0, 0, 0), None)            # 36 -> 32 channels: nothing carries
+        assert plan(36, 256, 512)[5:] == [3 * 2 * 4 * 736 * 4 + 10 * 2048 * 4 + 128, 16 * 16, 5]   # (a zero tenth chunk)
+        assert forms(4, 256, 512) == ((1, 6, 0, 0, 0), None)             # the head
+        for dil in (2, 4):                                               # row-phase items
+            assert forms(32, 256, 512, dil) == ((2, 4, 0, RP, 0), (2, 3, 2, RP, 0)), dil
+        assert forms(36, 256, 512, 2) == ((2, 3, 0, RP, 0), None)
+        assert forms(32, 256, 512, 8) == ((2, 3, 0, RP, 0), (1, 3, 1, RP, 0))
+        assert plan(32, 256, 512, 8, carrying=1)[5:] == [3 * 4 * 880 * 4 + 65536 + 128 + 8192, 8 * 2 * 16, 8]
+        assert 3 * 4 * 880 * 4 + 65536 + 128 + 8192 == 116096
+        assert forms(32, 40, 512, 8) == ((1, 3, 0, 0, 0), (1, 3, 1, 0, 0))   # 8 phases x 1 item row > 3 tile rows: square
+        assert forms(4, 256, 512, 2) == (None, None) and forms(36, 256, 512, 4) == (None, None)   # not instantiated
+        assert plan(32, 256, 512, k=5, stride=2, carrying=1) is None     # the stride-2 layer carries nothing
+        lib.mvsn_debug_set_wino_rowphase(2)                              # square tiles only
+        assert forms(32, 256, 512, 2) == ((2, 3, 0, 0, 0), (2, 3, 2, 0, 0))
+        assert forms(32, 256, 512, 4) == ((2, 3, 0, 0, 0), (1, 3, 1, 0, 0))
+        assert forms(32, 256, 512, 8) == ((1, 3, 0, 0, 0), (1, 3, 1, 0, 0))
+        assert plan(32, 256, 512, 4)[5:] == [3 * 2 * 4 * (24 * 40 + 16) * 4 + 65536 + 128, 16 * 16, 4]
+        lib.mvsn_debug_set_wino_rowphase(0)
+        # volume form
+        assert forms(32, 16, 32, depth=64, kd=3) == ((2, 3, 0, 0, 1), (2, 3, 1, 0, 1))
+        assert forms(32, 64, 128, depth=64, kd=3)[0] == (2, 3, 0, 0, 0)
+        assert forms(32, 10, 40, depth=64, kd=3)[0] == (2, 3, 0, 1, 0)
+        assert forms(32, 30, 40, depth=96, kd=3) == ((2, 4, 0, 2, 0), (2, 3, 1, 2, 0))
+        # rolling strips: 15 raw rows x 48 columns; U streams through 4 (3 when carrying) stages of two chunks
+        assert plan(32, 30, 40, depth=96, kd=3)[5:] == [4 * 2 * 4 * (15 * 48 + 16) * 4 + 4 * 2 * 2048 * 4 + 128, 240, 12]
+        assert plan(32, 30, 40, depth=96, kd=3, carrying=1)[5:] == [3 * 2 * 4 * 736 * 4 + 3 * 2 * 2048 * 4 + 128, 240, 12]
+    finally:
+        lib.mvsn_debug_set_wino_rowphase(old)
+
+
 def test_banded_plan_selection_host_logic():
     """Which plan a banded call runs, and what it needs, from the host side alone (no device: the library assumes 256
     CUs): thin bands while the chains fit one of their passes, slabs beyond (mvsn_chain_slab.hip); passes of equal size, or
