@@ -52,7 +52,8 @@ const char *mvsn_last_error(void);
  *   idepth_samples (N,D)  H_lvl4 (N,D,3,3)  H_inc (N,D,3,3)  H_lvl0_plane0 (N,3,3)  baseline (N)
  * The idepth samples and the three homography outputs carry the bits of the reference's own fp32 evaluation (its
  * per-pixel tensor program and torch.sum's order; torch's CPU inverse of the pose, of the intrinsics and of H[d-1],
- * its 3x3 products: csrc/mvsn_setup.hip, namespace ref32; pinned by tests/golden/g11_incremental_homographies.npz)
+ * its 3x3 products: csrc/mvsn_setup.hip, namespace ref32; pinned by tests/golden/g11_incremental_homographies.npz and,
+ * for fx != fy, off-centre principal points and pyramids scaled differently in x and y, g12_camera_forms.npz)
  * when the intrinsics are [[fx,0,cx],[0,fy,cy],[0,0,1]]; for any other intrinsics they are a double-precision
  * evaluation rounded once.
  * ------------------------------------------------------------------------------------------- */
@@ -67,6 +68,13 @@ int mvsn_plane_sweep_setup_sources(const float *const *T_right_in_lefts, int n_s
                                    const float *K_lvl4, int batch, int rows4, int cols4, int num_idepth_samples,
                                    float *idepth_samples, float *H_lvl4, float *H_inc, float *H_lvl0_plane0,
                                    float *baseline, mvsn_stream_t stream);
+
+/* Host only, no device call: the order one chain's outputs are formed in, by the predicate the kernel itself evaluates
+ * on that chain's level-0 and level-4 intrinsics (each one row-major 4x4, HOST memory) and the level-4 grid.  Bit 0
+ * (value 1): H_lvl0_plane0, H_lvl4 and H_inc in the reference's fp32 order; bit 1 (value 2): the idepth samples too.
+ * 3 for every pin-hole K on a level-4 grid of 8 .. 8192 pixels, 1 outside that range, 0 for a K with a shear term or any
+ * other entry off [[fx,0,cx],[0,fy,cy],[0,0,1]] (and for null pointers or non-positive sizes). */
+int mvsn_plane_sweep_setup_path(const float *K_lvl0_host, const float *K_lvl4_host, int rows4, int cols4);
 
 /* ---------------------------------------------------------------------------------------------
  * Homography warp with bilinear, clamp-to-edge sampling and out-of-image zeroing.

@@ -47,6 +47,7 @@ SIGNATURES = {
     "mvsn_last_error": (c_char_p, []),
     "mvsn_plane_sweep_setup": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 5 + [c_void_p]),
     "mvsn_plane_sweep_setup_sources": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_void_p]),
+    "mvsn_plane_sweep_setup_path": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "mvsn_gather_focal": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
     "mvsn_homography_warp": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 2 + [c_void_p]),
     "mvsn_feature_refiner_packed_floats": (c_size_t, []),
@@ -157,6 +158,14 @@ def ptr(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def plane_sweep_setup_path(K_lvl0, K_lvl4, rows4: int, cols4: int):
+    """Per chain of K_lvl0 / K_lvl4 (N,4,4), the order mvsn_plane_sweep_setup forms its outputs in (bit 0: homographies,
+    bit 1: idepth samples in the reference's fp32 order) -- the kernel's own predicate, evaluated on the host."""
+    lib = load()
+    K0, K4 = (k.detach().to("cpu", torch.float32).contiguous() for k in (K_lvl0, K_lvl4))
+    return [lib.mvsn_plane_sweep_setup_path(K0[n].data_ptr(), K4[n].data_ptr(), rows4, cols4) for n in range(K0.shape[0])]
 
 
 def check(rc: int, what: str):

@@ -4,6 +4,11 @@
 // products, sgemm and summation order, found by matching bits on the host and pinned by tests/golden/g11), so that the
 // outputs carry the reference's bits; a double-precision evaluation, rounded once where the reference's pipeline
 // rounds, remains for intrinsics of another form (and for level-4 grids outside 8 .. 8192 pixels: the samples).
+// Which cameras get the reference's bits: every pin-hole K = [[fx,0,cx],[0,fy,cy],[0,0,1]] at levels 0 and 4 -- fx != fy,
+// principal points anywhere (off-centre, half-pixel, zero, negative), a K per batch element, pyramids scaled
+// differently in x and y; pinned by tests/golden/g11 (isotropic, centred) and g12 (all of the others).  Which do not:
+// a K with a shear term or any other entry off that form.  One predicate decides (setup_path below); the kernel and the
+// host query mvsn_plane_sweep_setup_path both call it, so a test can assert the path it means to test.
 // include/mvsn_hip.h names the call sites replaced.
 #include "mvsn_common.h"
 
@@ -12,6 +17,25 @@
 #endif
 
 namespace mvsn {
+
+constexpr int SETUP_THREADS = 256;
+constexpr int SETUP_MAX_PIXELS = 8192;   // level-4 pixels the reference-order sample path holds in LDS (else: the double path)
+
+// K (row-major 4x4) has the reference's form [[fx,0,cx],[0,fy,cy],[0,0,1]] in its 3x3 (anything else keeps the fp64 path)
+__host__ __device__ inline bool pinhole_form(const float *K) {
+  return K[1] == 0.f && K[4] == 0.f && K[8] == 0.f && K[9] == 0.f && K[10] == 1.f && K[0] != 0.f && K[5] != 0.f;
+}
+
+// THE predicate: which of a chain's outputs are formed in the reference's fp32 order (namespace ref32), from its level-0
+// and level-4 intrinsics and the level-4 grid.  MVSN_PATH_H: H0, H4 and H_inc; MVSN_PATH_SAMPLES: the idepth samples
+// (only with the homographies, and only for 8 .. 8192 level-4 pixels: a shorter row takes another ATen sum, a longer one
+// does not fit the LDS buffer).  0: everything from the fp64 evaluation.
+constexpr int MVSN_PATH_H = 1, MVSN_PATH_SAMPLES = 2;
+__host__ __device__ inline int setup_path(const float *K0, const float *K4, int rows4, int cols4) {
+  if (MVSN_SETUP_FP64_H || !pinhole_form(K0) || !pinhole_form(K4)) return 0;
+  const long long P = (long long)rows4 * cols4;
+  return MVSN_PATH_H | (P >= 8 && P <= SETUP_MAX_PIXELS ? MVSN_PATH_SAMPLES : 0);
+}
 
 __device__ inline void inv3(const double *m, double *o) {
   double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
@@ -65,8 +89,12 @@ __device__ inline void plane_homography(const double *K3, const double *K3inv, c
 //     reference's permuted (D,B,3,3) family is contiguous for every batch size, so this is the same shortcut): LU of
 //     the transpose as above; y without a fused operation; x2 = y2; x1 = fma(-l21, x2, y1);
 //     x0 = y0 - fma(l10, x1, l20 x2)       (5400 of 5400 entries of random matrices, every H tried);
-//   * inverse(K[:, :3, :3]) of an upper-triangular intrinsics matrix = LAPACK strti2: reciprocal diagonal,
-//     -(c * (1 / f)) above it;
+//   * inverse(K[:, :3, :3]) of the pin-hole intrinsics (image_predictor.py:456): the 3x3 is a STRIDED slice of the
+//     (N,4,4) tensor, so ATen copies it column-major and factors K itself, not its transpose.  K is upper triangular:
+//     L = I, U = K, no interchange whatever the values, and getrs 'N' is a back substitution that DIVIDES by the
+//     diagonal: 1 / f on it, (0 - c) / f above it (3060 of 3060 random and pyramid cameras, fx != fy, c of either sign
+//     or zero, batches of 1, 2 and 96).  Before g12 this read -(c * (1 / f)): the same number for the isotropic,
+//     centred cameras of g11, another one for a quarter of all other (c, f);
 //   * (N,3,3) @ (N,3,3) = ATen's small-matrix bmm: acc = 0, acc += a[i][k] * b[k][j] for k = 0, 1, 2, every operation rounded.
 // (stereo/image_predictor.py:446-459, multi_view_stereonet.py:167-194; the idepth samples keep their own path above.)
 namespace ref32 {
@@ -168,15 +196,13 @@ __device__ inline void inverse3(const float *M, float *X) {
   }
 }
 
-// true when K3 has the reference's form [[fx,0,cx],[0,fy,cy],[0,0,1]] (anything else keeps the fp64 path)
-__device__ inline bool inverse_intrinsics(const float *K3, float *Ki) {
+// K3 of the reference's form [[fx,0,cx],[0,fy,cy],[0,0,1]] (pinhole_form above)
+__device__ inline void inverse_intrinsics(const float *K3, float *Ki) {
 #pragma clang fp contract(off)
-  if (!(K3[1] == 0.f && K3[3] == 0.f && K3[6] == 0.f && K3[7] == 0.f && K3[8] == 1.f && K3[0] != 0.f && K3[4] != 0.f)) return false;
   for (int i = 0; i < 9; ++i) Ki[i] = 0.f;
   Ki[0] = 1.0f / K3[0], Ki[4] = 1.0f / K3[4], Ki[8] = 1.0f;
-  Ki[2] = -(K3[2] * Ki[0]);
-  Ki[5] = -(K3[5] * Ki[4]);
-  return true;
+  Ki[2] = (0.0f - K3[2]) / K3[0];
+  Ki[5] = (0.0f - K3[5]) / K3[4];
 }
 
 __device__ inline void mm3(const float *a, const float *b, float *o) {
@@ -259,9 +285,6 @@ __device__ inline float max_idepth_pixel(const MaxIdepth &g, float x, float y) {
 
 }  // namespace ref32
 
-constexpr int SETUP_THREADS = 256;
-constexpr int SETUP_MAX_PIXELS = 8192;   // level-4 pixels the reference-order sample path holds in LDS (else: the double path)
-
 // Where a chain's pose and intrinsics live: per chain (T (N,4,4), K (N,4,4)) or, `per_source`, as the forward holds
 // them -- one (B,4,4) pose tensor per source view and the B reference images' intrinsics shared by their S chains
 // (chain n = s * B + b): no cat / repeat in front of the launch.
@@ -285,7 +308,7 @@ __global__ __launch_bounds__(SETUP_THREADS) void plane_sweep_setup_kernel(
   __shared__ int s_cnt[SETUP_THREADS];
   __shared__ float s_top;
   __shared__ float s_Tl[16], s_K4i[9], s_K0i[9];   // ref32: the inverted (normalised) pose, the intrinsics' inverses
-  __shared__ int s_ref32;                // ... and whether the intrinsics have the form that path covers
+  __shared__ int s_ref32, s_path;        // ... and whether the intrinsics have the form that path covers (setup_path)
   __shared__ ref32::MaxIdepth s_g;       // ref32 sample path: K R K^-1, K t, D - 1
   __shared__ float s_m[SETUP_MAX_PIXELS];   // ... its per-pixel idepths, summed in torch's order below
   __shared__ float s_lane[32];
@@ -321,10 +344,13 @@ __global__ __launch_bounds__(SETUP_THREADS) void plane_sweep_setup_kernel(
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) K0f[i * 3 + j] = K0[i * 4 + j], K4f[i * 3 + j] = K4[i * 4 + j];
     ref32::inverse_pose(Tn, s_Tl);
-    const bool ok = ref32::inverse_intrinsics(K0f, s_K0i) && ref32::inverse_intrinsics(K4f, s_K4i) && !MVSN_SETUP_FP64_H;
+    s_path = setup_path(K0, K4, rows4, cols4);
+    const bool ok = (s_path & MVSN_PATH_H) != 0;
     s_ref32 = ok ? 1 : 0;
     if (ok) {
 #pragma clang fp contract(off)
+      ref32::inverse_intrinsics(K0f, s_K0i);
+      ref32::inverse_intrinsics(K4f, s_K4i);
       // disparity_to_idepth's own matrices: inverse(K) of the 4x4, K R K^-1 and (K T_left_in_right)[:3, 3] by ATen's
       // naive small products (image_predictor.py:148-160)
       float K4x4[16], Kinv[16], Kinv3[9], Tl3[9], tmp3[9];
@@ -347,7 +373,7 @@ __global__ __launch_bounds__(SETUP_THREADS) void plane_sweep_setup_kernel(
     }
   }
   __syncthreads();
-  const bool ref_samples = s_ref32 && P >= 8 && P <= SETUP_MAX_PIXELS;   // (rows shorter than one vector: another ATen sum)
+  const bool ref_samples = (s_path & MVSN_PATH_SAMPLES) != 0;   // (rows shorter than one vector: another ATen sum)
 
   // --- maximum idepth: mean over pixels of the idepth that yields D-1 px of disparity ----------
   // (stereo/image_predictor.py:148-207)
@@ -536,4 +562,10 @@ extern "C" int mvsn_plane_sweep_setup_sources(const float *const *T_right_in_lef
                      (const void *)src.T[2], (const void *)src.T[3], (const void *)src.T[4], (const void *)src.T[5],
                      (const void *)src.T[6], (const void *)src.T[7], (const void *)nullptr, (const void *)nullptr);
   return mvsn::check_launch("mvsn_plane_sweep_setup_sources");
+}
+
+// Host only: setup_path, the predicate the kernel itself evaluates per chain
+extern "C" int mvsn_plane_sweep_setup_path(const float *K_lvl0_host, const float *K_lvl4_host, int rows4, int cols4) {
+  if (!K_lvl0_host || !K_lvl4_host || rows4 <= 0 || cols4 <= 0) return 0;
+  return mvsn::setup_path(K_lvl0_host, K_lvl4_host, rows4, cols4);
 }

@@ -85,6 +85,27 @@ def make_batch(rows: int, cols: int, num_sources: int, batch: int = 1, seed: int
             "right_filename": [["synthetic"] * batch for _ in range(num_sources)]}
 
 
+def with_camera(batch: Dict[str, object], fy_scale=1.0, dcx=0.0, dcy=0.0, fx=None, fy=None, cx=None, cy=None):
+    """The same batch seen through another pin-hole camera: K (B,1,4,4) is changed IN PLACE (and the batch returned), in
+    fp32, before any unpacker sees it.  `fx` / `fy` / `cx` / `cy` set an entry outright; then fy = fy_scale * fx replaces
+    fy (fy_scale != 1) and the principal point moves by (dcx, dcy).  Every argument is a number for the whole batch or a
+    sequence with one value per batch element (a different camera per element)."""
+    K = batch["K"]
+    B = K.shape[0]
+
+    def per_element(v):
+        return torch.as_tensor(v, dtype=torch.float32).expand(B) if v is not None else None
+
+    for (i, j), v in (((0, 0), fx), ((1, 1), fy), ((0, 2), cx), ((1, 2), cy)):
+        if v is not None:
+            K[:, 0, i, j] = per_element(v)
+    scale = per_element(fy_scale)
+    K[:, 0, 1, 1] = torch.where(scale != 1.0, K[:, 0, 0, 0] * scale, K[:, 0, 1, 1])
+    K[:, 0, 0, 2] += per_element(dcx)
+    K[:, 0, 1, 2] += per_element(dcy)
+    return batch
+
+
 # ---- an analytic scene with exact depth, for the depth-map fusion (fusion.py) ----------------------------------------
 # A slanted plane n.X = h behind a sphere, seen by cameras on an arc about the y axis that all look at a pivot point.
 # Depth is ray-cast exactly (fp64), so a fusion can be checked against the true surface.
@@ -160,11 +181,12 @@ def fusion_scene_surface_distance(points: torch.Tensor) -> torch.Tensor:
     return torch.minimum(((p * n).sum(-1) - h).abs(), ((p - s0).norm(dim=-1) - SCENE_SPHERE_RADIUS).abs())
 
 
-def fusion_scene(views: int, rows: int, cols: int, arc: float = 0.3, device="cpu") -> Dict[str, torch.Tensor]:
+def fusion_scene(views: int, rows: int, cols: int, arc: float = 0.3, device="cpu", K=None) -> Dict[str, torch.Tensor]:
     """Posed frames of the analytic scene: depth (V,1,H,W) fp32, label (V,1,H,W) int8, images (V,3,H,W) fp32 in [-1,1]
     (a texture fixed to the surfaces), K and T_cam_in_world (V,4,4) fp32 (the depth is ray-cast with these fp32
-    cameras)."""
-    K = fusion_scene_intrinsics(views, rows, cols).to(torch.float32)
+    cameras).  `K` (V,4,4): the views' own intrinsics instead of fusion_scene_intrinsics (fx != fy, off-centre, a
+    camera per view)."""
+    K = (fusion_scene_intrinsics(views, rows, cols) if K is None else K.cpu()).to(torch.float32)
     T = fusion_scene_poses(views, arc).to(torch.float32)
     ys, xs = torch.meshgrid(torch.arange(rows, dtype=torch.float64, device=device),
                             torch.arange(cols, dtype=torch.float64, device=device), indexing="ij")

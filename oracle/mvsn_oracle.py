@@ -134,12 +134,32 @@ def idepth_samples(T_right_in_left: torch.Tensor, K: torch.Tensor, rows: int, co
 # --------------------------------------------------------------------------------------
 # a4: homographies
 # --------------------------------------------------------------------------------------
+def inv_intrinsics(K3: torch.Tensor) -> torch.Tensor:
+    """`torch.inverse(K[:, :3, :3])` (stereo/image_predictor.py:456) with the rounding of the host the reference was
+    captured on (tests/golden/g11, g12): the strided 3x3 slice is factored as it stands -- upper triangular, so L = I,
+    U = K -- and back-substituted with a DIVISION by the diagonal: 1 / f, (0 - c) / f.  Written in elementwise ops, which
+    round alike on every host; MKL's small solve does not (on an AMD EPYC host it multiplies by the reciprocal instead:
+    -(c * (1 / f)), 2000 of 2000 random cameras, which is another number for a quarter of all (c, f) though the same one
+    for every isotropic, centred camera of synthetic.make_batch -- so there this oracle was not the reference for cameras
+    with fx != fy or off-centre principal points).  Equal to torch.linalg.inv bit for bit on the capture's host
+    (tests/test_reference_geometry_cpu.py).  A K of any other form: torch.linalg.inv."""
+    pinhole = ((K3[:, 0, 1] == 0) & (K3[:, 1, 0] == 0) & (K3[:, 2, 0] == 0) & (K3[:, 2, 1] == 0) & (K3[:, 2, 2] == 1)
+               & (K3[:, 0, 0] != 0) & (K3[:, 1, 1] != 0))
+    if not bool(pinhole.all()):
+        return torch.linalg.inv(K3)
+    out = torch.zeros_like(K3, memory_format=torch.contiguous_format)
+    one, zero = torch.ones_like(K3[:, 0, 0]), torch.zeros_like(K3[:, 0, 0])
+    out[:, 0, 0], out[:, 1, 1], out[:, 2, 2] = one / K3[:, 0, 0], one / K3[:, 1, 1], one
+    out[:, 0, 2], out[:, 1, 2] = (zero - K3[:, 0, 2]) / K3[:, 0, 0], (zero - K3[:, 1, 2]) / K3[:, 1, 1]
+    return out
+
+
 def plane_sweep_homographies(T_right_in_left: torch.Tensor, K: torch.Tensor,
                              idepths: torch.Tensor) -> torch.Tensor:
     """H[b,d] = K (R + t*idepth[b,d] e3^T) K^-1, (R,t) = inverse(T_right_in_left). (B,n,3,3)."""
     T_lr = torch.linalg.inv(T_right_in_left)
     K3 = K[:, :3, :3]
-    K3inv = torch.linalg.inv(K3)
+    K3inv = inv_intrinsics(K3)
     R = T_lr[:, :3, :3]
     t = T_lr[:, :3, 3]
     B, n = idepths.shape

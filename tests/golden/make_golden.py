@@ -25,6 +25,7 @@ Fixtures:
   gc3_gta_512x256_d64_s5.npz    BASELINE config 3 (five source views): outputs only
   gc5_gta_1024x512_d128_s4.npz  BASELINE config 5 geometry (fp32 reference): idepth_0 (fp32), idepth_4, mask_4
   g11_incremental_homographies.npz  every homography the reference hands its warper during a forward (H0, H family, H_inc)
+  g12_camera_forms.npz          the same capture through cameras with fx != fy, off-centre principal points, ragged pyramids
 
     python tests/golden/make_golden.py [name-prefix ...]     # e.g. "gc" regenerates only the gc* fixtures
 """
@@ -383,15 +384,34 @@ INC_CASES = [  # (tag, rows, cols, D, S, B, seed, jitter): the golden forwards' 
     ("b2_jitter", 80, 96, 8, 2, 2, 2, 0.3), ("b2_wide_jitter", 256, 512, 64, 2, 2, 40, 0.5)]
 
 
-def incremental_homography_pins(name):
+# The same capture through cameras real calibrations have (g12): (..., camera) with camera = the keyword arguments of
+# synthetic.with_camera, applied to the batch BEFORE the reference's unpacker runs.  None = make_batch's own camera.
+ANISO, OFFC = {"fy_scale": 1.137}, {"dcx": 13.25, "dcy": -7.6}
+BOTH = {**ANISO, **OFFC}
+CAMERA_CASES = [
+    ("fy_only", 256, 512, 64, 2, 1, 7, 0.0, ANISO), ("offcentre_only", 256, 512, 64, 2, 1, 7, 0.0, OFFC),
+    ("fy_and_offcentre", 256, 512, 64, 2, 1, 7, 0.0, BOTH),
+    ("b2_fy_below_fx", 192, 320, 16, 2, 2, 31, 0.3, {"fy_scale": (0.83, 0.91), "dcx": (13.25, -9.5), "dcy": (-7.6, 4.75)}),
+    ("ragged_131x277", 131, 277, 24, 2, 1, 5, 0.3, None), ("ragged_131x277_cam", 131, 277, 24, 2, 1, 5, 0.3, BOTH),
+    ("ragged_250x500", 250, 500, 32, 3, 1, 11, 0.3, None), ("ragged_250x500_cam", 250, 500, 32, 3, 1, 11, 0.3, BOTH),
+    ("ragged_60x90", 60, 90, 8, 2, 1, 17, 0.3, None), ("ragged_60x90_cam", 60, 90, 8, 2, 1, 17, 0.3, BOTH),
+    ("demon_like", 480, 640, 96, 1, 1, 9, 0.0, {"fx": 0.89115971 * 640, "fy": 1.18821287 * 480}),
+    ("half_pixel", 128, 256, 16, 2, 1, 19, 0.0, {"cx": 256 / 2 - 0.5 - 0.5, "cy": 128 / 2 - 0.5 - 0.5})]
+
+
+def incremental_homography_pins(name, cases=INC_CASES):
     """Every homography the reference's PlaneSweepWarper is HANDED during a forward (multi_view_stereonet.py:254-283):
     call 0 of a source = the level-0 plane-0 matrix, call 1 = the level-4 family, calls 2.. = the incremental
     `inverse(H[d-1]) @ H[d]` of every step -- captured by a pre-hook on the warper, so the values are the reference's own
     (its tensor layouts, hence its ATen paths, included).  Inputs are regenerated from the seeds by the tests."""
     net = ref_net("gta_sfm_150epochs")
     d = {}
-    for tag, rows, cols, D, S, B, seed, jitter in INC_CASES:
+    for tag, rows, cols, D, S, B, seed, jitter, *camera in cases:
         batch = synthetic.make_batch(rows, cols, S, batch=B, seed=seed, pose_jitter=jitter)
+        if camera:          # g12: the K the reference is given, and the pyramid its unpacker makes of it, are stored
+            if camera[0] is not None:
+                synthetic.with_camera(batch, **camera[0])
+            d[f"{tag}_K"] = npy(batch["K"])                                     # (B,1,4,4)
         seen = []
         hook = net.right_feature_extractor.warper.register_forward_pre_hook(lambda m, i: seen.append(i[1].clone()))
         spy = {}
@@ -418,6 +438,8 @@ def incremental_homography_pins(name):
             # multi_view_stereonet_utils.py:597-604): torch's reduction there rounds differently from host to host, so
             # the tests take it from here instead of re-deriving it on whatever host they run on
             d[f"{tag}_T_{s}"] = npy(inputs["T_right_in_left"][s])               # (B,4,4)
+        if camera:
+            d[f"{tag}_Kpyr"] = npy(torch.stack(inputs["K_pyr"]))                # (5,B,4,4)
         d[f"{tag}_meta"] = np.array([rows, cols, D, S, B, seed, int(round(jitter * 100))], np.int64)
     np.savez_compressed(os.path.join(HERE, name), **d)
     print(name, "ok")
@@ -443,6 +465,7 @@ def main():
         ("gc5_gta_1024x512_d128_s4.npz", lambda n: outputs_only(n, G, 512, 1024, 128, 4, seed=25, slim=True)),
         ("g9_two_view_consistency.npz", lambda n: consistency_pins(n)),
         ("g11_incremental_homographies.npz", lambda n: incremental_homography_pins(n)),
+        ("g12_camera_forms.npz", lambda n: incremental_homography_pins(n, CAMERA_CASES)),
     ]
     want = sys.argv[1:]
     for name, job in jobs:

@@ -41,6 +41,34 @@ def test_parameter_shapes_examples():
     assert "left_feature_extractor.conv0.bias" not in ps and "left_feature_extractor.conv_final.bias" in ps
 
 
+def test_plane_sweep_setup_path_reports_the_kernels_own_predicate():
+    """mvsn_plane_sweep_setup_path (host only): 3 = homographies and idepth samples in the reference's fp32 order for every
+    pin-hole K -- fx != fy, principal point anywhere -- on a level-4 grid of 8 .. 8192 pixels; 1 outside that range (the
+    samples from the fp64 evaluation); 0 for a K off the form [[fx,0,cx],[0,fy,cy],[0,0,1]] at either level."""
+    import torch
+    from multi_view_stereonet_amd import synthetic
+    from multi_view_stereonet_amd import multi_view_stereonet_utils as snu
+    batch = synthetic.with_camera(synthetic.make_batch(131, 277, 1, batch=2, seed=1), fy_scale=(1.137, 0.83), dcx=13.25, dcy=-7.6)
+    K = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)["K_pyr"]
+    K0, K4 = K[0], K[4]
+    path = _native.plane_sweep_setup_path
+    assert path(K0, K4, 9, 18) == [3, 3]
+    assert path(K0, K4, 2, 4) == [3, 3] and path(K0, K4, 64, 128) == [3, 3]                    # 8 and 8192 pixels
+    assert path(K0, K4, 1, 7) == [1, 1] and path(K0, K4, 1, 8193) == [1, 1] and path(K0, K4, 96, 100) == [1, 1]
+    assert path(K0, K4, 0, 18) == [0, 0]
+    for lvl in (0, 4):
+        for (i, j), v in (((0, 1), 0.3), ((1, 0), 1e-6), ((2, 0), 1e-3), ((2, 1), -1e-3), ((2, 2), 0.5), ((0, 0), 0.0),
+                          ((1, 1), 0.0), ((0, 1), float("nan"))):
+            Ks = [K0.clone(), K4.clone()]
+            Ks[lvl // 4][1, i, j] = v
+            assert path(Ks[0], Ks[1], 9, 18) == [3, 0], (lvl, i, j, v)
+    zero_centre = K0.clone()
+    zero_centre[:, 0, 2] = 0.0
+    zero_centre[:, 1, 2] = -4.5
+    assert path(zero_centre, K4, 9, 18) == [3, 3]
+    assert _native.load().mvsn_plane_sweep_setup_path(None, None, 9, 18) == 0
+
+
 def test_library_exports_every_declared_symbol():
     header = open(os.path.join(ROOT, "include", "mvsn_hip.h")).read()
     declared = set(re.findall(r"\b(mvsn_[a-z0-9_]+)\s*\(", header))

@@ -62,6 +62,31 @@ def test_fusion_matches_the_restatement_on_the_analytic_scene():
     assert _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3) > 0.8 * 6 * 96 * 128
 
 
+def anisotropic_scene(V=6, H=90, W=150, device="cpu"):
+    """The analytic scene through cameras real calibrations have: fy = 1.137 fx (0.83 fx for the odd views), principal
+    points well off the centre and different from view to view, a non-square image -- a kernel that read fx for fy,
+    cx for cy, W for H or one view's K for another's would project to other pixels."""
+    K = synthetic.fusion_scene_intrinsics(V, H, W)
+    for v in range(V):
+        K[v, 1, 1] = K[v, 0, 0] * (1.137 if v % 2 == 0 else 0.83)
+        K[v, 0, 2] += 13.25 - 3.5 * v
+        K[v, 1, 2] += -7.6 + 2.25 * v
+    return synthetic.fusion_scene(V, H, W, device=device, K=K)
+
+
+def test_fusion_with_anisotropic_off_centre_cameras_matches_the_restatement():
+    sc = anisotropic_scene()
+    assert (sc["K"][:, 0, 0] != sc["K"][:, 1, 1]).all() and not torch.equal(sc["K"][0], sc["K"][1])
+    nb = nearest_neighbours(6, 5)
+    ref = fuse_reference(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    got = fuse_depthmaps(sc["depth"].to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb,
+                         images=sc["images"].to(DEV))
+    shared = _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3)
+    print(f"anisotropic fusion: {shared} shared points, {int(ref['margin'].sum())} margin pixels of {ref['margin'].size}, "
+          f"{int((got.count.cpu().numpy() != ref['count']).sum())} counts differ")
+    assert shared > 0.6 * 6 * 90 * 150
+
+
 def test_fusion_odd_size_padding_valid_mask_and_ref_subset():
     V, H, W = 6, 97, 131
     sc = synthetic.fusion_scene(V, H, W)

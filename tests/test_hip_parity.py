@@ -65,8 +65,32 @@ def test_mfma_fragment_mapping():
 def test_plane_sweep_setup(rows, cols, S, B, D, skew):
     """`skew` != 0: intrinsics with a shear term are not of the form the reference-order path (ref32, csrc/mvsn_setup.hip)
     covers -- the kernel's double-precision evaluation, rounded once, must serve them inside the same tolerances."""
+    _plane_sweep_setup_case(rows, cols, S, B, D, skew, None, 0 if skew else 3)
+
+
+# cameras real calibrations have (synthetic.with_camera); a K per batch element where the value is a tuple
+ANISO, OFFCENTRE = {"fy_scale": 1.137}, {"dcx": 13.25, "dcy": -7.6}
+CAMERAS = {"fy": ANISO, "offcentre": OFFCENTRE, "both": {**ANISO, **OFFCENTRE},
+           "per_element": {"fy_scale": (0.83, 1.137, 0.91), "dcx": (13.25, -9.5, 0.0), "dcy": (-7.6, 4.75, 11.0)}}
+
+
+@pytest.mark.parametrize("rows,cols,S,B,D,camera,path", [
+    (256, 512, 2, 2, 64, "fy", 3), (256, 512, 2, 2, 64, "offcentre", 3), (256, 512, 2, 2, 64, "both", 3),
+    (131, 277, 2, 3, 24, "per_element", 3), (60, 90, 2, 3, 8, "per_element", 3), (480, 640, 1, 1, 96, "both", 3),
+    (32, 48, 2, 2, 8, "both", 1),              # a 2 x 3 level-4 grid, under 8 pixels: the samples from the fp64 evaluation
+    (1536, 1600, 1, 1, 16, "both", 1)])        # 96 x 100 = 9600 level-4 pixels, over 8192: likewise
+def test_plane_sweep_setup_through_changed_cameras(rows, cols, S, B, D, camera, path):
+    """test_plane_sweep_setup's checks, tolerances unchanged, through cameras with fx != fy, off-centre principal points
+    and a K per batch element (no shear term), and on level-4 grids outside 8 .. 8192 pixels -- each on the path it means
+    to test (mvsn_plane_sweep_setup_path)."""
+    _plane_sweep_setup_case(rows, cols, S, B, D, 0.0, CAMERAS[camera], path)
+
+
+def _plane_sweep_setup_case(rows, cols, S, B, D, skew, camera, path):
     eng = net_for("gta_sfm_150epochs").engine()
     batch = synthetic.make_batch(rows, cols, S, batch=B, seed=3, pose_jitter=0.3)
+    if camera:
+        synthetic.with_camera(batch, **{k: (v[:B] if isinstance(v, tuple) else v) for k, v in camera.items()})
     inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
     r4, c4 = inp["left_image_pyr"][4].shape[-2:]
     T = torch.cat(inp["T_right_in_left"], 0)
@@ -74,6 +98,7 @@ def test_plane_sweep_setup(rows, cols, S, B, D, skew):
         inp["K_pyr"][lvl] = inp["K_pyr"][lvl].clone()
         inp["K_pyr"][lvl][:, 0, 1] = skew
     K0, K4 = inp["K_pyr"][0].repeat(S, 1, 1), inp["K_pyr"][4].repeat(S, 1, 1)
+    assert _native.plane_sweep_setup_path(K0, K4, r4, c4) == [path] * (S * B)
     samples, H4, Hinc, H0, base = eng.plane_sweep_setup(T.to(DEV), K0.to(DEV), K4.to(DEV), r4, c4, D)
     # oracle: renormalise per source, then the reference pipeline
     Tn = T.clone()
@@ -100,8 +125,29 @@ def test_plane_sweep_setup(rows, cols, S, B, D, skew):
 @pytest.mark.parametrize("rows,cols,S,D,jitter", [(256, 512, 2, 64, 0.0), (512, 1024, 4, 128, 0.3), (480, 640, 1, 96, 0.3),
                                                     (256, 512, 5, 64, 0.5), (64, 128, 1, 16, 0.0)])
 def test_plane_sweep_homographies_follow_the_reference_fp32_chain(rows, cols, S, D, jitter):
+    _fp32_chain_case(rows, cols, S, D, jitter, None)
+
+
+@pytest.mark.parametrize("rows,cols,S,D,jitter,camera", [(256, 512, 2, 64, 0.0, "fy"), (256, 512, 2, 64, 0.0, "offcentre"),
+                                                           (256, 512, 2, 64, 0.0, "both"), (131, 277, 2, 24, 0.3, "per_element"),
+                                                           (480, 640, 1, 96, 0.3, "both"), (250, 500, 2, 32, 0.0, "per_element")])
+def test_plane_sweep_homographies_follow_the_reference_fp32_chain_through_changed_cameras(rows, cols, S, D, jitter, camera):
+    """The same figures and thresholds through cameras with fx != fy and off-centre principal points.  (On the host that
+    captured the fixtures the numpy restatement of the kernel's order equals the oracle on these inputs in every H0 entry,
+    jittered or not, so the 0.93 / 0.6 shares hold with the margin they had.)  Two things about the HOST this runs on:
+    its MKL may round `inverse(K[:, :3, :3])` otherwise than the capture's host did (an AMD EPYC multiplies by the
+    reciprocal where the capture's host divides), which one ulp of K^-1 turns into 3e-5 of an H0 entry through the
+    cancellation in K R K^-1 -- the oracle therefore forms that inverse in elementwise ops (oracle.inv_intrinsics), equal
+    to the capture on any host; and the un-jittered rows keep to two sources, as the un-jittered rows above do: the 0.93
+    share allows for the residues that host's 4x4 inverse leaves in entries that are zero in exact arithmetic, and a
+    third source's larger rotation leaves two per chain -- 300 of 324 entries (0.926) at 250x500 with three sources, with
+    make_batch's own camera exactly as with the changed ones (largest difference 1.9e-9), 216 of 216 with two."""
+    _fp32_chain_case(rows, cols, S, D, jitter, CAMERAS[camera])
+
+
+def _fp32_chain_case(rows, cols, S, D, jitter, camera):
     """Round 6: the homographies the kernels consume (H at levels 0 and 4) are formed by the reference's own fp32 chain --
-    torch's CPU inverse of the pose (MKL's pivoted LU of the transpose + trans solve), the strti2 inverse of the
+    torch's CPU inverse of the pose (MKL's pivoted LU of the transpose + trans solve), the back-substituted inverse of the
     intrinsics, ATen's naive 3x3 products -- instead of an fp64 evaluation rounded once: one ulp of the level-0
     translation entries was the whole forward's deviation from the reference on noise frames (profiles/r06_parity/).
     Against the oracle (the same torch ops as the reference): the entries agree BIT FOR BIT except cancellation residues
@@ -111,10 +157,13 @@ def test_plane_sweep_homographies_follow_the_reference_fp32_chain(rows, cols, S,
     worst = worst4 = 0.0
     for seed in range(6):
         batch = synthetic.make_batch(rows, cols, S, batch=2, seed=40 + seed, pose_jitter=jitter)
+        if camera:
+            synthetic.with_camera(batch, **{k: (v[:2] if isinstance(v, tuple) else v) for k, v in camera.items()})
         inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
         r4, c4 = inp["left_image_pyr"][4].shape[-2:]
         T = torch.cat(inp["T_right_in_left"], 0)
         K0, K4 = inp["K_pyr"][0].repeat(S, 1, 1), inp["K_pyr"][4].repeat(S, 1, 1)
+        assert _native.plane_sweep_setup_path(K0, K4, r4, c4) == [3] * (2 * S)
         samples, H4, _, H0, _ = eng.plane_sweep_setup(T.to(DEV), K0.to(DEV), K4.to(DEV), r4, c4, D)
         Tn = T.clone()
         Tn[:, :3, 3] /= Tn[:, :3, 3].pow(2).sum(1).sqrt()[:, None]
@@ -145,15 +194,34 @@ def test_plane_sweep_setup_reproduces_the_captured_reference_homographies():
     handed its warper during seven forwards (tests/golden/g11_incremental_homographies.npz: level-0 plane-0 H, the level-4
     family, every incremental `inverse(H[d-1]) @ H[d]`; the golden configs, batches of one and two, jittered poses) against
     what `mvsn_plane_sweep_setup` emits for the same inputs -- bit for bit, every chain."""
+    _captured_reference_case("g11_incremental_homographies.npz")
+
+
+def test_plane_sweep_setup_reproduces_the_captured_reference_through_changed_cameras():
+    """The same against tests/golden/g12_camera_forms.npz: twelve forwards of the reference through cameras with fx != fy
+    (above and below), off-centre and half-pixel principal points, a K per batch element, DeMoN-like focal lengths, and
+    pyramids whose level scales differ in x and y, with the fixture's K.  First the DEVICE-side unpacker
+    (mvsn_prepare_cameras) must reproduce the poses and every level of the K pyramid the reference's unpacker made, bit for
+    bit; then the samples and H0 / H4 / H_inc, bit for bit, every chain, on the reference-order path."""
+    _captured_reference_case("g12_camera_forms.npz")
+
+
+def _captured_reference_case(name):
     eng = net_for("gta_sfm_150epochs").engine()
-    fix = load_golden("g11_incremental_homographies.npz")
+    fix = load_golden(name)
     report = []
     for key in sorted(k for k in fix if k.endswith("_meta")):
         tag = key[:-5]
         rows, cols, D, S, B, seed, jit = (int(v) for v in fix[key])
         batch = synthetic.make_batch(rows, cols, S, batch=B, seed=seed, pose_jitter=jit / 100.0)
+        if f"{tag}_K" in fix:
+            batch["K"] = t(fix[f"{tag}_K"]).clone()
         inp = snu.multi_view_unpack_batch(batch, DEV, 5)
         r4, c4 = inp["left_image_pyr"][4].shape[-2:]
+        if f"{tag}_Kpyr" in fix:
+            same = torch.stack(inp["K_pyr"]).cpu().numpy().view(np.int32) == fix[f"{tag}_Kpyr"].view(np.int32)
+            report.append(f"{tag}: K pyramid {int(same.sum())} of {same.size}")
+            assert same.shape == (5, B, 4, 4) and same.all(), (tag, "device-side K pyramid", np.argwhere(~same)[:8])
         # the poses as the reference's unpacker produced them (the fixture's): the host-side normalisation is a torch
         # reduction that rounds differently from host to host; the DEVICE-side unpacker (what the module uses) must give
         # exactly these
@@ -161,6 +229,7 @@ def test_plane_sweep_setup_reproduces_the_captured_reference_homographies():
         T_dev = torch.cat(inp["T_right_in_left"], 0).cpu()
         assert torch.equal(T_dev.view(torch.int32), T.view(torch.int32)), (tag, "device-side unpack", float((T_dev - T).abs().max()))
         K0, K4 = inp["K_pyr"][0].repeat(S, 1, 1), inp["K_pyr"][4].repeat(S, 1, 1)
+        assert _native.plane_sweep_setup_path(K0, K4, r4, c4) == [3] * (S * B), tag
         samples, H4, Hinc, H0, _ = eng.plane_sweep_setup(T.to(DEV), K0.to(DEV), K4.to(DEV), r4, c4, D)
         want = {k: np.concatenate([fix[f"{tag}_{k}_{s}"] for s in range(S)], 0) for k in ("samples", "H4", "Hinc", "H0")}
         got = {"samples": samples.cpu().numpy(), "H4": H4.cpu().numpy(), "Hinc": Hinc.cpu().numpy()[:, 1:],
@@ -2536,6 +2605,108 @@ def test_two_view_bidirectional_golden():
         inputs["T_right_in_left"], inputs["T_left_in_right"], inputs["K_pyr"], out["left_idepthmap_pyr"],
         occ["left_occlusion_mask_pyr"], out["right_idepthmap_pyr"], occ["right_occlusion_mask_pyr"])
     assert loss.is_cuda and loss.dim() == 0    # (NaN when every pixel is occluded, as in the reference)
+
+
+def _project_f64(K, T_right_in_left, idepth):
+    """x' ~ K (R K^-1 [x y 1]^T / idepth + t), (R, t) = inverse(T_right_in_left), in float64 from first principles, with the
+    guards of the operation under test (depth = 1 / (idepth + 1e-6), idepth' = 1 / (z' + 1e-6), a divisor of z' + 1e-7;
+    stereo/image_predictor.py:538-576): normalised right-image coordinate (B,rows,cols,2), idepth' (B,1,rows,cols), and the
+    out-of-image mask |n| > 1."""
+    K, T, idp = K.cpu().double(), T_right_in_left.cpu().double(), idepth.cpu().double()
+    B, _, rows, cols = idp.shape
+    Tl, Ki = torch.linalg.inv(T), torch.linalg.inv(K[:, :3, :3])
+    ys, xs = torch.meshgrid(torch.arange(rows, dtype=torch.float64), torch.arange(cols, dtype=torch.float64), indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(rows * cols, dtype=torch.float64)], 0)
+    X = (Ki @ pix) / (idp.reshape(B, 1, -1) + 1e-6)
+    Xr = Tl[:, :3, :3] @ X + Tl[:, :3, 3:4]
+    id_prime = (1.0 / (Xr[:, 2] + 1e-6)).view(B, 1, rows, cols)
+    cam = K[:, :3, :3] @ Xr
+    u, v = cam[:, 0] / (cam[:, 2] + 1e-7), cam[:, 1] / (cam[:, 2] + 1e-7)
+    uv = torch.stack([(u + 0.5) * 2.0 / cols - 1.0, (v + 0.5) * 2.0 / rows - 1.0], -1).view(B, rows, cols, 2)
+    return uv, id_prime, ((uv[..., 0].abs() > 1.0) | (uv[..., 1].abs() > 1.0)).unsqueeze(1)
+
+
+@pytest.mark.parametrize("rows,cols", [(131, 277), (96, 200)])
+def test_two_view_projection_and_occlusion_through_changed_cameras(rows, cols):
+    """mvsn_idepth_reproject / mvsn_occlusion_mask with fx != fy (above fx for one batch element, below for the other),
+    off-centre principal points and, at 131x277, level scales that differ in x and y -- every pyramid level: `uv`,
+    `idepth_in_other` and `invalid` against a float64 evaluation written here (the projector tolerances of
+    test_two_view_consistency_ops_golden; the reference's own fp32 ops sit at 0.13 / 0.02 of them on these inputs), the
+    occlusion mask against the oracle (the share of test_two_view_bidirectional_golden).  A pixel whose flag differs must
+    sit on its predicate, in float64: |n| within 16 ulps of 1 (as test_homography_warp), or `sampled - idepth'` within
+    what those same tolerances let either side move it of the image's mean |difference| (idepth' by its rtol / atol; the
+    sample by the uv tolerance, measured on the map itself; the mean by the mean of both)."""
+    from multi_view_stereonet_amd import losses
+    mv = synthetic.with_camera(synthetic.make_batch(rows, cols, 1, batch=2, seed=13, pose_jitter=0.2),
+                               fy_scale=(1.137, 0.83), dcx=(13.25, -9.5), dcy=(-7.6, 4.75))
+    inp = snu.multi_view_unpack_batch(mv, torch.device("cpu"), 5)
+    T = inp["T_right_in_left"][0]
+    gen = torch.Generator().manual_seed(99)
+    sample = lambda img, at: F.grid_sample(img.double(), at, mode="bilinear", padding_mode="border", align_corners=False)  # noqa: E731
+    for lvl in range(5):
+        r, c = inp["left_image_pyr"][lvl].shape[-2:]
+        K = inp["K_pyr"][lvl]
+        assert K[0, 0, 0] != K[0, 1, 1] and not torch.equal(K[0], K[1])
+        L = 0.06 + 0.04 * synthetic._smooth_image(gen, 2, r, c)[:, :1]       # (the maps of g9: sensible at unit baseline)
+        R = 0.06 + 0.04 * synthetic._smooth_image(gen, 2, r, c)[:, :1]
+        R[:, :, : r // 3] += 0.05                                            # a nearer band: real occlusions
+        uv, idp, inv = losses.idepthmap_projector(K.to(DEV), T.to(DEV), L.to(DEV))
+        uv64, idp64, inv64 = _project_f64(K, T, L)
+        e_uv = float(((uv.cpu().double() - uv64).abs() / (2e-6 + 1e-5 * uv64.abs())).max())
+        e_id = float(((idp.cpu().double() - idp64).abs() / (1e-7 + 1e-5 * idp64.abs())).max())
+        edge = torch.minimum((uv64[..., 0].abs() - 1.0).abs(), (uv64[..., 1].abs() - 1.0).abs()).unsqueeze(1)
+        inv_diff = inv.cpu() != inv64
+        occ = losses.get_occlusion_mask(K.to(DEV), T.to(DEV), L.to(DEV), None, R.to(DEV), None).cpu()
+        ref = oracle.get_occlusion_mask(K, T, L, R)
+        occ_diff = occ != ref
+        print(f"{rows}x{cols} level {lvl} ({r}x{c}): uv / idepth' error over tolerance {e_uv:.3f} / {e_id:.3f}; invalid flags "
+              f"differing {int(inv_diff.sum())}, occlusion flags differing {int(occ_diff.sum())} of {ref.numel()} "
+              f"({float(ref.double().mean()):.3f} set, {float(inv64.double().mean()):.3f} out of the image)")
+        close(uv, uv64, rtol=1e-5, atol=2e-6)
+        close(idp, idp64, rtol=1e-5, atol=1e-7)
+        assert int(inv_diff.sum()) <= 1 and bool((edge[inv_diff] < 16 * 2.0 ** -23).all())
+        assert occ.dtype == torch.bool and int(occ_diff.sum()) <= max(2, ref.numel() // 2000)
+        if occ_diff.any():
+            at = sample(R, uv64)
+            id_diff = at - idp64
+            thr = id_diff.view(2, -1).abs().mean(1).view(2, 1, 1, 1)
+            duv = 2e-6 + 1e-5 * uv64.abs()
+            slack = 1e-7 + 1e-5 * idp64.abs()
+            for axis in (0, 1):
+                step = torch.zeros_like(uv64)
+                step[..., axis] = duv[..., axis]
+                slack = slack + torch.maximum((sample(R, uv64 + step) - at).abs(), (sample(R, uv64 - step) - at).abs())
+            bound = slack + slack.view(2, -1).mean(1).view(2, 1, 1, 1) + 1e-6 * thr
+            on_predicate = ((id_diff - thr).abs() <= bound) | (edge < 16 * 2.0 ** -23)
+            assert bool(on_predicate[occ_diff].all()), ((id_diff - thr).abs()[occ_diff], bound[occ_diff], edge[occ_diff])
+
+
+@pytest.mark.parametrize("rows,cols,D", [(131, 277, 8), (256, 512, 16)])
+def test_forward_through_two_different_cameras_vs_oracle(rows, cols, D):
+    """End to end through cameras real calibrations have: a batch of two with a DIFFERENT K per element (fy = 1.137 fx
+    and 0.83 fx, principal points 13.25 / -7.6 and -9.5 / 4.75 px off the centre), two sources, jittered poses; 131x277
+    adds a pyramid whose levels are scaled differently in x and y.  Unpacked on the device (mvsn_prepare_cameras) and on
+    the host for the oracle; every level at the file's budgets, the final map under the contract."""
+    wname = "gta_sfm_150epochs"
+    batch = synthetic.with_camera(synthetic.make_batch(rows, cols, 2, batch=2, seed=rows + cols, pose_jitter=0.2, smooth=True),
+                                  fy_scale=(1.137, 0.83), dcx=(13.25, -9.5), dcy=(-7.6, 4.75))
+    inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
+    ref = oracle.forward(load_weights(wname), inp["left_image_pyr"], inp["K_pyr"], inp["T_right_in_left"],
+                         inp["right_image_pyr"], D)
+    dev_in = snu.multi_view_unpack_batch(batch, torch.device(DEV), 5)
+    for a, b in zip(dev_in["K_pyr"], inp["K_pyr"]):
+        assert torch.equal(a.cpu(), b)
+    out = snu.multi_view_forward(net_for(wname), dev_in, {"num_idepth_samples": D, "cost_volume_filter": True,
+                                                          "refiners": [True] * 5})
+    figures = []
+    for lvl in range(5):
+        got = out["left_idepthmap_pyr"][lvl].cpu()
+        assert got.shape == ref["left_idepthmap_pyr"][lvl].shape
+        figures.append((lvl,) + tuple(rel_err(got, ref["left_idepthmap_pyr"][lvl])))
+    print(f"{rows}x{cols} D {D}, two cameras: " + "; ".join(f"level {l} mean-rel {m:.2e} max-rel {x:.2e}" for l, m, x in figures))
+    for lvl, mean_rel, max_rel in figures:
+        assert mean_rel < 2e-4 and max_rel < 1e-3, (lvl, mean_rel, max_rel)
+    assert_contract(out["left_idepthmap_pyr"][0].cpu(), ref["left_idepthmap_pyr"][0], f"{rows}x{cols} two cameras")
 
 
 def test_torchscript_archive_matches_eager(tmp_path):

@@ -3,9 +3,10 @@ that generated the fixtures: the operation order of torch's CPU `inverse` of a p
 its small matrix products, of `matmul(KRKinv, xyz_pix)` and of `torch.sum` (stereo/image_predictor.py:120-209, 400-461,
 multi_view_stereonet.py:131-194, 279-282).  A plain numpy restatement of those orders -- the same one the kernel implements --
 reproduces torch bit for bit (random matrices, poses, homographies), the oracle's idepth samples and homographies, and the capture
-of what the reference hands its warper (tests/golden/g11_incremental_homographies.npz).  If a future torch / MKL changes an order,
+of what the reference hands its warper (tests/golden/g11_incremental_homographies.npz; g12_camera_forms.npz: the same through
+cameras with fx != fy, off-centre principal points and ragged pyramids).  If a future torch / MKL changes an order,
 these tests say so (the kernel would then merely be one more correctly-behaved fp32 evaluation, a few ulps from the reference's, as
-it was before round 6); the g11 comparisons are data against data and do not depend on the host."""
+it was before round 6); the g11 / g12 comparisons are data against data and do not depend on the host."""
 import numpy as np
 import torch
 
@@ -105,10 +106,14 @@ def inverse3(M):
 
 
 def inverse_intrinsics(K):
-    """LAPACK strti2 on [[fx,0,cx],[0,fy,cy],[0,0,1]]: reciprocal diagonal, -(c * (1 / f)) above it."""
+    """`torch.inverse(K[:, :3, :3])` of [[fx,0,cx],[0,fy,cy],[0,0,1]] (stereo/image_predictor.py:456).  The 3x3 is a STRIDED slice
+    of the (N,4,4) intrinsics, so ATen copies it column-major and factors K itself, not its transpose: K is upper triangular, the
+    LU is L = I, U = K without an interchange whatever the values, and sgetrs 'N' is a back substitution that DIVIDES by the
+    diagonal: 1 / f on it, (0 - c) / f above it (c = 0 gives +0).  Until g12 this read -(c * (1 / f)), which is the same number
+    for every isotropic, centred camera the suite had (c = (n - 1) / 2, f = 0.8 cols) and another for a quarter of all others."""
     o = np.zeros((3, 3), f32)
     o[0, 0], o[1, 1], o[2, 2] = f32(1) / K[0, 0], f32(1) / K[1, 1], 1
-    o[0, 2], o[1, 2] = -f32(K[0, 2] * o[0, 0]), -f32(K[1, 2] * o[1, 1])
+    o[0, 2], o[1, 2] = f32(f32(0) - K[0, 2]) / K[0, 0], f32(f32(0) - K[1, 2]) / K[1, 1]
     return o
 
 
@@ -124,10 +129,23 @@ def mm3(a, b):
     return o
 
 
-def poses(jitter):
-    for seed in range(24):
+ANISO, OFFCENTRE = {"fy_scale": 1.137}, {"dcx": 13.25, "dcy": -7.6}
+CAMERAS = (ANISO, OFFCENTRE, {**ANISO, **OFFCENTRE}, {"fy_scale": 0.83, "dcx": -21.5, "dcy": 9.125})
+RAGGED = ((131, 277), (250, 500), (60, 90))       # pyramids whose level scales differ in x and y
+
+
+def poses(jitter, cameras=False):
+    """Normalised poses and K pyramids of the synthetic batches; `cameras`: the same through cameras with fx != fy and
+    off-centre principal points (all three changes) at the headline size, and through all of them at the ragged sizes."""
+    forms = [(256, 512, None)] * 24
+    if cameras:
+        forms = [(256, 512, CAMERAS[n % 4]) for n in range(12)] + [RAGGED[n % 3] + (CAMERAS[n % 4],) for n in range(12)]
+        forms += [size + (None,) for size in RAGGED]
+    for seed, (rows, cols, camera) in enumerate(forms):
         S = (1, 2, 4)[seed % 3]
-        batch = synthetic.make_batch(256, 512, S, batch=1, seed=300 + seed, pose_jitter=jitter)
+        batch = synthetic.make_batch(rows, cols, S, batch=1, seed=300 + seed, pose_jitter=jitter)
+        if camera:
+            synthetic.with_camera(batch, **camera)
         inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
         for Tt in inp["T_right_in_left"]:
             T = Tt.clone()
@@ -164,10 +182,41 @@ def test_inverse_of_the_pose_matches_torch_bit_for_bit():
     assert wrong == 0, (wrong, total)
 
 
+def test_intrinsics_inverse_matches_torch_bit_for_bit_for_any_pinhole_camera():
+    """`inverse_intrinsics` against `torch.linalg.inv(K[:, :3, :3])` (the strided slice the reference inverts): random fx != fy and
+    principal points of either sign or zero, batches of 1, 2 and 96 (the reference inverts D * B copies at once), and every
+    pyramid level of the ragged sizes through every changed camera."""
+    rng = np.random.default_rng(12)
+    total = same = 0
+    for n in range(3000):
+        B = (1, 2, 96)[n % 3]
+        K = torch.eye(4).repeat(B, 1, 1)
+        K[:, 0, 0] = float(rng.uniform(0.5, 5000.0))
+        K[:, 1, 1] = K[:, 0, 0] * (float(rng.uniform(0.5, 2.0)) if n % 4 else 1.0)
+        K[:, 0, 2] = 0.0 if n % 50 == 0 else float(rng.uniform(-3000.0, 3000.0))
+        K[:, 1, 2] = 0.0 if n % 70 == 0 else float(rng.uniform(-3000.0, 3000.0))
+        want = torch.linalg.inv(K[:, :3, :3])[B - 1].numpy()
+        assert np.array_equal(oracle.inv_intrinsics(K[:, :3, :3])[B - 1].numpy().view(np.int32), want.view(np.int32))
+        total += 1
+        same += int(np.array_equal(inverse_intrinsics(K[B - 1, :3, :3].numpy()).view(np.int32), want.view(np.int32)))
+    for rows, cols in RAGGED:
+        for camera in CAMERAS:
+            batch = synthetic.with_camera(synthetic.make_batch(rows, cols, 1, batch=2, seed=1), **camera)
+            K_pyr = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)["K_pyr"]
+            sizes = [tuple(im.shape[-2:]) for im in snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)["left_image_pyr"]]
+            assert any(r * cols != c * rows for r, c in sizes), sizes      # some level is scaled differently in x and y
+            for K in K_pyr:
+                want = torch.linalg.inv(K[:, :3, :3])[1].numpy()
+                total += 1
+                same += int(np.array_equal(inverse_intrinsics(K[1, :3, :3].numpy()).view(np.int32), want.view(np.int32)))
+    print(f"intrinsics inverses equal bit for bit: {same} of {total}")
+    assert same == total and total >= 3060
+
+
 def test_intrinsics_inverse_and_homographies_match_the_oracle():
     total = exact = 0
-    for jitter in (0.0, 0.5):
-        for T, K_pyr in poses(jitter):
+    for jitter, cameras in ((0.0, False), (0.5, False), (0.0, True), (0.3, True)):
+        for T, K_pyr in poses(jitter, cameras):
             Tl = inverse_pose(T[0].numpy())
             for lvl in (0, 4):
                 K = K_pyr[lvl]
@@ -177,9 +226,7 @@ def test_intrinsics_inverse_and_homographies_match_the_oracle():
                 idepths = torch.tensor([[0.0, 0.37, 1.9]])
                 want = oracle.plane_sweep_homographies(T, K, idepths)[0].numpy()
                 for d, idp in enumerate(idepths[0].numpy()):
-                    core = Tl[:3, :3].copy()
-                    core[:, 2] = (core[:, 2] + (Tl[:3, 3] * f32(idp)).astype(f32)).astype(f32)
-                    H = mm3(K3, mm3(core, Ki))
+                    H = restated_homography(K3, Ki, Tl, idp)
                     total += 9
                     exact += int((H.view(np.int32) == want[d].view(np.int32)).sum())
     print(f"homography entries equal bit for bit: {exact} of {total}")
@@ -222,23 +269,51 @@ def test_reference_layout_keeps_the_plane_slice_contiguous_for_any_batch():
     assert torch.equal(oracle.inv3x3(H[:, 3]), per_image)
 
 
-def g11_cases():
-    """The homographies the REFERENCE handed its warper (tests/golden/g11_incremental_homographies.npz, captured by a hook
-    in make_golden.py), with the inputs regenerated from the recorded seeds."""
+def captured_cases(files=("g11_incremental_homographies.npz", "g12_camera_forms.npz")):
+    """The homographies the REFERENCE handed its warper (captured by a hook in make_golden.py), with the inputs regenerated
+    from the recorded seeds: g11 through make_batch's own camera, g12 through the K stored with each case (fx != fy,
+    off-centre and half-pixel principal points, a K per batch element, pyramids whose level scales differ)."""
     from conftest import load_golden
-    fix = load_golden("g11_incremental_homographies.npz")
-    for key in sorted(k for k in fix if k.endswith("_meta")):
-        tag = key[:-5]
-        rows, cols, D, S, B, seed, jit = (int(v) for v in fix[key])
-        batch = synthetic.make_batch(rows, cols, S, batch=B, seed=seed, pose_jitter=jit / 100.0)
-        inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
-        yield tag, fix, inp, D, S, B
+    for name in files:
+        fix = load_golden(name)
+        for key in sorted(k for k in fix if k.endswith("_meta")):
+            tag = key[:-5]
+            rows, cols, D, S, B, seed, jit = (int(v) for v in fix[key])
+            batch = synthetic.make_batch(rows, cols, S, batch=B, seed=seed, pose_jitter=jit / 100.0)
+            if f"{tag}_K" in fix:
+                batch["K"] = torch.from_numpy(fix[f"{tag}_K"]).clone()
+            inp = snu.multi_view_unpack_batch(batch, torch.device("cpu"), 5)
+            yield tag, fix, inp, D, S, B
+
+
+def test_both_captures_are_read_and_g12_holds_the_camera_forms():
+    tags = {tag: inp for tag, fix, inp, D, S, B in captured_cases()}
+    assert len(tags) >= 7 + 12 and "headline" in tags and "ragged_131x277_cam" in tags
+    K = tags["ragged_131x277_cam"]["K_pyr"]
+    assert K[0][0, 0, 0] != K[0][0, 1, 1] and K[4][0, 0, 0] / K[0][0, 0, 0] != K[4][0, 1, 1] / K[0][0, 1, 1]
+    assert not torch.equal(tags["b2_fy_below_fx"]["K_pyr"][0][0], tags["b2_fy_below_fx"]["K_pyr"][0][1])
+
+
+def test_host_intrinsics_pyramid_equals_the_captured_reference_bit_for_bit():
+    """`multi_view_unpack_batch` on the CPU against the K pyramid the reference's unpacker made of the same K (g12): every
+    level, every batch element -- the level scales sx = cols_l / cols_0 and sy = rows_l / rows_0 differ at the ragged sizes,
+    and the principal points are off-centre, so an x / y mix-up in the pyramid shows here."""
+    total = same = 0
+    for tag, fix, inp, D, S, B in captured_cases(("g12_camera_forms.npz",)):
+        want = fix[f"{tag}_Kpyr"]
+        assert want.shape == (5, B, 4, 4)
+        for lvl in range(5):
+            eq = inp["K_pyr"][lvl].numpy().view(np.int32) == want[lvl].view(np.int32)
+            total += eq.size
+            same += int(eq.sum())
+    print(f"K pyramid entries equal bit for bit: {same} of {total}")
+    assert same == total and total >= 12 * 5 * 16
 
 
 def test_oracle_geometry_equals_the_captured_reference_bit_for_bit():
     """Same torch, same host as the generator: idepth samples, both homography families and every incremental homography of the
     oracle ARE the reference's, for batches of one and of two (the permuted layout, `inv3x3`)."""
-    for tag, fix, inp, D, S, B in g11_cases():
+    for tag, fix, inp, D, S, B in captured_cases():
         r4, c4 = inp["left_image_pyr"][4].shape[-2:]
         for s in range(S):
             T = inp["T_right_in_left"][s].clone()
@@ -253,11 +328,27 @@ def test_oracle_geometry_equals_the_captured_reference_bit_for_bit():
             assert np.array_equal(inc.numpy().view(np.int32), fix[f"{tag}_Hinc_{s}"].view(np.int32)), (tag, s)
 
 
+def own_baseline(T):
+    """A chain's pose over its own baseline (multi_view_stereonet.py:566-571), every operation rounded."""
+    T = T.copy()
+    tx, ty, tz = T[0, 3], T[1, 3], T[2, 3]
+    base = np.sqrt(f32(f32(f32(tx * tx) + f32(ty * ty)) + f32(tz * tz)))
+    T[:3, 3] = (T[:3, 3] / f32(base)).astype(f32)
+    return T
+
+
+def restated_homography(K3, Ki, Tl, idepth):
+    core = Tl[:3, :3].copy()
+    core[:, 2] = (core[:, 2] + (Tl[:3, 3] * f32(idepth)).astype(f32)).astype(f32)
+    return mm3(K3, mm3(core, Ki))
+
+
 def test_restated_orders_reproduce_the_captured_incremental_homographies():
     """The numpy restatement (= csrc/mvsn_setup.hip, ref32) on the reference's own H family: every H_inc entry, bit for bit --
-    host-independent from here on (the fixture is data)."""
+    host-independent from here on (the fixture is data).  And the families themselves, H0 and H4, restated from the captured
+    pose, the captured samples and the K pyramid: every entry of every case, g12's cameras included."""
     total = 0
-    for tag, fix, inp, D, S, B in g11_cases():
+    for tag, fix, inp, D, S, B in captured_cases():
         for s in range(S):
             H4, want = fix[f"{tag}_H4_{s}"], fix[f"{tag}_Hinc_{s}"]
             for b in range(B):
@@ -266,6 +357,24 @@ def test_restated_orders_reproduce_the_captured_incremental_homographies():
                     assert np.array_equal(got.view(np.int32), want[b, d - 1].view(np.int32)), (tag, s, b, d)
                     total += 1
     assert total >= 150
+    entries = same = 0
+    for tag, fix, inp, D, S, B in captured_cases():
+        case = [0, 0]
+        for s in range(S):
+            for b in range(B):
+                Tl = inverse_pose(own_baseline(fix[f"{tag}_T_{s}"][b]))
+                K0, K4 = (inp["K_pyr"][lvl][b, :3, :3].numpy() for lvl in (0, 4))
+                smp = fix[f"{tag}_samples_{s}"][b]
+                H0 = restated_homography(K0, inverse_intrinsics(K0), Tl, smp[0])
+                eq = [H0.view(np.int32) == fix[f"{tag}_H0_{s}"][b, 0].view(np.int32)]
+                K4i = inverse_intrinsics(K4)
+                for d in range(D):
+                    eq.append(restated_homography(K4, K4i, Tl, smp[d]).view(np.int32) == fix[f"{tag}_H4_{s}"][b, d].view(np.int32))
+                case[0] += int(np.sum(eq))
+                case[1] += 9 * len(eq)
+        print(f"{tag}: restated H0 / H4 entries equal to the capture bit for bit: {case[0]} of {case[1]}")
+        same, entries = same + case[0], entries + case[1]
+    assert same == entries, (same, entries)
 
 
 # ---- the idepth samples (the maximum idepth is a mean over the level-4 pixels of an fp32 tensor program) ----------------------
@@ -392,14 +501,11 @@ def test_restated_idepth_samples_match_the_oracle_and_the_captured_reference():
     """Against the captured reference (g11, host-independent data): every chain.  Against the oracle on this host: torch's vectorised
     sqrt is an ulp off the correctly rounded root for ~0.7 % of its arguments, which the restatement does not follow -- the mean
     over the pixels absorbs it (204 of 204 chains when this was written); a chain or two may differ on another host."""
-    for tag, fix, inp, D, S, B in g11_cases():
+    for tag, fix, inp, D, S, B in captured_cases():
         r4, c4 = inp["left_image_pyr"][4].shape[-2:]
         for s in range(S):
             for b in range(B):
-                T = fix[f"{tag}_T_{s}"][b].copy()
-                tx, ty, tz = T[0, 3], T[1, 3], T[2, 3]
-                base = np.sqrt(f32(f32(f32(tx * tx) + f32(ty * ty)) + f32(tz * tz)))
-                T[:3, 3] = (T[:3, 3] / f32(base)).astype(f32)
+                T = own_baseline(fix[f"{tag}_T_{s}"][b])
                 got = idepth_samples_restated(T, inp["K_pyr"][-1][b].numpy(), r4, c4, D)
                 assert np.array_equal(got.view(np.int32), fix[f"{tag}_samples_{s}"][b].view(np.int32)), (tag, s, b)
     total = same = 0
