@@ -129,16 +129,18 @@ struct Bilinear {
 };
 
 __device__ __forceinline__ Bilinear bilinear_taps(float ix, float iy, int rows, int cols) {
-  // NaN coordinates (u2 == 0) propagate through the weights exactly as in grid_sample; fminf/fmaxf
-  // would swallow them, so clamp with comparisons.
-  ix = ix < 0.0f ? 0.0f : (ix > (float)(cols - 1) ? (float)(cols - 1) : ix);
-  iy = iy < 0.0f ? 0.0f : (iy > (float)(rows - 1) ? (float)(rows - 1) : iy);
+  // A NaN coordinate (0 / 0 where u2 == 0) is clamped to 0, as grid_sample's border padding does it (its clip is
+  // min(size - 1, max(coordinate, 0)) with the operands ordered so that a NaN leaves as 0): the voxel reads texel 0 of
+  // that axis with finite weights and nothing non-finite reaches the volume (pinned by tests/golden/g13_zero_denominator.npz,
+  // the reference's own warper on such homographies).  +-inf clamps to the nearer border like any other coordinate.
+  ix = ix > 0.0f ? (ix > (float)(cols - 1) ? (float)(cols - 1) : ix) : 0.0f;
+  iy = iy > 0.0f ? (iy > (float)(rows - 1) ? (float)(rows - 1) : iy) : 0.0f;
   float fx0 = floorf(ix), fy0 = floorf(iy);
   float fx = ix - fx0, fy = iy - fy0;
   Bilinear b;
   b.x0 = (int)fx0;
   b.y0 = (int)fy0;
-  if (!(b.x0 >= 0 && b.x0 < cols)) b.x0 = 0;  // only reachable through NaN
+  if (!(b.x0 >= 0 && b.x0 < cols)) b.x0 = 0;  // (unreachable after the clamp above; kept: an index is never out of range)
   if (!(b.y0 >= 0 && b.y0 < rows)) b.y0 = 0;
   b.x1 = b.x0 + 1 < cols ? b.x0 + 1 : cols - 1;
   b.y1 = b.y0 + 1 < rows ? b.y0 + 1 : rows - 1;

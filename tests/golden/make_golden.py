@@ -26,6 +26,7 @@ Fixtures:
   gc5_gta_1024x512_d128_s4.npz  BASELINE config 5 geometry (fp32 reference): idepth_0 (fp32), idepth_4, mask_4
   g11_incremental_homographies.npz  every homography the reference hands its warper during a forward (H0, H family, H_inc)
   g12_camera_forms.npz          the same capture through cameras with fx != fy, off-centre principal points, ragged pyramids
+  g13_zero_denominator.npz      PlaneSweepWarper where the homography's third row is exactly 0 on a column of pixel centres
 
     python tests/golden/make_golden.py [name-prefix ...]     # e.g. "gc" regenerates only the gc* fixtures
 """
@@ -445,6 +446,24 @@ def incremental_homography_pins(name, cases=INC_CASES):
     print(name, "ok")
 
 
+def zero_denominator_pins(name):
+    """PlaneSweepWarper on a 3-channel 8x12 frame and three homographies whose denominator u2 = H[2] . (x, y, 1) is EXACTLY
+    zero on the column of pixel centres x = 5 (every entry a small dyadic number: the products and sums are exact in fp32
+    in any order, so matmul and scalar evaluation agree to the bit).  On that column the reference divides by zero:
+      plane 0: u0 = 2 (x - 5) + (y - 3): 0/0 at y = 3, +-inf elsewhere;  u1 = y + 0.5 > 0: +inf;      u2 = x - 5
+      plane 1: u0 = x = 5: inf;  u1 = (x - 5) + (y - 4) / 2: 0/0 at y = 4, +-inf elsewhere;            u2 = 5 - x
+      plane 2: u0 = (x - 5) / 2: 0/0 on the whole column;  u1 = y - 2: 0/0 at y = 2, +-inf elsewhere;  u2 = (x - 5) / 4
+    Left of it (planes 0, 2) or right of it (plane 1) u2 < 0: the plane lies behind the camera."""
+    g = torch.Generator().manual_seed(13)
+    img = torch.rand(1, 3, 8, 12, generator=g) * 2 - 1
+    H = torch.tensor([[[2.0, 1.0, -13.0], [0.0, 1.0, 0.5], [1.0, 0.0, -5.0]],
+                      [[1.0, 0.0, 0.0], [1.0, 0.5, -7.0], [-1.0, 0.0, 5.0]],
+                      [[0.5, 0.0, -2.5], [0.0, 1.0, -2.0], [0.25, 0.0, -1.25]]])[None]
+    vol, mask = PlaneSweepWarper()(img, H.clone())
+    np.savez_compressed(os.path.join(HERE, name), zd_image=npy(img), zd_H=npy(H), zd_volume=npy(vol), zd_mask=npy(mask))
+    print(name, "ok")
+
+
 def main():
     torch.set_num_threads(8)
     G = "gta_sfm_150epochs"
@@ -466,6 +485,7 @@ def main():
         ("g9_two_view_consistency.npz", lambda n: consistency_pins(n)),
         ("g11_incremental_homographies.npz", lambda n: incremental_homography_pins(n)),
         ("g12_camera_forms.npz", lambda n: incremental_homography_pins(n, CAMERA_CASES)),
+        ("g13_zero_denominator.npz", lambda n: zero_denominator_pins(n)),
     ]
     want = sys.argv[1:]
     for name, job in jobs:

@@ -1083,9 +1083,37 @@ def _oracle_chain(w, src4, H, Hinc, F0, FL):
     return fvol_ref, cost_ref, mask_ref
 
 
-def _motion_family(N, D, kind, seed):
-    """Incremental homographies with a prescribed inter-plane motion (H = their running product)."""
+GENERAL_KINDS = ("roll", "zoom", "tilt", "behind", "gone", "general")
+# the banded form's plans (header of csrc/mvsn_chain_band.hip): grid -> (band rows, gather window +- rows) of each plan;
+# 16x32 runs 8 bands of 2 rows ("half split") up to CUs / 8 chains and 4 bands of 4 rows beyond
+BAND_PLANS = {(16, 32): ((4, 3), (2, 3)), (30, 40): ((2, 3),), (32, 64): ((2, 1),)}
+
+
+def _motion_family(N, D, kind, seed, grid=(16, 32)):
+    """Incremental homographies with a prescribed inter-plane motion (H = their running product).
+
+    "small" / "vertical" / "mixed": near-translations, the same displacement for every pixel of a plane (built in fp32, as
+    they always were).  GENERAL_KINDS: homographies in general position for a rows x cols = `grid` plane, built in
+    float64 -- Hinc per plane, H its running product -- and rounded ONCE to fp32:
+      roll    in-plane rotation about the image centre, alternating in sign (the product stays a small rotation).  The
+              row displacement of a rotation is sin(angle) * (x - cx) in EVERY band, so whether a band's gathers stay
+              inside its window depends on the band only through the image border (rows above 0 / below rows - 1 do
+              not exist, their taps clamp).  The edge displacement therefore cycles per plane through ~4 rows (-4 at one
+              edge, +4 at the other, sub-row in the middle: every band beyond a +-3-row window), 2.2 - 2.8 rows (the
+              interior bands beyond it, the first band inside) and 0.3 - 0.9 rows (inside a +-3 window everywhere; on
+              the +-1-row window of 32x64 the first band inside, the others beyond)
+      zoom    scale about an off-centre point, 0.8 - 0.95 per plane on even chains and 1.05 - 1.25 on odd ones (~0.3x /
+              ~3x over the chain): the row displacement grows with the distance from that point, band by band
+      tilt    perspective: u2 runs from ~0.4 in one corner to ~2.5 in the opposite one, the orientation turning from
+              plane to plane; u2 > 0 everywhere, for Hinc and for H
+      behind  u2 changes sign inside the image on odd planes (even planes undo it), the zero line BETWEEN pixel centres:
+              u2 != 0 everywhere, no coordinate is NaN.  u0 changes sign close by, so on even chains voxels behind the
+              camera (u2 < 0) land inside the source and stay unmasked; on odd chains the front side does
+      gone    a sideways jump of 1.5 image widths and back: one whole plane outside, its neighbours partly inside
+      general roll x zoom x a milder tilt x a translation on every plane, one plane behind the camera, one jump away"""
     g = torch.Generator().manual_seed(seed)
+    if kind in GENERAL_KINDS:
+        return _general_family(N, D, kind, g, grid)
     Hinc = torch.eye(3).repeat(N, D, 1, 1)
     for n in range(N):
         for d in range(1, D):
@@ -1105,6 +1133,196 @@ def _motion_family(N, D, kind, seed):
     for d in range(1, D):
         H[:, d] = H[:, d - 1] @ Hinc[:, d]
     return H, Hinc
+
+
+def _general_family(N, D, kind, g, grid):
+    rows, cols = grid
+    cx, cy = (cols - 1) / 2.0, (rows - 1) / 2.0
+    u = lambda: float(torch.rand(1, generator=g, dtype=torch.float64))
+    M = lambda m: torch.tensor(m, dtype=torch.float64)
+    shift = lambda tx, ty: M([[1, 0, tx], [0, 1, ty], [0, 0, 1]])
+    about = lambda A, px, py: shift(px, py) @ A @ shift(-px, -py)
+
+    def roll(n, d):
+        edge = (0.3 + 0.6 * u(), 3.6 + 0.8 * u(), 2.2 + 0.6 * u())[d % 3] * (1 if d % 2 else -1)
+        s = max(-0.5, min(0.5, edge / cx))             # sin(angle): `edge` rows at x = 0 and x = cols - 1 (30 degrees at most)
+        c = (1.0 - s * s) ** 0.5
+        return shift(0.5 * u() - 0.25, 0.4 * u() - 0.2) @ about(M([[c, -s, 0], [s, c, 0], [0, 0, 1]]), cx, cy)
+
+    def zoom(n, d, span=None):
+        a, b = span if span else ((0.8, 0.95) if n % 2 == 0 else (1.05, 1.25))
+        s = a + (b - a) * u()
+        return about(M([[s, 0, 0], [0, s, 0], [0, 0, 1]]), cols * (0.25 + 0.1 * u()), rows * (0.55 + 0.15 * u()))
+
+    def tilt(n, d, lo=0.4, hi=2.5, pair=None):
+        # u2 = lo in one corner and hi in the opposite one, the image centre a fixed point (up to a sub-pixel shift).  `pair` (the "tilt" kind): an even plane tilts the opposite way to the
+        # odd plane before it -- the product of the two is nearly affine, so the running product H alternates between
+        # a full tilt and a mild one and its u2 stays positive (same-way tilts compound into a horizon inside the image)
+        if pair is not None and d % 2 == 0:
+            sx, sy, wx = -pair[0], -pair[1], pair[2] + 0.06 * (u() - 0.5)
+        else:
+            sx, sy, wx = (1 if (d // 2) % 2 else -1), (1 if (d // 2 + n) % 2 else -1), 0.35 + 0.3 * u()
+            if pair is not None:
+                pair[:] = [sx, sy, wx]
+        gx, gy = sx * wx * (hi - lo) / (cols - 1), sy * (1 - wx) * (hi - lo) / (rows - 1)
+        a0 = lo - min(gx, 0.0) * (cols - 1) - min(gy, 0.0) * (rows - 1)
+        k = a0 + gx * cx + gy * cy
+        return shift(u() - 0.5, u() - 0.5) @ about(M([[k, 0, 0], [0, k, 0], [gx, gy, k]]), cx, cy)
+
+    def behind(n, d):
+        # u2 = gz (x - xz) (+ a slight dependence on y), xz at least a quarter pixel from a pixel centre;
+        # u0 = r gz xz (x - 1.3 xz): px = r xz (x - 1.3 xz) / (x - xz) is 0.4 cols at x = 0, rises to +inf at xz- (u0 and
+        # u2 of one sign: inside the source up to the right border), comes back from -inf and re-enters at 1.3 xz;
+        # py = xz (y - t) / (xz - x): positive left of the line only
+        xz = int(cols * (0.35 + 0.2 * u())) + 0.25 + 0.5 * u()
+        gz = (0.04 + 0.02 * u()) * (1 if n % 2 == 0 else -1)
+        r = cols / 3.2 / xz
+        return M([[r * gz * xz, 0, -1.3 * r * gz * xz * xz], [0, -gz * xz, gz * xz * (u() - 0.5)],
+                  [gz, 0.002 * gz, -gz * xz]])
+
+    def gone(n, d):
+        k, side = 2 + n % max(1, D - 3), (1 if n % 2 == 0 else -1)     # the plane that leaves; back on the next one
+        if d == k:
+            return shift(1.5 * cols * side, 0.5 * u())
+        if d == k + 1:
+            return shift(-1.5 * cols * side + u(), -0.5 * u())
+        return shift(0.3 * cols * (u() - 0.5), 0.3 * rows * (u() - 0.5))
+
+    def general(n, d, back):
+        A = shift(2 * u() - 1, 2 * u() - 1) @ roll(n, d) @ zoom(n, d, (0.87, 0.97) if d % 2 else (1.04, 1.16)) \
+            @ tilt(n, d, 0.75, 1.4)
+        kb, kg = 2 + n % 2, 5 + n % 2
+        if d == kb:                                    # behind the camera on this plane ...
+            back[0] = behind(n, d)
+            A = A @ back[0]
+        elif d == kb + 1:                              # ... and in front of it again on the next
+            A = torch.linalg.inv(back[0]) @ A
+        if d in (kg, kg + 1):                          # 1.5 widths away and back
+            A = A @ shift(1.5 * cols * (1 if d == kg else -1), 0.0)
+        return A
+
+    ys, xs = torch.meshgrid(torch.arange(rows, dtype=torch.float64), torch.arange(cols, dtype=torch.float64), indexing="ij")
+
+    def clear_of_centres(A):
+        # u2 is not zero at any pixel centre, in fp32 as in float64: the line u2 = 0 stays 0.002 px away from every centre,
+        # hundreds of times the rounding of an fp32 evaluation.  (The "behind" planes draw a near-vertical line a
+        # quarter pixel from the centres; a line in general position crosses the grid too close to some centre for more.)
+        u2 = A[2, 0] * xs + A[2, 1] * ys + A[2, 2]
+        return float(u2.abs().min()) >= 0.002 * float((A[2, 0] ** 2 + A[2, 1] ** 2) ** 0.5)
+
+    Hinc = torch.eye(3, dtype=torch.float64).repeat(N, D, 1, 1)
+    H = Hinc.clone()
+    for n in range(N):
+        back, pair = [None], [0, 0, 0.5]
+        for d in range(1, D):
+            for attempt in range(100):                 # (re-drawn until the zero lines of Hinc and H clear the pixel centres)
+                if kind == "behind":
+                    A = behind(n, d) if d % 2 else torch.linalg.inv(Hinc[n, d - 1]) @ shift(u() - 0.5, u() - 0.5)
+                elif kind == "general":
+                    A = general(n, d, back)
+                elif kind == "tilt":
+                    A = tilt(n, d, pair=pair)
+                else:
+                    A = {"roll": roll, "zoom": zoom, "gone": gone}[kind](n, d)
+                if clear_of_centres(A) and clear_of_centres(H[n, d - 1] @ A):
+                    break
+            else:
+                raise AssertionError(f"{kind}: no admissible plane {d} of chain {n}")
+            Hinc[n, d] = A
+            H[n, d] = H[n, d - 1] @ A
+    return H.float(), Hinc.float()
+
+
+def _coords_f64(H, rows, cols):
+    """The reference's coordinate expression (stereo/image_predictor.py:493-516) in float64 on fp32 (or any) homographies
+    H (..., 3, 3): u2, the normalised nx, ny, and the mask |n| > 1, each (..., rows, cols)."""
+    H = H.double()
+    ys, xs = torch.meshgrid(torch.arange(rows, dtype=torch.float64), torch.arange(cols, dtype=torch.float64), indexing="ij")
+    e = lambda i, j: H[..., i, j, None, None]
+    u0, u1, u2 = (e(i, 0) * xs + e(i, 1) * ys + e(i, 2) for i in range(3))
+    nx = ((u0 / u2 + 0.5) * 2.0) / cols - 1.0
+    ny = ((u1 / u2 + 0.5) * 2.0) / rows - 1.0
+    return u2, nx, ny, (nx.abs() > 1.0) | (ny.abs() > 1.0)
+
+
+def _warp_f64(img, H):
+    """The reference's warp restated in float64, same expression order: ((p + 0.5) * 2) / size - 1, grid_sample's
+    un-normalisation and border clamp (which sends a NaN coordinate to 0), four taps, times (not mask).
+    img (B,C,rows,cols), H (B,n,3,3) -> volume (B,C,n,rows,cols) float64, mask (B,n,rows,cols)."""
+    B, C, rows, cols = img.shape
+    n = H.shape[1]
+    _, nx, ny, mask = _coords_f64(H, rows, cols)
+    taps = []
+    for nrm, size in ((nx, cols), (ny, rows)):
+        i = ((nrm + 1.0) * size - 1.0) / 2.0
+        i = torch.where(i > 0, i, torch.zeros_like(i)).clamp(max=size - 1.0)
+        i0 = i.floor()
+        taps.append((i0.long(), (i0.long() + 1).clamp(max=size - 1), i - i0))
+    (x0, x1, fx), (y0, y1, fy) = taps
+    flat = img.double().reshape(B, 1, C, rows * cols).expand(B, n, C, rows * cols)
+    tap = lambda yi, xi: torch.gather(flat, 3, (yi * cols + xi).reshape(B, n, 1, rows * cols).expand(-1, -1, C, -1))
+    w = lambda a, b: (a * b).reshape(B, n, 1, rows * cols)
+    out = tap(y0, x0) * w(1 - fx, 1 - fy) + tap(y0, x1) * w(fx, 1 - fy) + tap(y1, x0) * w(1 - fx, fy) + tap(y1, x1) * w(fx, fy)
+    out = out * (~mask).double().reshape(B, n, 1, rows * cols)
+    return out.reshape(B, n, C, rows, cols).permute(0, 2, 1, 3, 4).contiguous(), mask
+
+
+MASK_EDGE = 16 * 2.0 ** -23
+
+
+def _mask_rule(mask, mref, H, what):
+    """test_homography_warp's rule for masks (B,n,rows,cols) of homographies in general position: EVERY voxel that differs
+    from the reference has its coordinate recomputed in float64 and must lie within 16 * 2^-23 of the |n| > 1 predicate,
+    and at most max(1, numel // 20000) voxels may differ.  Returns the number of mismatches."""
+    rows, cols = mask.shape[-2:]
+    diff = (mask != mref).nonzero()
+    cap = max(1, mref.numel() // 20000)
+    print(f"{what}: {diff.shape[0]} of {mref.numel()} mask voxels differ (cap {cap})")
+    if diff.shape[0]:
+        b, d, yy, xx = diff.unbind(1)
+        Hd = H[b, d].double()                                                        # (K,3,3)
+        uu = Hd[:, :, 0] * xx.double()[:, None] + Hd[:, :, 1] * yy.double()[:, None] + Hd[:, :, 2]
+        nx = ((uu[:, 0] / uu[:, 2] + 0.5) * 2.0) / cols - 1.0
+        ny = ((uu[:, 1] / uu[:, 2] + 0.5) * 2.0) / rows - 1.0
+        edge = torch.minimum((nx.abs() - 1.0).abs(), (ny.abs() - 1.0).abs())
+        worst = int(torch.where(torch.isnan(edge), torch.full_like(edge, float("inf")), edge).argmax())
+        assert bool((edge < MASK_EDGE).all()), \
+            f"{what}: mask voxel {tuple(diff[worst].tolist())} differs {float(edge[worst]):.3e} away from the predicate"
+    assert diff.shape[0] <= cap, f"{what}: {diff.shape[0]} mask voxels differ, cap {cap}"
+    return diff.shape[0]
+
+
+def _band_paths(Hinc, grid, BR, W):
+    """Which gather path each band of the banded form takes at each step, from its inputs alone (float64): prepare() in
+    csrc/mvsn_chain_band.hip takes the min / max source row (y0, and y1 = the clamped y0 + 1) over the pixels of the
+    band's rows lo - 1 .. hi + 1 that exist, and gathers from the LDS window iff they lie in lo - W .. hi + W + 1.
+    Hinc (N,D,3,3) -> bool (N, D, rows // BR), True = window path (plane 0 has no step: True)."""
+    rows, cols = grid
+    _, _, ny, _ = _coords_f64(Hinc, rows, cols)
+    iy = ((ny + 1.0) * rows - 1.0) / 2.0
+    iy = torch.where(iy > 0, iy, torch.zeros_like(iy)).clamp(max=rows - 1.0)
+    y0 = iy.floor().long()
+    y1 = (y0 + 1).clamp(max=rows - 1)
+    fast = torch.ones(Hinc.shape[0], Hinc.shape[1], rows // BR, dtype=torch.bool)
+    for m in range(rows // BR):
+        lo, hi = m * BR, m * BR + BR - 1
+        a, b = max(lo - 1, 0), min(hi + 1, rows - 1) + 1
+        fast[:, :, m] = (y0[:, :, a:b].amin((2, 3)) >= lo - W) & (y1[:, :, a:b].amax((2, 3)) <= hi + W + 1)
+    fast[:, 0] = True
+    return fast
+
+
+def _planes_on_both_paths(Hinc, grid, interior=False):
+    """Per plan of the grid: the (chain, plane) pairs whose bands are on BOTH gather paths.  `interior`: counting only
+    the bands that have a neighbour on either side -- the first and the last band have no rows beyond the image to reach
+    for, so the border alone can keep them on the window path while every other band is off it."""
+    out = []
+    for BR, W in BAND_PLANS[tuple(grid)]:
+        fast = _band_paths(Hinc, grid, BR, W)[:, 1:]
+        if interior:
+            fast = fast[:, :, 1:-1]
+        out.append((fast.any(2) & ~fast.all(2)).nonzero().tolist())
+    return out
 
 
 @pytest.mark.parametrize("kind,N,D,grid", [("small", 1, 12, (16, 32)), ("vertical", 2, 10, (16, 32)),
@@ -1193,6 +1411,203 @@ def test_slab_chain_gather_paths_vs_oracle(kind, N, D, grid, extra):
                   f"max-rel {max_rel:.3e}")
             assert mean_rel < 1e-5 and max_rel < 1e-4, (form, name, mean_rel, max_rel)
     assert torch.equal(got["banded"][1], got[other][1])
+
+
+# (kind, N, D, grid, family seed): every kind on every banded geometry, small; the last case has more chains than
+# CUs / 8 = 32, where 16x32 runs the banded form's many-chain plan (4 bands of 4 rows)
+GENERAL_CHAIN_CASES = [(kind, 2, 8, grid, 3) for kind in GENERAL_KINDS for grid in ((16, 32), (30, 40), (32, 64))] + \
+    [("general", 36, 4, (16, 32), 3)]
+CHAIN_FORMS = ("direct", "winograd", "stepwise", "banded", "slab")
+BOTH_PATHS_KINDS = ("roll", "general")     # kinds whose inputs must put bands of one plane on both gather paths
+
+
+def _general_chain_inputs(kind, N, D, grid, seed):
+    """src4, H, Hinc, F0, FL of a case (seeded like test_banded_chain_gather_paths_vs_oracle's)."""
+    g = torch.Generator().manual_seed(5)
+    H, Hinc = _motion_family(N, D, kind, seed, grid)
+    r4, c4 = grid
+    src4 = torch.rand(N, 3, r4, c4, generator=g) * 2 - 1
+    F0 = torch.randn(N, 32, r4, c4, generator=g)
+    FL = torch.randn(N, 32, r4, c4, generator=g)
+    return src4, H, Hinc, F0, FL
+
+
+def _assert_both_paths(kind, Hinc, grid):
+    """The condition on the inputs of BOTH_PATHS_KINDS.  "general": on every plan of the grid some plane splits its
+    INTERIOR bands between the window path and the granule path -- window rows and hand-off granules consumed side by
+    side.  "roll": some plane splits its bands at all; a rotation moves every band by the same rows, so there the split
+    is (almost only) the first or last band against the rest, through the image border -- on 32x64's +-1-row window
+    even "small" splits that way, so for roll on that grid this assertion constrains nothing; the side-by-side state
+    rests on general, tilt and zoom."""
+    r4, c4 = grid
+    for (BR, W), planes in zip(BAND_PLANS[grid], _planes_on_both_paths(Hinc, grid, interior=kind == "general")):
+        assert planes, f"{kind} on {r4}x{c4}: no plane has bands of {BR} rows on both sides of the +-{W}-row window"
+
+
+def _run_chain_form(net, eng, form, dev):
+    try:
+        net.options.chain_form = "banded" if form == "slab" else form
+        eng.lib.mvsn_debug_set_band_flags(SLAB if form == "slab" else 0)
+        cost, mask, fvol = eng.incremental_cost_volume(*dev, want_features=True)
+        torch.cuda.synchronize()
+        assert eng.chain_status() == 0, form
+        return cost.cpu(), mask.cpu(), fvol.cpu()
+    finally:
+        eng.lib.mvsn_debug_set_band_flags(0)
+        net.options.chain_form = "auto"
+
+
+@pytest.mark.parametrize("kind,N,D,grid,seed", GENERAL_CHAIN_CASES)
+def test_chain_forms_on_general_homographies(kind, N, D, grid, seed):
+    """Every form of the chain that has a plan for the grid (direct, stepwise, banded, slab; Winograd on 16x32) on
+    homographies in general position (_motion_family's GENERAL_KINDS: roll, zoom, strong perspective, planes behind the
+    camera, a plane wholly outside, and their product) against the oracle's recurrence: status 0; features and cost
+    within the chain tolerances of this file's header where the masks agree; the mask bit-identical in all forms and,
+    against the oracle, by test_homography_warp's rule (_mask_rule: the oracle forms H @ grid as a matmul;
+    tests/test_homography_families_cpu.py proves on the CPU that these very inputs leave the fp32 oracle within the cap
+    against the float64 predicate).  For "roll" and "general" the inputs must put bands of ONE plane on both gather
+    paths of the banded form (_assert_both_paths: about the inputs, from Hinc and the band geometry)."""
+    w = load_weights("gta_sfm_150epochs")
+    net = net_for("gta_sfm_150epochs")
+    eng = net.engine()
+    r4, c4 = grid
+    inputs = _general_chain_inputs(kind, N, D, grid, seed)
+    src4, H, Hinc, F0, FL = inputs
+    if kind in BOTH_PATHS_KINDS:
+        _assert_both_paths(kind, Hinc, grid)
+    fvol_ref, cost_ref, mask_ref = _oracle_chain(w, *inputs)
+    dev = [x.to(DEV) for x in inputs]
+    forms = [f for f in CHAIN_FORMS
+             if f != "winograd" or eng.lib.mvsn_incremental_cost_volume_form(r4, c4) == _native.CHAIN_WINOGRAD]
+    assert c4 % 4 == 0 and set(forms) >= {"direct", "stepwise", "banded", "slab"}
+    got = {form: _run_chain_form(net, eng, form, dev) for form in forms}
+    for form, (cost, mask, fvol) in got.items():
+        assert torch.equal(mask, got["direct"][1]), f"the {form} form's mask differs from the direct form's"
+        what = f"chain[{form}] {kind} {r4}x{c4} N={N} D={D}"
+        _mask_rule(mask, mask_ref, H, what)
+        agree = (mask == mask_ref)[:, None].expand_as(fvol_ref)
+        for name, a, b in (("features", fvol, fvol_ref), ("cost", cost, cost_ref)):
+            assert bool(torch.isfinite(a).all()), (form, name)
+            mean_rel, max_rel = rel_err(a[agree], b[agree])
+            print(f"{what} {name}: mean-rel {mean_rel:.3e} max-rel {max_rel:.3e}")
+            assert mean_rel < 1e-5 and max_rel < 1e-4, (form, name, mean_rel, max_rel)
+
+
+# (B, C, n, rows, cols) -> the kernel form the launch selects (csrc/mvsn_warp.hip: warp_launch)
+WARP_GENERAL_SHAPES = [(2, 3, 6, 30, 42),       # one pixel per thread, cols % 4 != 0
+                       (2, 5, 7, 8, 2),         # ... a frame of two columns: every pair shifted at the right border
+                       (2, 32, 3, 30, 40),      # SPLIT: a small launch with many channels
+                       (24, 5, 3, 128, 512)]    # four pixels per thread (homography_warp_px_kernel<4>): past the threshold
+
+
+def _family_H(kind, B, n, rows, cols, seed=3):
+    """n absolute homographies per frame: planes 1 .. n of a family's running product (plane 0 is the identity)."""
+    return _motion_family(B, n + 1, kind, seed, (rows, cols))[0][:, 1:].contiguous()
+
+
+def _general_warp_inputs(kind, B, C, n, rows, cols):
+    g = torch.Generator().manual_seed(rows * cols + n)
+    return torch.rand(B, C, rows, cols, generator=g) * 2 - 1, _family_H(kind, B, n, rows, cols)
+
+
+@pytest.mark.parametrize("B,C,n,rows,cols", WARP_GENERAL_SHAPES)
+@pytest.mark.parametrize("kind", GENERAL_KINDS)
+def test_homography_warp_on_general_homographies(kind, B, C, n, rows, cols):
+    """mvsn_homography_warp on the absolute homographies of _motion_family's GENERAL_KINDS, at shapes that reach each
+    form of the kernel, against the float64 restatement of the reference's expression (_warp_f64).  Masks by
+    test_homography_warp's rule; values where the masks agree within rtol 1e-4 and atol = cols * 2^-23 * 8 -- or, where
+    the fp32 ORACLE on the same inputs is itself further from the float64 restatement than that bound (strong
+    perspective: px = u0 / u2 magnifies the rounding of u2), four times the oracle's own excess (the margin covers the
+    different but legitimate fp32 association of the three-term dot products).  Both figures are printed.
+    (homography_warp_px_kernel<8> is a compile-time variant, -DMVSN_WARP_PX=8; the shipped library has <4>.)"""
+    eng = net_for("gta_sfm_150epochs").engine()
+    img, H = _general_warp_inputs(kind, B, C, n, rows, cols)
+    if (B, C, n, rows, cols) == WARP_GENERAL_SHAPES[-1]:
+        assert B * n * rows * cols >= 4 * 16 * 64 * 4 * 256      # (the four-pixel form's threshold on 256 CUs)
+    vol, mask = eng.homography_warp(img.to(DEV), H.to(DEV))
+    vol, mask = vol.cpu().double(), mask.cpu()
+    v64, m64 = _warp_f64(img, H)
+    what = f"homography_warp[{kind}] {B}x{C}x{n}x{rows}x{cols}"
+    _mask_rule(mask, m64, H, what)
+    vor, mor = oracle.homography_warp(img, H)
+    rtol, base = 1e-4, cols * 2.0 ** -23 * 8
+    both = (mor == m64)[:, None].expand_as(v64)
+    excess = float(((vor.double() - v64).abs() - rtol * v64.abs())[both].max())
+    atol = max(base, 4 * excess)
+    agree = (mask == m64)[:, None].expand_as(v64)
+    err = float(((vol - v64).abs() - rtol * v64.abs())[agree].max())
+    print(f"{what}: kernel {err:.3e} | fp32 oracle {excess:.3e} beyond rtol {rtol:g} of the float64 restatement; "
+          f"atol {atol:.3e} (cols * 2^-23 * 8 = {base:.3e})")
+    assert bool(torch.isfinite(vol).all())
+    assert err <= atol, (what, err, atol)
+
+
+def test_homography_warp_many_frames_form_is_bit_identical_on_general_homographies():
+    """test_homography_warp_many_frames_form_is_bit_identical with the "general" family: the four-pixel form against the
+    same frames warped one frame and one plane at a time, bit for bit."""
+    B, C, n, rows, cols = 24, 5, 3, 128, 512
+    eng = net_for("gta_sfm_150epochs").engine()
+    g = torch.Generator().manual_seed(B * 131 + cols)
+    img = torch.rand(B, C, rows, cols, generator=g) * 2 - 1
+    img[0, 0, 3, 5], img[B - 1, C - 1, rows - 1, cols - 1] = float("nan"), float("inf")
+    img, H = img.to(DEV), _family_H("general", B, n, rows, cols).to(DEV)
+    assert B * n * rows * cols >= 4 * 16 * 64 * 4 * 256
+    vol, mask = eng.homography_warp(img, H)
+    for b in range(B):
+        for d in range(n):
+            v1, m1 = eng.homography_warp(img[b:b + 1], H[b:b + 1, d:d + 1].contiguous())
+            assert torch.equal(m1[0, 0], mask[b, d])
+            assert torch.equal(v1[0, :, 0].view(torch.int32), vol[b, :, d].view(torch.int32)), (b, d)
+
+
+def test_zero_denominator_follows_the_reference():
+    """tests/golden/g13_zero_denominator.npz: the reference's own warper (PlaneSweepWarper, on the CPU) on an 8x12 frame
+    and three homographies whose u2 is exactly 0 on the column x = 5 of pixel centres -- 0/0 at some of those pixels,
+    +-inf at the others.  grid_sample's border clamp sends a NaN coordinate to 0, so the reference's volume holds no NaN
+    at all: the voxel reads texel 0 of that axis, and is masked or not by the |n| > 1 predicate (false for NaN).
+    mvsn_homography_warp must give the same mask bits, NaN at the same positions (none) and the same values; so must the
+    chain's image gather on the same H (planes 1 .. 3 of a chain whose Hinc is the identity: its features against the
+    oracle's recurrence fed with the REFERENCE's warped planes)."""
+    fix = load_golden("g13_zero_denominator.npz")
+    w = load_weights("gta_sfm_150epochs")
+    net = net_for("gta_sfm_150epochs")
+    eng = net.engine()
+    img, H, vref, mref = t(fix["zd_image"]), t(fix["zd_H"]), t(fix["zd_volume"]), t(fix["zd_mask"])[:, 0]
+    assert not bool(torch.isnan(vref).any())
+    for frame in (img, img.repeat(1, 11, 1, 1)):        # 33 channels: the SPLIT form
+        vol, mask = eng.homography_warp(frame.to(DEV), H.to(DEV))
+        want = vref.repeat(1, frame.shape[1] // 3, 1, 1, 1)
+        assert torch.equal(mask.cpu(), mref)
+        assert torch.equal(torch.isnan(vol.cpu()), torch.isnan(want))
+        close(vol, want, rtol=1e-5, atol=2e-6)
+    v64, m64 = _warp_f64(img, H)                         # (the restatement's NaN rule is the reference's)
+    assert torch.equal(m64, mref)
+    close(v64, vref, rtol=1e-5, atol=2e-6)
+    # the chain: plane 0 = identity, planes 1 .. 3 = the fixture's homographies, features carried over unmoved
+    rows, cols = img.shape[-2:]
+    g = torch.Generator().manual_seed(13)
+    Hc = torch.cat([torch.eye(3)[None, None], H], 1)
+    Hinc = torch.eye(3).repeat(1, 4, 1, 1)
+    F0, FL = torch.randn(1, 32, rows, cols, generator=g), torch.randn(1, 32, rows, cols, generator=g)
+    mask_ref = torch.cat([torch.zeros(1, 1, rows, cols, dtype=torch.bool), mref], 1)
+    planes = [F0]
+    for d in range(1, 4):
+        moved, _ = oracle.homography_warp(planes[-1], Hinc[:, d:d + 1])
+        planes.append(oracle.feature_refiner(w, "right_feature_extractor.refiner", vref[:, :, d - 1], moved[:, :, 0]))
+    fvol_ref = torch.stack(planes, 2) * (~mask_ref).float()[:, None]
+    cost_ref = (~mask_ref).float()[:, None] * (FL[:, :, None] - fvol_ref).abs()
+    dev = [x.to(DEV) for x in (img, Hc, Hinc, F0, FL)]
+    forms = ["direct", "stepwise"]
+    if eng.lib.mvsn_incremental_cost_volume_form(rows, cols) == _native.CHAIN_WINOGRAD:
+        forms.append("winograd")
+    for form in forms:
+        cost, mask, fvol = _run_chain_form(net, eng, form, dev)
+        assert torch.equal(mask, mask_ref), form
+        for name, a, b in (("features", fvol, fvol_ref), ("cost", cost, cost_ref)):
+            assert torch.equal(torch.isnan(a), torch.isnan(b)), (form, name)
+            mean_rel, max_rel = rel_err(a, b)
+            print(f"zero denominator chain[{form}] {name}: mean-rel {mean_rel:.3e} max-rel {max_rel:.3e}")
+            assert mean_rel < 1e-5 and max_rel < 1e-4, (form, name, mean_rel, max_rel)
 
 
 @pytest.mark.parametrize("grid,N", [((30, 40), 24), ((32, 64), 20), ((30, 40), 12), ((16, 32), 80)])
