@@ -21,7 +21,7 @@
 // When that exceeds 160 KiB the activation planes move to a per-chain global workspace
 // (L2-resident); the code path is otherwise identical.
 #include "mvsn_chain.h"
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 #include "mvsn_conv_wino.h"
 
 namespace mvsn {
@@ -33,7 +33,6 @@ constexpr int W1_FLOATS = CH_W1_FLOATS;
 constexpr int SP_FLOATS = CH_SP_FLOATS;
 constexpr int PACKED_FLOATS = CH_PACKED_FLOATS;
 constexpr int RED_FLOATS = 4 * CH_WAVES * 4;
-constexpr float GN_EPS = 1e-5f;
 
 // ---------------------------------------------------------------------------------------------
 // weight packing
@@ -240,7 +239,7 @@ __device__ __forceinline__ void groupnorm_lrelu(floatx4 (&acc)[TP][2], const boo
   block_group_sum(q, red_b, lane, wave);
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const float rstd = 1.0f / sqrtf(q[t] * inv_count + GN_EPS);
+    const float rstd = 1.0f / sqrtf(q[t] * inv_count + MVSN_GN_EPS);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = t * 16 + cbase + r;

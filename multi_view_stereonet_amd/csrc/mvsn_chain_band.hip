@@ -54,12 +54,11 @@
 #include <type_traits>
 
 #include "mvsn_chain.h"
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 
 namespace mvsn {
 
 constexpr int CB_THREADS = 256, CB_WAVES = 4;
-constexpr float CB_GN_EPS = 1e-5f;
 constexpr unsigned CB_SPIN_LIMIT = 1u << 21;
 
 template <int ROWS, int COLS, int BR_, int W_, int CSA_, bool HS_ = false>
@@ -100,17 +99,7 @@ typedef BandGeo<16, 32, 2, 3, 160, true> Band16x32H;   // 8 bands of 2 rows, hal
 typedef BandGeo<30, 40, 2, 3, 168> Band30x40;
 typedef BandGeo<32, 64, 2, 1, 264> Band32x64;
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef float float2v __attribute__((ext_vector_type(2)));
 typedef int intx2 __attribute__((ext_vector_type(2)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-#define CB_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define CB_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define CB_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
-
-__device__ __forceinline__ void cb_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Two neighbouring granules (16-byte aligned pair) in ONE write-through store: half the fabric writes of a publish.
 // Each 8-byte half is still a self-contained {value, tag} granule for the reader (8-byte halves of a 16-byte sc1
@@ -127,123 +116,38 @@ __device__ __forceinline__ void cb_publish2(gu64 *g, unsigned tag, float v0, flo
 template <int N, class Addr>
 __device__ __forceinline__ void cb_sweep(Addr addr, unsigned tag, bool active, float (&v)[N], bool &dead, gu32 *status,
                                          unsigned spin_limit) {
-  for (unsigned spins = 0;; ++spins) {
-    bool ok = true;
-    if (active) {
+  poll_granules(
+      [&](unsigned) {
+        bool ok = true;
+        if (active) {
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        const u64 x = __hip_atomic_load(addr(j), CB_RLX_AGENT);
-        v[j] = __builtin_bit_cast(float, (unsigned)x);
-        ok &= (unsigned)(x >> 32) == tag;
-      }
-    }
-    if (__all(ok) || dead) return;
-    if (spins >= spin_limit) {
-      dead = true;
-      __hip_atomic_store(status, 1u, CB_RLX_AGENT);
-      return;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
+          for (int j = 0; j < N; ++j) {
+            const u64 x = __hip_atomic_load(addr(j), MVSN_RLX_AGENT);
+            v[j] = __builtin_bit_cast(float, (unsigned)x);
+            ok &= (unsigned)(x >> 32) == tag;
+          }
+        }
+        return ok;
+      },
+      dead, status, 1u, spin_limit);
 }
 
-// one 3x3 layer for ONE cout tile: acc[xi] (+)= U_xi * V_xi over NC k-steps, then the output transform
-// (wino_layer of mvsn_chain_wino.hip with the cout-tile dimension dealt to the waves).  The pinned order -- transform,
-// then the eight multiplies back to back -- is the measured best: interleaving the next k-step's transform with the
-// multiplies (one wave per SIMD has nobody else to fill the pipe) took 24.2 us per step against 22.8 (HISTORY 3.6).
-// HSEL = -1: both transform-row halves (y = half 0's outputs + half 1's); 0 / 1: that half alone (y = its outputs; the
-// caller adds the two waves' results in the same order, so the sum is bit for bit the one-wave form's).
+// one 3x3 layer for ONE cout tile `ct` (f23_resident_layer, mvsn_resident.h, with the cout-tile dimension dealt to the
+// waves).  The pinned order -- transform, then the eight multiplies back to back -- is the measured best: interleaving
+// the next k-step's transform with the multiplies (one wave per SIMD has nobody else to fill the pipe) took 24.2 us per
+// step against 22.8 (HISTORY 3.6).  HSEL: the half split, see there.
 template <int NC, int CSA, int RS, int HSEL = -1>
 __device__ __forceinline__ void band_layer(const float *__restrict__ act, const float *__restrict__ U, int ct, int wb,
-                                           int lane, float (&y)[4][4]) {
+                                           int lane, float (&y)[1][4][4]) {
   const float *wbase = act + (lane >> 4) * CSA + wb;
   const float *ub = U + ct * 1024 + lane * 4;
+  f23_resident_layer<NC, 1, HSEL>(
+      [&](int half, int c4, float (&d)[3][4]) { window_rows(wbase + c4 * 4 * CSA + half * RS, RS, d); },
+      [&](int half, int c4, floatx4 (&u)[2]) {
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    if (HSEL >= 0 && half != HSEL) continue;
-    floatx4 acc[8];
-    float d[2][3][4];
-    floatx4 u[2][2];
-    auto fetch = [&](int buf, int c4) {
-      const float *wp = wbase + c4 * 4 * CSA + half * RS;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const float2 lo = *reinterpret_cast<const float2 *>(wp + i * RS);
-        const float2 hi = *reinterpret_cast<const float2 *>(wp + i * RS + 2);
-        d[buf][i][0] = lo.x, d[buf][i][1] = lo.y, d[buf][i][2] = hi.x, d[buf][i][3] = hi.y;
-      }
-#pragma unroll
-      for (int xq = 0; xq < 2; ++xq)
-        u[buf][xq] = *reinterpret_cast<const floatx4 *>(ub + (c4 * 8 + half * 2 + xq) * 256);
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int c4 = 0; c4 < NC; ++c4) {
-      const int cur = c4 & 1;
-      float t[2][4], v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (half == 0) {
-          t[0][j] = d[cur][0][j] - d[cur][2][j];
-          t[1][j] = d[cur][1][j] + d[cur][2][j];
-        } else {
-          t[0][j] = d[cur][1][j] - d[cur][0][j];
-          t[1][j] = d[cur][0][j] - d[cur][2][j];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        v[i * 4 + 0] = t[i][0] - t[i][2];
-        v[i * 4 + 1] = t[i][1] + t[i][2];
-        v[i * 4 + 2] = t[i][2] - t[i][1];
-        v[i * 4 + 3] = t[i][1] - t[i][3];
-      }
-      if (c4 + 1 < NC) fetch(cur ^ 1, c4 + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int xq = 0; xq < 2; ++xq)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const floatx4 c0 = c4 == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[xq * 4 + j];
-          acc[xq * 4 + j] = mfma16x16x4(u[cur][xq][j], v[xq * 4 + j], c0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float s0[4], s1[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (half == 0) {
-          s0[j] = acc[j][r] + acc[4 + j][r];
-          s1[j] = acc[4 + j][r];
-        } else {
-          s0[j] = acc[j][r];
-          s1[j] = -acc[j][r] - acc[4 + j][r];
-        }
-      }
-      const float y0 = s0[0] + s0[1] + s0[2], y1 = s0[1] - s0[2] - s0[3];
-      const float y2 = s1[0] + s1[1] + s1[2], y3 = s1[1] - s1[2] - s1[3];
-      if (half == 0 || HSEL == 1) y[r][0] = y0, y[r][1] = y1, y[r][2] = y2, y[r][3] = y3;
-      else y[r][0] += y0, y[r][1] += y1, y[r][2] += y2, y[r][3] += y3;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// sums of two values over the 32 lanes of each half-wave; the totals land in lanes 16..31 / 48..63
-__device__ __forceinline__ void cb_half_wave_sums(float (&s)[2]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0xB1>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x4E>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x141>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x140>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    s[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s[k]), 0x142, 0xA, 0xF, false));
+        for (int xq = 0; xq < 2; ++xq) u[xq] = *reinterpret_cast<const floatx4 *>(ub + (c4 * 8 + half * 2 + xq) * 256);
+      },
+      y);
 }
 
 // wave-wide min / max of two ints (DPP within the 16-lane rows, then the four rows through scalar registers)
@@ -303,8 +207,8 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     const int runs = nchunks * (CW_UCHUNK / 256);
     const char *base = reinterpret_cast<const char *>(src + (size_t)wave * 256);
     for (int run = wave, i = 0; run < runs; run += CB_WAVES, ++i)
-      __builtin_amdgcn_global_load_lds(CB_GPTR(base + (size_t)i * (CB_WAVES * 1024) + (unsigned)lane16),
-                                       CB_LPTR(U + run * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(MVSN_GPTR(base + (size_t)i * (CB_WAVES * 1024) + (unsigned)lane16),
+                                       MVSN_LPTR(U + run * 256), 16, 0, 0);
   };
   auto dma_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
 
@@ -496,7 +400,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     }
   };
   if (D > 1) prepare(1);
-  cb_barrier();   // step 1's row range is complete; plane 0 sits in the window
+  lds_barrier();   // step 1's row range is complete; plane 0 sits in the window
 
   // ---- the recurrence ------------------------------------------------------------------------
   for (int d = 1; d < D; ++d) {
@@ -543,7 +447,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
 #pragma unroll
               for (int j = 0; j < GEO::FROW; ++j) {
                 const int i = tid + CB_THREADS * j, c = i / cols, x = i - c * cols;
-                const u64 xv = __hip_atomic_load(g + (size_t)c * P + x, CB_RLX_AGENT);
+                const u64 xv = __hip_atomic_load(g + (size_t)c * P + x, MVSN_RLX_AGENT);
                 v[s][j] = __builtin_bit_cast(float, (unsigned)xv);
                 ok &= (unsigned)(xv >> 32) == (unsigned)d;
               }
@@ -551,7 +455,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
           if (__all(ok) || dead) break;
           if (spins >= spin_limit) {
             dead = true;
-            __hip_atomic_store(status, 2u, CB_RLX_AGENT);
+            __hip_atomic_store(status, 2u, MVSN_RLX_AGENT);
             break;
           }
           __builtin_amdgcn_s_sleep(1);
@@ -568,7 +472,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
       }
       footprints();
       CB_STAMP(2);
-      cb_barrier();   // B2: window complete
+      lds_barrier();   // B2: window complete
       // A2 gather.  The +1 column tap is read unclamped: where the clamp would act its weight is exactly zero and the
       // slot read is the zero halo column; the +1 row tap re-reads row y0 there (weight exactly zero as well).
 #pragma unroll
@@ -625,7 +529,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
           }
         }
       }
-      cb_barrier();   // (keeps the barrier count of the two paths equal)
+      lds_barrier();   // (keeps the barrier count of the two paths equal)
     }
     if (tid == 0) range[par * 2] = 1 << 20, range[par * 2 + 1] = -1;   // (read by everyone before B2; next use: step d+2)
     CB_STAMP(3);
@@ -656,7 +560,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
       }
     }
     dma_landed();   // conv0's U
-    cb_barrier();   // B3
+    lds_barrier();   // B3
     CB_STAMP(4);
 
     float y[4][4] = {};
@@ -665,14 +569,14 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     auto layer = [&](auto nc) {
       constexpr int NC = decltype(nc)::value;
       if constexpr (HS) {
-        if (hsel == 0) band_layer<NC, CSA, RS, 0>(act, U, ct, wb, lane, y);
-        else band_layer<NC, CSA, RS, 1>(act, U, ct, wb, lane, y);
+        if (hsel == 0) band_layer<NC, CSA, RS, 0>(act, U, ct, wb, lane, reinterpret_cast<float (&)[1][4][4]>(y));
+        else band_layer<NC, CSA, RS, 1>(act, U, ct, wb, lane, reinterpret_cast<float (&)[1][4][4]>(y));
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           *reinterpret_cast<floatx4 *>(comb + (((hsel * 2 + ct) * 4 + r) * 64 + lane) * 4) =
               floatx4{y[r][0], y[r][1], y[r][2], y[r][3]};
       } else {
-        if (tile_live) band_layer<NC, CSA, RS>(act, U, ct, wb, lane, y);
+        if (tile_live) band_layer<NC, CSA, RS>(act, U, ct, wb, lane, reinterpret_cast<float (&)[1][4][4]>(y));
       }
     };
     auto combine = [&]() {
@@ -686,7 +590,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     };
     layer(std::integral_constant<int, 9>{});
     CB_STAMP(5);
-    cb_barrier();   // B4: act and U free
+    lds_barrier();   // B4: act and U free
     dma_u(upk + CW_U0_FLOATS, 8);
     combine();
 
@@ -712,7 +616,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
         }
       }
       if (!sum_owner) s[0] = s[1] = 0.f;
-      cb_half_wave_sums(s);
+      half_wave_sums(s);
       gu64 *Sl = Sg + (size_t)layer * (G * CB_WAVES * 4);
       if ((lane & 31) == 16) {
         gu64 *g = Sl + (m * CB_WAVES + wave) * 4 + (lane >> 5) * 2;
@@ -742,7 +646,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
         for (unsigned spins = 0;; ++spins) {
           bool ok = true;
           if (sum_role) {
-            const u64 x = __hip_atomic_load(Sl + tid0, CB_RLX_AGENT);
+            const u64 x = __hip_atomic_load(Sl + tid0, MVSN_RLX_AGENT);
             sv = __builtin_bit_cast(float, (unsigned)x);
             ok &= (unsigned)(x >> 32) == (unsigned)d;
           }
@@ -753,7 +657,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
               const gu64 *g = Rl + ((size_t)((hs[it] ? m + 1 : m - 1) * 2 + (hs[it] ? 0 : 1)) * 32 + hcg[it] * 8) * cols + hx[it];
 #pragma unroll
               for (int j = 0; j < 8; ++j) {
-                const u64 x = __hip_atomic_load(g + j * cols, CB_RLX_AGENT);
+                const u64 x = __hip_atomic_load(g + j * cols, MVSN_RLX_AGENT);
                 hr[it][j] = __builtin_bit_cast(float, (unsigned)x);
                 ok &= (unsigned)(x >> 32) == (unsigned)d;
               }
@@ -761,7 +665,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
           if (__all(ok) || dead) break;
           if (spins >= spin_limit) {
             dead = true;
-            __hip_atomic_store(status, 3u + layer, CB_RLX_AGENT);
+            __hip_atomic_store(status, 3u + layer, MVSN_RLX_AGENT);
             break;
           }
           __builtin_amdgcn_s_sleep(1);
@@ -769,7 +673,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
         if (sum_role) red[tid0] = sv;
       }
       CB_STAMP(18 + layer * 4);
-      cb_barrier();
+      lds_barrier();
       // totals in a fixed order: every workgroup of the chain forms the same statistics bit for bit
       float own_mean, own_rstd, h_mean[HI], h_rstd[HI];
       if constexpr (G <= 4 || HS) {
@@ -789,7 +693,7 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
           const float ms = s1 * inv_n;
           const float var = fmaxf(s2 * inv_n - ms * ms, 0.0f);
           mean = sh + ms;
-          rstd = 1.0f / sqrtf(var + CB_GN_EPS);
+          rstd = 1.0f / sqrtf(var + MVSN_GN_EPS);
         };
         stats_of(gown, shift, own_mean, own_rstd);
 #pragma unroll
@@ -820,10 +724,10 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
             const float ms = s2v[0] * inv_n;
             const float var = fmaxf(s2v[1] * inv_n - ms * ms, 0.0f);
             gs[g * 2] = gs[g * 2] + ms;                         // mean = shift + E[x - shift]
-            gs[g * 2 + 1] = 1.0f / sqrtf(var + CB_GN_EPS);
+            gs[g * 2 + 1] = 1.0f / sqrtf(var + MVSN_GN_EPS);
           }
         }
-        cb_barrier();
+        lds_barrier();
         own_mean = gs[gown * 2], own_rstd = gs[gown * 2 + 1];
 #pragma unroll
         for (int it = 0; it < HI; ++it) h_mean[it] = gs[hcg[it] * 2], h_rstd[it] = gs[hcg[it] * 2 + 1];
@@ -864,12 +768,12 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     exchange(0, bias0, gn0w, gn0b, false, [] {});
     CB_STAMP(6);
     dma_landed();
-    cb_barrier();   // B6
+    lds_barrier();   // B6
     CB_STAMP(7);
 
     layer(std::integral_constant<int, 8>{});
     CB_STAMP(8);
-    cb_barrier();   // B7
+    lds_barrier();   // B7
     dma_u(upk + CW_U0_FLOATS + CW_U1_FLOATS, 8);
     combine();
     exchange(1, bias1, gn1w, gn1b, true, [&] {   // x2 = x1 + LReLU(GN(conv1(x1)))
@@ -877,14 +781,14 @@ __global__ __launch_bounds__(CB_THREADS) void chain_band_kernel(ChainArgs a, int
     });
     CB_STAMP(9);
     dma_landed();
-    cb_barrier();   // B10
+    lds_barrier();   // B10
     CB_STAMP(10);
 
     layer(std::integral_constant<int, 8>{});
     float2 fl[4][2] = {};
     load_left(fl);
     CB_STAMP(11);
-    cb_barrier();   // B11
+    lds_barrier();   // B11
     dma_u(upk, 9);  // conv0 of the next step
     combine();
 

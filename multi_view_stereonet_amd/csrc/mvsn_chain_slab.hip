@@ -32,12 +32,11 @@
 //               weights)
 // 32x64: 65,536 + 896 + 96 + 2,048 + 35 x 672 x 4 = 162,656 bytes of the 163,840.
 #include "mvsn_chain.h"
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 
 namespace mvsn {
 
 constexpr int SB_THREADS = 512, SB_WAVES = 8;
-constexpr float SB_GN_EPS = 1e-5f;
 constexpr unsigned SB_SPIN_LIMIT = 1u << 21;
 #ifndef MVSN_SB_ABLATE   // tuning aid (wrong results): 1 no U DMA in the step loop, 2 no gather plan, 4 hand-off polls return at once
 #define MVSN_SB_ABLATE 0
@@ -73,24 +72,13 @@ typedef SlabGeo<30, 40, 3, 544> Slab30x40;
 typedef SlabGeo<32, 64, 4, 672> Slab32x64;
 typedef SlabGeo<16, 32, 2, 352> Slab16x32;    // (tests: the plane-resident kernel's grid on two workgroups)
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef float sb_float2v __attribute__((ext_vector_type(2)));
-typedef unsigned sb_uintx4 __attribute__((ext_vector_type(4)));
-#define SB_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define SB_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define SB_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
-
-__device__ __forceinline__ void sb_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Two neighbouring granules in one 16-byte write-through store (see cb_publish2, mvsn_chain_band.hip), addressed as
 // scalar base + 32-bit lane offset + immediate: no 64-bit address arithmetic in vector registers (with 512 threads a wave
 // has 256 of them, and the addresses of a hand-off's sixteen stores, hoisted out of the step loop, were what spilled).
 template <int OFF>
 __device__ __forceinline__ void sb_publish2(const gu64 *base, unsigned voff_bytes, unsigned tag, float v0, float v1) {
   static_assert(OFF >= 0 && OFF < 4096, "13-bit signed immediate");
-  sb_uintx4 q;
+  uintx4 q;
   q[0] = __builtin_bit_cast(unsigned, v0), q[1] = tag, q[2] = __builtin_bit_cast(unsigned, v1), q[3] = tag;
   asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" ::"v"(voff_bytes), "v"(q), "s"(base), "n"(OFF) : "memory");
 }
@@ -112,31 +100,27 @@ template <int N, int STRIDE>
 __device__ __forceinline__ void sb_sweep(const gu64 *base, unsigned off, unsigned tag, bool active, float (&v)[N], bool &dead,
                                          gu32 *status, unsigned code, unsigned spin_limit) {
   const unsigned voff = off * 8u;
-  for (unsigned spins = 0;; ++spins) {
-    bool ok = true;
-    if ((MVSN_SB_ABLATE & 4) && spins > 0) return;
-    if (active) {
-      u64 x[N];
-      sb_issue<0, N, STRIDE>(base, voff, x);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  poll_granules(
+      [&](unsigned spins) {
+        bool ok = true;
+        if ((MVSN_SB_ABLATE & 4) && spins > 0) return true;
+        if (active) {
+          u64 x[N];
+          sb_issue<0, N, STRIDE>(base, voff, x);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        asm volatile("" : "+v"(x[j]));
-        v[j] = __builtin_bit_cast(float, (unsigned)x[j]);
-        ok &= (unsigned)(x[j] >> 32) == tag;
-      }
-    }
-    if (__all(ok) || dead) return;
-    if (spins >= spin_limit) {
-      dead = true;
-      __hip_atomic_store(status, code, SB_RLX_AGENT);
-      return;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
+          for (int j = 0; j < N; ++j) {
+            asm volatile("" : "+v"(x[j]));
+            v[j] = __builtin_bit_cast(float, (unsigned)x[j]);
+            ok &= (unsigned)(x[j] >> 32) == tag;
+          }
+        }
+        return ok;
+      },
+      dead, status, code, spin_limit);
 }
 
-// One 3x3 layer (wino_layer of mvsn_chain_wino.hip; the U blocks by (transform-row half, k-step): block s = half * NC + c4
+// One 3x3 layer (f23_resident_layer, mvsn_resident.h; the U blocks by (transform-row half, k-step): block s = half * NC + c4
 // sits in LDS slot s while s < SB_USLOTS, the others -- conv0's last two -- come from L2 straight into the registers the
 // LDS reads would fill, fetched one k-step ahead like them).  `ug` = the layer's U in global memory (chain_wino layout:
 // [k-step][cout tile][xi quad][lane][4]).
@@ -146,111 +130,33 @@ __device__ __forceinline__ void slab_layer(const float *__restrict__ act, const 
   // conv0: channel 4 * 8 + 3 = 35 is the K padding (zero weights): its lane re-reads plane 34
   const float *wbase = act + (lane >> 4) * CSA + wb;
   const float *ub = U + lane * 4;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    floatx4 acc[2][8];
-    float d[2][3][4];
-    floatx4 u[2][4];
-    auto fetch = [&](int buf, int c4) {
-      const float *wp = wbase + c4 * 4 * CSA + half * RS;
-      if constexpr (NC == 9) {
-        if (c4 == 8) {   // (formed here, from an opaque copy of the lane id: as a fourth base address held across the layer it spilled)
-          int kk = lane;
-          asm volatile("" : "+v"(kk));
-          wp -= (kk >> 4) == 3 ? CSA : 0;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const float2 lo = *reinterpret_cast<const float2 *>(wp + i * RS);
-        const float2 hi = *reinterpret_cast<const float2 *>(wp + i * RS + 2);
-        d[buf][i][0] = lo.x, d[buf][i][1] = lo.y, d[buf][i][2] = hi.x, d[buf][i][3] = hi.y;
-      }
-      const int s = half * NC + c4;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq) {
-          if (s < SB_USLOTS) u[buf][ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + s * 1024 + (ct * 2 + xq) * 256);
-          else   // (buffer descriptor + lane offset + scalar offset: the eight addresses are never vector registers)
-            u[buf][ct * 2 + xq] = __builtin_bit_cast(
-                floatx4, __builtin_amdgcn_raw_buffer_load_b128(
-                             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ug), 0, NC * CW_UCHUNK * 4, 0x00020000),
-                             lane * 16, ((c4 * 2 + ct) * 4 + half * 2 + xq) * 1024, 0));
-        }
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int c4 = 0; c4 < NC; ++c4) {
-      const int cur = c4 & 1;
-      float t[2][4], v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (half == 0) {
-          t[0][j] = d[cur][0][j] - d[cur][2][j];
-          t[1][j] = d[cur][1][j] + d[cur][2][j];
-        } else {
-          t[0][j] = d[cur][1][j] - d[cur][0][j];
-          t[1][j] = d[cur][0][j] - d[cur][2][j];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        v[i * 4 + 0] = t[i][0] - t[i][2];
-        v[i * 4 + 1] = t[i][1] + t[i][2];
-        v[i * 4 + 2] = t[i][2] - t[i][1];
-        v[i * 4 + 3] = t[i][1] - t[i][3];
-      }
-      if (c4 + 1 < NC) fetch(cur ^ 1, c4 + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const floatx4 c0 = c4 == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ct][xq * 4 + j];
-            acc[ct][xq * 4 + j] = mfma16x16x4(u[cur][ct * 2 + xq][j], v[xq * 4 + j], c0);
-          }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s0[4], s1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (half == 0) {
-            s0[j] = acc[ct][j][r] + acc[ct][4 + j][r];
-            s1[j] = acc[ct][4 + j][r];
-          } else {
-            s0[j] = acc[ct][j][r];
-            s1[j] = -acc[ct][j][r] - acc[ct][4 + j][r];
+  f23_resident_layer<NC, 2>(
+      [&](int half, int c4, float (&d)[3][4]) {
+        const float *wp = wbase + c4 * 4 * CSA + half * RS;
+        if constexpr (NC == 9) {
+          if (c4 == 8) {   // (formed here, from an opaque copy of the lane id: as a fourth base address held across the layer it spilled)
+            int kk = lane;
+            asm volatile("" : "+v"(kk));
+            wp -= (kk >> 4) == 3 ? CSA : 0;
           }
         }
-        const float y0 = s0[0] + s0[1] + s0[2], y1 = s0[1] - s0[2] - s0[3];
-        const float y2 = s1[0] + s1[1] + s1[2], y3 = s1[1] - s1[2] - s1[3];
-        if (half == 0) y[ct][r][0] = y0, y[ct][r][1] = y1, y[ct][r][2] = y2, y[ct][r][3] = y3;
-        else y[ct][r][0] += y0, y[ct][r][1] += y1, y[ct][r][2] += y2, y[ct][r][3] += y3;
-      }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// sums of four values over the 32 lanes of each half-wave; totals in lanes 16..31 / 48..63 (chain_wino: half_wave_sums)
-__device__ __forceinline__ void sb_half_wave_sums(float (&s)[4]) {
+        window_rows(wp, RS, d);
+      },
+      [&](int half, int c4, floatx4 (&u)[4]) {
+        const int s = half * NC + c4;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0xB1>(s[k]);
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x4E>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x141>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x140>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    s[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s[k]), 0x142, 0xA, 0xF, false));
+          for (int xq = 0; xq < 2; ++xq) {
+            if (s < SB_USLOTS) u[ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + s * 1024 + (ct * 2 + xq) * 256);
+            else   // (buffer descriptor + lane offset + scalar offset: the eight addresses are never vector registers)
+              u[ct * 2 + xq] = __builtin_bit_cast(
+                  floatx4, __builtin_amdgcn_raw_buffer_load_b128(
+                               __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ug), 0, NC * CW_UCHUNK * 4, 0x00020000),
+                               lane * 16, ((c4 * 2 + ct) * 4 + half * 2 + xq) * 1024, 0));
+          }
+      },
+      y);
 }
 
 template <class GEO, bool C16 = false>   // C16: the cost volume stored as bf16 (ChainArgs::cost_bf16, the bf16 feature tier)
@@ -297,7 +203,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
       const int s = i >> 2, r = i & 3, half = s >= nc ? 1 : 0, c4 = s - half * nc;
       const int run = (c4 * 2 + (r >> 1)) * 4 + half * 2 + (r & 1);
       const char *g = reinterpret_cast<const char *>(src + (size_t)run * 256);
-      __builtin_amdgcn_global_load_lds(SB_GPTR(g + (unsigned)l16), SB_LPTR(U + i * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(MVSN_GPTR(g + (unsigned)l16), MVSN_LPTR(U + i * 256), 16, 0, 0);
     }
   };
   auto dma_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
@@ -547,7 +453,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
       }
     }
     SB_STAMP(1);
-    sb_barrier();   // Ba: F_{d-1} complete on rows lo-1 .. hi+1 (own rows: the previous step's epilogue)
+    lds_barrier();   // Ba: F_{d-1} complete on rows lo-1 .. hi+1 (own rows: the previous step's epilogue)
     SB_STAMP(2);
 
     // A2: previous plane's features moved by the incremental homography
@@ -603,7 +509,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
                 float acc = 0.f;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                  const u64 x = __hip_atomic_load(Fg + (base + (unsigned)(r * P) + ((t & 1) ? dx : 0u) + ((t & 2) ? dy : 0u)), SB_RLX_AGENT);
+                  const u64 x = __hip_atomic_load(Fg + (base + (unsigned)(r * P) + ((t & 1) ? dx : 0u) + ((t & 2) ? dy : 0u)), MVSN_RLX_AGENT);
                   ok &= (unsigned)(x >> 32) == (unsigned)d;
                   acc += __builtin_bit_cast(float, (unsigned)x) * w[t];
                 }
@@ -613,7 +519,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
             if (__all(ok) || dead) break;
             if (spins >= spin_limit) {
               dead = true;
-              __hip_atomic_store(status, 1u, SB_RLX_AGENT);
+              __hip_atomic_store(status, 1u, MVSN_RLX_AGENT);
               break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -636,7 +542,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
     // E1b (publish): the band's boundary rows of the moved features are the neighbours' conv0 halo rows
     publish_rows(lane_geo(), GEO::E1B, (unsigned)d, fp);
     SB_STAMP(3);
-    sb_barrier();   // B1: every gather of plane d-1 is done
+    lds_barrier();   // B1: every gather of plane d-1 is done
     SB_STAMP(4);
 
     // A3: lay out the refiner input [image(3) | moved features(32)] on rows lo-1 .. hi+1
@@ -675,7 +581,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
     }
     dma_landed();   // conv0's U
     SB_STAMP(5);
-    sb_barrier();   // B2
+    lds_barrier();   // B2
     SB_STAMP(6);
 
     float y[2][4][4] = {};
@@ -707,7 +613,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
         }
       }
       if (!(pvalid && tile_live)) s[0] = s[1] = s[2] = s[3] = 0.f;
-      sb_half_wave_sums(s);
+      half_wave_sums(s);
       const gu64 *Sl = ws + GEO::SG + (size_t)layer * (NB * 64);
       if ((lane_s & 31) == 16) {   // record of (wave, group = ct * 2 + half-wave): [sum, sum of squares]
         const unsigned g8 = (unsigned)(m * 64 + wave * 8 + (lane_s >> 5) * 2) * 8u;
@@ -716,7 +622,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
       }
       publish_rows(L, region, (unsigned)d, y);
       SB_STAMP(16 + layer * 4);
-      sb_barrier();   // B3 / B7: planes and U free
+      lds_barrier();   // B3 / B7: planes and U free
       // (issued in front of the hand-off's polling loads; behind them measured the same: profiles/r05_slab/README.md)
       dma_u(upk + (layer == 0 ? CW_U0_FLOATS : CW_U0_FLOATS + CW_U1_FLOATS), 8);
       meanwhile();    // work that needs none of the hand-off, placed where the workgroup would otherwise only wait
@@ -746,7 +652,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
         const float ms = s1 * inv_n;
         const float var = fmaxf(s2 * inv_n - ms * ms, 0.0f);
         mean = sh + ms;
-        rstd = 1.0f / sqrtf(var + SB_GN_EPS);
+        rstd = 1.0f / sqrtf(var + MVSN_GN_EPS);
       };
       // (the shuffles are wave-wide: every lane takes part, with or without a patch)
 #pragma unroll
@@ -796,7 +702,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
     const float nm0 = exchange(0, GEO::E2, bias0, gn0w, gn0b, false, [] {});
     SB_STAMP(8);
     dma_landed();
-    sb_barrier();   // B6
+    lds_barrier();   // B6
     if (wave == 0 && lane_s < 4) gstat[lane_s] = nm0;
     SB_STAMP(9);
 
@@ -808,7 +714,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
     });
     SB_STAMP(11);
     dma_landed();
-    sb_barrier();   // B10
+    lds_barrier();   // B10
     if (wave == 0 && lane_s < 4) gstat[4 + lane_s] = nm1;
     SB_STAMP(12);
 
@@ -827,7 +733,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
         for (int a2 = 0; a2 < 2; ++a2)
           fl[ct][r][a2] = *reinterpret_cast<const float2 *>(fl_lane + (size_t)(ct * 16 + r) * P + a2 * cols);
     SB_STAMP(13);
-    sb_barrier();   // B11: planes and U free
+    lds_barrier();   // B11: planes and U free
     dma_u(upk, 9);  // conv0 of the next step
     const bool next_slow = (fastw[par ^ 1] != 0 || (flags & 1)) && d + 1 < D;   // (complete since B10)
     if (tid == 0) fastw[par] = 0;   // (read by everyone at the top of this step; next written during step d + 1)
@@ -873,7 +779,7 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
             cost_t *cdst = cd + ((ct * 16 + r) * D) * P + slice_off;
 #pragma unroll
             for (int a2 = 0; a2 < 2; ++a2) {
-              sb_float2v c2;
+              float2v c2;
               c2.x = out[a2 * 2] ? 0.0f : fabsf(fl[ct][r][a2].x - f[a2 * 2]);
               c2.y = out[a2 * 2 + 1] ? 0.0f : fabsf(fl[ct][r][a2].y - f[a2 * 2 + 1]);
               chain_cost_nt(cdst + a2 * cols, c2);
@@ -882,10 +788,10 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
               float *fdst = fd + ((ct * 16 + r) * D) * P + slice_off;
 #pragma unroll
               for (int a2 = 0; a2 < 2; ++a2) {
-                sb_float2v f2;
+                float2v f2;
                 f2.x = out[a2 * 2] ? 0.0f : f[a2 * 2];
                 f2.y = out[a2 * 2 + 1] ? 0.0f : f[a2 * 2 + 1];
-                __builtin_nontemporal_store(f2, reinterpret_cast<sb_float2v *>(fdst + a2 * cols));
+                __builtin_nontemporal_store(f2, reinterpret_cast<float2v *>(fdst + a2 * cols));
               }
             }
           }

@@ -32,22 +32,13 @@
 //                           ch 0..2 image plane d, ch 3..34 features, ch 35 zero (K padding).
 // 16x32: 18432 + 224 + 256 + 512 + 20842 floats = 161,064 bytes of the 163,840.
 #include "mvsn_chain.h"
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 
 namespace mvsn {
 
 constexpr int CW_THREADS = 512;
 constexpr int CW_WAVES = 8;
 constexpr int CW_RED_FLOATS = 2 * CW_WAVES * 4 * 4;
-constexpr float CW_GN_EPS = 1e-5f;
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-// Workgroup barrier that publishes LDS writes but leaves global loads / stores in flight (__syncthreads() also waits
-// for vmcnt(0): the cost-slice stores and the left-feature loads would be drained at every barrier of the step).
-__device__ __forceinline__ void cw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-#define CW_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define CW_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 static size_t chain_wino_lds_bytes(int rows, int cols) {
   const int P = rows * cols, RS = cols + 2, CS = (rows + 1) * RS;
@@ -61,129 +52,24 @@ bool chain_wino_supported(int rows, int cols) {
   return patches <= CW_WAVES * 16 && rows * cols <= 2 * CW_THREADS && chain_wino_lds_bytes(rows, cols) <= 160 * 1024;
 }
 
-// ---------------------------------------------------------------------------------------------
-// one 3x3 layer: acc[ct][xi] (+)= U_xi * V_xi over NC k-steps of 4 input channels, then the output transform
-// ---------------------------------------------------------------------------------------------
-// The 16 xi = (i, j) are walked in two halves by transform row i (i = 0,1 then i = 2,3): 64 accumulator registers
-// at a time instead of 128, each half's output transform folded into y as soon as its multiplies are done.  The
-// input transform costs the same (row i of B^T d B needs two rows of d), the window reads 3 rows per half.
-// Software pipeline per k-step: transform the window that is already in registers, issue the LDS reads of the NEXT
-// k-step (3 window rows + 4 quads of U), then the 16 multiplies -- no LDS round trip sits in front of an MFMA.
-// Measured (tools/chain_phases.py, s_memtime stamps per wave), 9 k-steps x 2 halves of the first layer:
-//   * one wave per SIMD alone: 730 cycles per k-step = 16 MFMAs x 32 + 23 VALU / LDS instructions x ~9.5;
-//   * two waves per SIMD (this kernel): 1405 per pair of k-steps -- the two waves leave their barrier together, run
-//     their transform sections together and then alternate on the matrix pipe, so the sections ADD instead of
-//     hiding under each other (73 % of the pipe); a raised priority for one wave of each pair starves the other
-//     instead (same total);
-//   * the next k-step's transform interleaved instruction by instruction with the multiplies (sched_group_barrier,
-//     MFMA / VALU alternating): 834 cycles per k-step for a wave alone, 7 % slower for the pair -- a VALU
-//     instruction between two fp32 MFMAs costs more than its slot.
-// The in-register transform costs one VALU per MFMA at 32 output channels; that ratio, not the schedule, is the limit.
+// one 3x3 layer (f23_resident_layer, mvsn_resident.h): the window from the activation planes (four ds_read2_b64), U
+// from the layer's LDS copy in the packed layout [k-step][cout tile][xi quad][lane][4 xi]
 template <int NC>
 __device__ __forceinline__ void wino_layer(const float *__restrict__ act, const float *__restrict__ U, int CS, int RS,
                                            int wb, int lane, float (&y)[2][4][4]) {
   const float *wbase = act + (lane >> 4) * CS + wb;
   const float *ub = U + lane * 4;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    floatx4 acc[2][8];
-    float d[2][3][4];
-    floatx4 u[2][4];
-    auto fetch = [&](int buf, int c4) {
+  f23_resident_layer<NC, 2>(
       // rows (half 0: 0,1,2; half 1: 1,2,3) of this lane's 4x4 window: rows 2pr-1 .. 2pr+2, columns 2pc-1 .. 2pc+2
-      const float *wp = wbase + c4 * 4 * CS + half * RS;
+      [&](int half, int c4, float (&d)[3][4]) { window_rows(wbase + c4 * 4 * CS + half * RS, RS, d); },
+      [&](int half, int c4, floatx4 (&u)[4]) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const float2 lo = *reinterpret_cast<const float2 *>(wp + i * RS);
-        const float2 hi = *reinterpret_cast<const float2 *>(wp + i * RS + 2);
-        d[buf][i][0] = lo.x, d[buf][i][1] = lo.y, d[buf][i][2] = hi.x, d[buf][i][3] = hi.y;
-      }
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq)
-          u[buf][ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + ((c4 * 2 + ct) * 4 + half * 2 + xq) * 256);
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int c4 = 0; c4 < NC; ++c4) {
-      const int cur = c4 & 1;
-      // V = B^T d B,  B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]]; rows i = 2*half, 2*half + 1
-      float t[2][4], v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (half == 0) {
-          t[0][j] = d[cur][0][j] - d[cur][2][j];   // d0 - d2
-          t[1][j] = d[cur][1][j] + d[cur][2][j];   // d1 + d2
-        } else {
-          t[0][j] = d[cur][1][j] - d[cur][0][j];   // d2 - d1
-          t[1][j] = d[cur][0][j] - d[cur][2][j];   // d1 - d3
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        v[i * 4 + 0] = t[i][0] - t[i][2];
-        v[i * 4 + 1] = t[i][1] + t[i][2];
-        v[i * 4 + 2] = t[i][2] - t[i][1];
-        v[i * 4 + 3] = t[i][1] - t[i][3];
-      }
-      if (c4 + 1 < NC) fetch(cur ^ 1, c4 + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const floatx4 c0 = c4 == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ct][xq * 4 + j];
-            acc[ct][xq * 4 + j] = mfma16x16x4(u[cur][ct * 2 + xq][j], v[xq * 4 + j], c0);
-          }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // Y = A^T m A,  A^T = [[1,1,1,0],[0,1,-1,-1]]: rows m0, m1 (half 0) / m2, m3 (half 1) of m enter
-    // s0 = m0 + m1 + m2 and s1 = m1 - m2 - m3; element r of acc[ct][xi] is cout ct*16 + (lane>>4)*4 + r
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s0[4], s1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (half == 0) {
-            s0[j] = acc[ct][j][r] + acc[ct][4 + j][r];
-            s1[j] = acc[ct][4 + j][r];
-          } else {
-            s0[j] = acc[ct][j][r];
-            s1[j] = -acc[ct][j][r] - acc[ct][4 + j][r];
-          }
-        }
-        const float y0 = s0[0] + s0[1] + s0[2], y1 = s0[1] - s0[2] - s0[3];
-        const float y2 = s1[0] + s1[1] + s1[2], y3 = s1[1] - s1[2] - s1[3];
-        if (half == 0) y[ct][r][0] = y0, y[ct][r][1] = y1, y[ct][r][2] = y2, y[ct][r][3] = y3;
-        else y[ct][r][0] += y0, y[ct][r][1] += y1, y[ct][r][2] += y2, y[ct][r][3] += y3;
-      }
-    // keep the halves apart: interleaved by the scheduler they hold all 128 accumulators at once, and whatever is
-    // live across the layer (moved features, left features) spills
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// Sums of four values at once over the 32 lanes of each half-wave (lanes 0..31 hold the channels of GroupNorm group
-// 2ct, lanes 32..63 of group 2ct+1).  Four DPP steps leave every lane of a 16-lane row with its row's sum;
-// row_bcast:15 then adds row 0 into row 1 and row 2 into row 3, so the half-wave sums sit in rows 1 and 3
-// (lanes 16..31 / 48..63) -- no LDS crossbar round trip (ds_bpermute) in the chain of dependent steps.
-__device__ __forceinline__ void half_wave_sums(float (&s)[4]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0xB1>(s[k]);    // quad_perm [1, 0, 3, 2]
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x4E>(s[k]);    // quad_perm [2, 3, 0, 1]
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x141>(s[k]);   // row_half_mirror
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] += dpp_mov<0x140>(s[k]);   // row_mirror
-#pragma unroll
-  for (int k = 0; k < 4; ++k)                                  // row_bcast:15 into rows 1 and 3 (row_mask 0xA)
-    s[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s[k]), 0x142, 0xA, 0xF, false));
+          for (int xq = 0; xq < 2; ++xq)
+            u[ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + ((c4 * 2 + ct) * 4 + half * 2 + xq) * 256);
+      },
+      y);
 }
 
 // y (+bias) -> LeakyReLU(GroupNorm(.)) in place, statistics over the whole workgroup, in two parts around the barrier
@@ -240,7 +126,7 @@ __device__ __forceinline__ void wino_groupnorm_apply(float (&y)[2][4][4], float 
     const float var = fmaxf(s2 * inv_n - ms * ms, 0.0f);
     const float mean = shift[ct] + ms;
     shift[ct] = mean;
-    const float rstd = 1.0f / sqrtf(var + CW_GN_EPS);
+    const float rstd = 1.0f / sqrtf(var + MVSN_GN_EPS);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = ct * 16 + cbase + r;
@@ -295,8 +181,8 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
     const int runs = nchunks * (CW_UCHUNK / 256);
     const char *base = reinterpret_cast<const char *>(src + (size_t)wave * 256);   // wave-uniform (SGPR pair)
     for (int run = wave, i = 0; run < runs; run += CW_WAVES, ++i)
-      __builtin_amdgcn_global_load_lds(CW_GPTR(base + (size_t)i * (CW_WAVES * 1024) + (unsigned)lane16),
-                                       CW_LPTR(U + run * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(MVSN_GPTR(base + (size_t)i * (CW_WAVES * 1024) + (unsigned)lane16),
+                                       MVSN_LPTR(U + run * 256), 16, 0, 0);
   };
   auto dma_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
 
@@ -473,7 +359,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
       }
     }
     CW_STAMP(1);
-    cw_barrier();  // B1: every gather of plane d-1 is done
+    lds_barrier();  // B1: every gather of plane d-1 is done
 #ifndef MVSN_CW_NO_HTOUCH
     asm volatile("" : "+s"(ht0), "+s"(ht1), "+s"(ht2), "+s"(ht3));   // (behind the barrier's s_waitcnt lgkmcnt(0))
 #endif
@@ -503,7 +389,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
       }
     }
     dma_landed();     // conv0's U (issued behind the previous step's conv2, or in the set-up)
-    cw_barrier();  // B2
+    lds_barrier();  // B2
     CW_STAMP(3);
 
     float y[2][4][4] = {};
@@ -512,7 +398,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
     wino_groupnorm_sums(y, pvalid && tile_live, shift0, bias0, red, lane_s, wave);
     CW_STAMP(4);
     CW_WSTAMP(1);
-    cw_barrier();  // B3: act and U free, GroupNorm records published
+    lds_barrier();  // B3: act and U free, GroupNorm records published
     CW_WSTAMP(2);
     dma_u(upk + CW_U0_FLOATS, 8);
     CW_WSTAMP(6);
@@ -531,14 +417,14 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
     CW_WSTAMP(3);
     dma_landed();
     CW_WSTAMP(4);
-    cw_barrier();  // B6
+    lds_barrier();  // B6
     CW_WSTAMP(5);
     CW_STAMP(6);
 
     if (tile_live) wino_layer<8>(act, U, CS, RS, wb, lane, y);
     wino_groupnorm_sums(y, pvalid && tile_live, shift1, bias1, red + CW_RED_FLOATS / 2, lane_s, wave);
     CW_STAMP(7);
-    cw_barrier();  // B7 (+ records)
+    lds_barrier();  // B7 (+ records)
     dma_u(upk + CW_U0_FLOATS + CW_U1_FLOATS, 8);
     CW_STAMP(8);
 
@@ -553,7 +439,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
         }
     }
     dma_landed();
-    cw_barrier();  // B10
+    lds_barrier();  // B10
     CW_STAMP(9);
 
     if (tile_live) wino_layer<8>(act, U, CS, RS, wb, lane, y);
@@ -566,7 +452,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
         for (int a2 = 0; a2 < 2; ++a2)
           fl[ct][r][a2] = *reinterpret_cast<const float2 *>(fl_lane + (size_t)(ct * 16 + r) * P + a2 * cols);
     CW_STAMP(10);
-    cw_barrier();  // B11
+    lds_barrier();  // B11
     dma_u(upk, 9);    // conv0 of the next step
     CW_STAMP(11);
 
@@ -610,7 +496,7 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
         }
     }
     CW_STAMP(12);
-    cw_barrier();  // B12
+    lds_barrier();  // B12
     CW_STAMP(13);
   }
 #undef CW_STAMP

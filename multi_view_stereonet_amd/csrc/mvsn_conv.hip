@@ -11,7 +11,7 @@
 //
 // LDS tile: [4 ch][HZ][HY][XS], channel stride CST = 16 (mod 32) -> the 16-column x 4-channel
 // fragment read is bank-conflict-free at stride 1.
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 #include "mvsn_conv_bf16x3.h"
 #include "mvsn_conv_wino.h"
 
@@ -556,8 +556,6 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_mfma_kernel(ConvGeom g, co
 // ---------------------------------------------------------------------------------------------
 __device__ floatx4 g_zero16 = {0.f, 0.f, 0.f, 0.f};
 
-#define MVSN_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define MVSN_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 template <int NPT, int KD, int IPC, int CT, int MODE>
 __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel(ConvGeom g, const float *__restrict__ in,

@@ -41,7 +41,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 #include "mvsn_conv_wino.h"
 
 namespace mvsn {
@@ -61,8 +61,6 @@ constexpr int WN_MAX_CHUNKS = 9;                       // resident U: up to 36 i
 constexpr int WN_LDS_MAX = 160 * 1024;                 // bytes of LDS a workgroup can have
 
 __device__ floatx4 g_wn_zero16 = {0.f, 0.f, 0.f, 0.f};
-#define WN_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define WN_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 #ifndef MVSN_WN_ABLATE   // tuning aid: bit 0 no input transform, 1 no U fragment reads, 2 no DMA in the loop, 3 no barrier, 4 no epilogue, 5 no raw reads, 6 no output stores
 #define MVSN_WN_ABLATE 0
@@ -214,10 +212,10 @@ __device__ __forceinline__ void wn_barrier() {
 template <bool ASM>
 __device__ __forceinline__ void wn_dma16(const float *g, const float *l) {
   if constexpr (ASM) {
-    const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)WN_LPTR(l));
+    const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)MVSN_LPTR(l));
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(la) : "memory", "m0");
   } else {
-    __builtin_amdgcn_global_load_lds(WN_GPTR(g), WN_LPTR(l), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(MVSN_GPTR(g), MVSN_LPTR(l), 16, 0, 0);
   }
 }
 // The same piece through a buffer descriptor (base = a channel plane, num_records = its bytes): lanes whose offset lies
@@ -234,7 +232,7 @@ __device__ __forceinline__ void wn_dma16_buf(const float *base, unsigned bytes, 
     srd[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
     srd[2] = __builtin_amdgcn_readfirstlane((int)bytes);
     srd[3] = 0x00020000;
-    const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)WN_LPTR(l));
+    const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)MVSN_LPTR(l));
 #if MVSN_WN_NT_RAW
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen nt lds" ::"v"(voff), "s"(srd), "s"(la)
                  : "memory", "m0");
@@ -244,7 +242,7 @@ __device__ __forceinline__ void wn_dma16_buf(const float *base, unsigned bytes, 
 #endif
   } else {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)bytes, 0x00020000),
-                                             WN_LPTR(l), 16, (int)voff, 0, 0, MVSN_WN_NT_RAW ? 2 : 0);
+                                             MVSN_LPTR(l), 16, (int)voff, 0, 0, MVSN_WN_NT_RAW ? 2 : 0);
   }
 }
 #pragma clang diagnostic pop

@@ -2,7 +2,7 @@
 // resize of idepth maps and hypothesis masks, multi-source fusion.
 #include <type_traits>
 
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 
 namespace mvsn {
 
@@ -490,7 +490,6 @@ namespace mvsn {
 //   B = 4 cins x 16 slots: lane (k, i) loads slots 64g + 4i .. + 3 of channel 4 ks + k with one dwordx4;
 //       register p of that load is the B fragment of "slot tile p" = slots {64g + 4i + p}, so the four
 //       accumulators of a lane are four CONSECUTIVE slots of one tap row -> one 16-byte LDS write.
-__device__ __forceinline__ void t3_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 constexpr int T3_TY = 16, T3_TX = 32;
 constexpr int T3_HY = T3_TY + 2, T3_XS = 40;          // haloed rows, row stride in slots
 constexpr int T3_SLOTS = T3_HY * T3_XS;               // 720
@@ -562,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void conv_to1_3d_mfma_kernel(const float *_
   }
   if constexpr (WHOLE) {   // halo slots of every tap row: zero, once
     for (int i = tid * 4; i < T3_LDS_FLOATS; i += 1024) *reinterpret_cast<floatx4 *>(P + i) = floatx4{0.f, 0.f, 0.f, 0.f};
-    t3_barrier();
+    lds_barrier();
   }
 
   // gather side: this thread's two output pixels (xx even)
@@ -645,7 +644,7 @@ __global__ __launch_bounds__(256, 2) void conv_to1_3d_mfma_kernel(const float *_
     if (z >= 0 && z < D) {   // uniform: planes outside the volume contribute nothing
       // ---- P = taps x slots for plane z
       plane_products(z);
-      t3_barrier();   // (LDS only: the next plane's first loads stay in flight across it)
+      lds_barrier();   // (LDS only: the next plane's first loads stay in flight across it)
       // ---- shift-and-add: input plane z feeds output planes z + 1 (dz = 0), z (dz = 1), z - 1 (dz = 2)
 #pragma unroll
       for (int dz = 0; dz < 3; ++dz)
@@ -666,7 +665,7 @@ __global__ __launch_bounds__(256, 2) void conv_to1_3d_mfma_kernel(const float *_
     acc[0][0] = acc[1][0], acc[0][1] = acc[1][1];
     acc[1][0] = acc[2][0], acc[1][1] = acc[2][1];
     acc[2][0] = 0.f, acc[2][1] = 0.f;
-    t3_barrier();   // everyone is done reading P before the next plane overwrites it
+    lds_barrier();   // everyone is done reading P before the next plane overwrites it
   }
 }
 

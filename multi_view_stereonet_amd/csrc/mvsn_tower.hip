@@ -25,7 +25,7 @@
 //
 // LDS (floats): U 18432 | params 96 x layers + tail | red 128 | planes 36 x 544 (pixel p at p, zero slot at 512;
 // channel c is skewed by one float when c & 2, so that the four channels of a k-step read disjoint bank sets).
-#include "mvsn_common.h"
+#include "mvsn_resident.h"
 
 namespace mvsn {
 
@@ -36,12 +36,7 @@ constexpr int TW_MAX_BLOCKS = 6;
 constexpr int TW_PARAMS = 96 * (TW_MAX_BLOCKS + 1) + 320;     // [bias | gamma | beta] per layer, then the tail's
 constexpr int TW_RED = 128;
 constexpr int TW_LDS_FLOATS = TW_UFLOATS + TW_PARAMS + TW_RED + 36 * TW_CS;
-constexpr float TW_GN_EPS = 1e-5f;
 
-#define TW_GPTR(p) ((const __attribute__((address_space(1))) void *)(p))
-#define TW_LPTR(p) ((__attribute__((address_space(3))) void *)(p))
-
-__device__ __forceinline__ void tw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ int tw_chan(int c) { return c * TW_CS + ((c >> 1) & 1); }
 
 struct TowerArgs {
@@ -61,101 +56,28 @@ struct TowerArgs {
   float *out;
 };
 
-// one 3x3 layer: acc[ct][xi] (+)= U_xi * V_xi over NC k-steps of 4 input channels; the window through `woff`
+// one 3x3 layer (f23_resident_layer, mvsn_resident.h); the window through `woff`, the channel planes through tw_chan
 template <int NC>
 __device__ __forceinline__ void tower_layer(const float *__restrict__ planes, const float *__restrict__ U,
                                             const int (&woff)[16], int lane, float (&y)[2][4][4]) {
   const int k = lane >> 4;
   const float *ub = U + lane * 4;
+  f23_resident_layer<NC, 2>(
+      [=, &woff](int half, int c4, float (&d)[3][4]) {
+        const float *cp = planes + tw_chan(c4 * 4 + k);
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    floatx4 acc[2][8];
-    float d[2][3][4];
-    floatx4 u[2][4];
-    auto fetch = [&](int buf, int c4) {
-      const float *cp = planes + tw_chan(c4 * 4 + k);
+        for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 4; ++j) d[i][j] = cp[woff[(half + i) * 4 + j]];
+      },
+      [=](int half, int c4, floatx4 (&u)[4]) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d[buf][i][j] = cp[woff[(half + i) * 4 + j]];
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq)
-          u[buf][ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + ((c4 * 2 + ct) * 4 + half * 2 + xq) * 256);
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int c4 = 0; c4 < NC; ++c4) {
-      const int cur = c4 & 1;
-      float t[2][4], v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (half == 0) {
-          t[0][j] = d[cur][0][j] - d[cur][2][j];
-          t[1][j] = d[cur][1][j] + d[cur][2][j];
-        } else {
-          t[0][j] = d[cur][1][j] - d[cur][0][j];
-          t[1][j] = d[cur][0][j] - d[cur][2][j];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        v[i * 4 + 0] = t[i][0] - t[i][2];
-        v[i * 4 + 1] = t[i][1] + t[i][2];
-        v[i * 4 + 2] = t[i][2] - t[i][1];
-        v[i * 4 + 3] = t[i][1] - t[i][3];
-      }
-      if (c4 + 1 < NC) fetch(cur ^ 1, c4 + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int xq = 0; xq < 2; ++xq)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const floatx4 c0 = c4 == 0 ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ct][xq * 4 + j];
-            acc[ct][xq * 4 + j] = mfma16x16x4(u[cur][ct * 2 + xq][j], v[xq * 4 + j], c0);
-          }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s0[4], s1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (half == 0) {
-            s0[j] = acc[ct][j][r] + acc[ct][4 + j][r];
-            s1[j] = acc[ct][4 + j][r];
-          } else {
-            s0[j] = acc[ct][j][r];
-            s1[j] = -acc[ct][j][r] - acc[ct][4 + j][r];
-          }
-        }
-        const float y0 = s0[0] + s0[1] + s0[2], y1 = s0[1] - s0[2] - s0[3];
-        const float y2 = s1[0] + s1[1] + s1[2], y3 = s1[1] - s1[2] - s1[3];
-        if (half == 0) y[ct][r][0] = y0, y[ct][r][1] = y1, y[ct][r][2] = y2, y[ct][r][3] = y3;
-        else y[ct][r][0] += y0, y[ct][r][1] += y1, y[ct][r][2] += y2, y[ct][r][3] += y3;
-      }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// sums of two values over the 32 lanes of each half-wave (totals in lanes 16..31 / 48..63)
-__device__ __forceinline__ void tw_half_wave_sums(float (&s)[2]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0xB1>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x4E>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x141>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) s[k] += dpp_mov<0x140>(s[k]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    s[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s[k]), 0x142, 0xA, 0xF, false));
+          for (int xq = 0; xq < 2; ++xq)
+            u[ct * 2 + xq] = *reinterpret_cast<const floatx4 *>(ub + ((c4 * 2 + ct) * 4 + half * 2 + xq) * 256);
+      },
+      y);
 }
 
 __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS10) {   // (MVSN_VIS10: mvsn_common.h)
@@ -173,8 +95,8 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
     const int runs = nchunks * 8;
     const char *base = reinterpret_cast<const char *>(src + (size_t)wave * 256);
     for (int run = wave, i = 0; run < runs; run += TW_WAVES, ++i)
-      __builtin_amdgcn_global_load_lds(TW_GPTR(base + (size_t)i * (TW_WAVES * 1024) + (unsigned)lane16),
-                                       TW_LPTR(U + run * 256), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(MVSN_GPTR(base + (size_t)i * (TW_WAVES * 1024) + (unsigned)lane16),
+                                       MVSN_LPTR(U + run * 256), 16, 0, 0);
   };
   auto dma_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
 
@@ -245,12 +167,12 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
           s[ct] += y[ct][r][e];
         }
       }
-    tw_half_wave_sums(s);
+    half_wave_sums(s);
     if ((lane & 31) == 16) {
       red[(wave * 4 + 0 + (lane >> 5)) * 1] = s[0];          // group ct*2 + half
       red[(wave * 4 + 2 + (lane >> 5)) * 1] = s[1];
     }
-    tw_barrier();
+    lds_barrier();
     float mean[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
@@ -270,19 +192,19 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
           const float dv = y[ct][r][e] - mean[ct];
           q[ct] += dv * dv;
         }
-    tw_half_wave_sums(q);
+    half_wave_sums(q);
     if ((lane & 31) == 16) {
       red[64 + wave * 4 + 0 + (lane >> 5)] = q[0];
       red[64 + wave * 4 + 2 + (lane >> 5)] = q[1];
     }
-    tw_barrier();
+    lds_barrier();
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       const int g = ct * 2 + (lane >> 5);
       float t = 0.f;
 #pragma unroll
       for (int w = 0; w < TW_WAVES; ++w) t += red[64 + w * 4 + g];
-      const float rstd = 1.0f / sqrtf(t * inv_n + TW_GN_EPS);
+      const float rstd = 1.0f / sqrtf(t * inv_n + MVSN_GN_EPS);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int c = ct * 16 + cb + r;
@@ -303,7 +225,7 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
   if (a.head_chunks) {
     set_dilation(1);
     tower_layer<9>(planes, U, woff, lane, y);
-    tw_barrier();                     // planes and U free
+    lds_barrier();                     // planes and U free
     dma_u(up, 8);
     up += 8 * 2048;
     groupnorm_lrelu(y, lp, lp + 32, lp + 64);
@@ -317,14 +239,14 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
         for (int e = 0; e < 4; ++e) dst[ooff[e]] = y[ct][r][e];
       }
     dma_landed();
-    tw_barrier();
+    lds_barrier();
   }
 
   // ---- residual blocks --------------------------------------------------------------------------------
   for (int blk = 0; blk < a.n_blocks; ++blk) {
     set_dilation(a.dil[blk]);
     tower_layer<8>(planes, U, woff, lane, y);
-    tw_barrier();
+    lds_barrier();
     if (blk + 1 < a.n_blocks || a.tail_mode == 0) {
       dma_u(up, 8);
       up += 8 * 2048;
@@ -340,7 +262,7 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, MVSN_VIS
         for (int e = 0; e < 4; ++e) dst[ooff[e]] += y[ct][r][e];
       }
     dma_landed();
-    tw_barrier();
+    lds_barrier();
   }
 
   // ---- tail -------------------------------------------------------------------------------------------
