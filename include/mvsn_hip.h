@@ -384,6 +384,30 @@ int mvsn_soft_argmin(const float *cost, const float *idepth_samples, int n, int 
                      int pixels, float *idepth, mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-pixel confidence of the soft-argmin (not part of the reference, which keeps the
+ * expectation only).  With p = softmax(-cost) over the hypotheses: idx = sum_d p_d * d (in index space),
+ * i = clamp(floor(idx), 0, D-1), confidence = p[i-1] + p[i] + p[i+1] + p[i+2], terms outside [0, D-1] left out: the
+ * probability mass of the four hypotheses around the estimate (MVSNet's photometric confidence).  A NaN cost gives a
+ * NaN confidence in its pixel.
+ * mvsn_soft_argmin_confidence: ONE launch in place of mvsn_soft_argmin; its idepth is the same bits.
+ *   cost (N,D,P)  idepth_samples (N,D)  ->  idepth, confidence (N,P)
+ * mvsn_confidence_fuse_sources: minimum over the sources, chain n = s * batch + b; NaN in any source gives NaN.
+ *   confidence (S*B,P)  ->  out (B,P)
+ * mvsn_confidence_mask: out = (confidence >= min_confidence) && (valid == NULL || valid) as bytes 0 / 1 -- the `valid`
+ * input of mvsn_fusion_consistency; a NaN confidence compares false.   confidence, valid, out: `count` elements
+ * mvsn_fusion_gather: out[i] = maps[view[i] * pixels_per_view + pixel[i]] for the `count` points of mvsn_fusion_emit
+ * (NaN for an index outside the maps).   maps (n_views, pixels_per_view)  view, pixel (count) int32
+ * ------------------------------------------------------------------------------------------- */
+int mvsn_soft_argmin_confidence(const float *cost, const float *idepth_samples, int n, int num_idepth_samples,
+                                int pixels, float *idepth, float *confidence, mvsn_stream_t stream);
+int mvsn_confidence_fuse_sources(const float *confidence, int n_sources, int batch, int pixels, float *out,
+                                 mvsn_stream_t stream);
+int mvsn_confidence_mask(const float *confidence, const uint8_t *valid, long count, float min_confidence,
+                         uint8_t *out, mvsn_stream_t stream);
+int mvsn_fusion_gather(const float *maps, const int *view, const int *pixel, int n_views, long pixels_per_view,
+                       long count, float *out, mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The three elementwise steps the flag branches of forward() leave outside the fused kernels:
  *   mvsn_channel_l2_norm      do_cost_volume_filter = False: cost = ||cost_volume||_2 over the channel axis
  *                             (torch.norm(.., dim=1), multi_view_stereonet.py:598).  x (N,C,P) -> out (N,P)

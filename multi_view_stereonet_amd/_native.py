@@ -90,6 +90,10 @@ SIGNATURES = {
     "mvsn_conv_to1_volume_norm": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
     "mvsn_conv_to1": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_void_p]),
     "mvsn_soft_argmin": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "mvsn_soft_argmin_confidence": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2 + [c_void_p]),
+    "mvsn_confidence_fuse_sources": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
+    "mvsn_confidence_mask": (c_int, [c_void_p, c_void_p, c_long, ctypes.c_float, c_void_p, c_void_p]),
+    "mvsn_fusion_gather": (c_int, [c_void_p] * 3 + [c_int, c_long, c_long, c_void_p, c_void_p]),
     "mvsn_channel_l2_norm": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_idepth_scale": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_refiner_epilogue": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p]),

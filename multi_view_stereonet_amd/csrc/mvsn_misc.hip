@@ -915,3 +915,150 @@ extern "C" int mvsn_conv_to1_block_records(const float *in_raw, const float *in_
   return conv_to1_block_launch("mvsn_conv_to1_block_records", in_raw, in_records, tiles, in_gamma, in_beta, in_residual,
                                weight, bias, prior, fx, n, rows, cols, out, stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Per-pixel confidence.  Kept at the end of the file: the kernels above keep their order.
+// ---------------------------------------------------------------------------------------------
+namespace mvsn {
+
+// ---- soft-argmin that keeps the distribution's sharpness -------------------------
+// The same walk and, for m, den and num, the same operations in the same order as soft_argmin_kernel (the idepth
+// output is the same bits); the second pass also accumulates sum e * d.  Third step: the expected hypothesis index
+// idx = (sum e d) / den, i = clamp(floor(idx), 0, D - 1), confidence = (e[i-1] + e[i] + e[i+1] + e[i+2]) / den with
+// the terms outside [0, D) left out.  Its four loads re-read costs this workgroup has just read twice (cache hits);
+// neighbouring pixels peak on neighbouring hypotheses, so they are still mostly row segments across the wave.
+// A NaN cost makes den NaN: tested before anything is converted to an int, and written as NaN.
+__global__ __launch_bounds__(256) void soft_argmin_confidence_kernel(const float *__restrict__ cost,
+                                                                     const float *__restrict__ samples, int D, int P,
+                                                                     float *__restrict__ out,
+                                                                     float *__restrict__ confidence) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = blockIdx.y;
+  if (p >= P) return;
+  const float *c = cost + (size_t)n * D * P + p;
+  const float *s = samples + (size_t)n * D;
+  float m = -INFINITY;
+  int d0 = 0;
+  for (; d0 + 16 <= D; d0 += 16) {
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = c[(size_t)(d0 + j) * P];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m = fmaxf(m, -v[j]);
+  }
+  for (int d = d0; d < D; ++d) m = fmaxf(m, -c[(size_t)d * P]);
+  float den = 0.0f, num = 0.0f, idx = 0.0f;
+  for (d0 = 0; d0 + 16 <= D; d0 += 16) {
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = c[(size_t)(d0 + j) * P];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float e = expf(-v[j] - m);
+      den += e;
+      num += e * s[d0 + j];
+      idx += e * (float)(d0 + j);
+    }
+  }
+  for (int d = d0; d < D; ++d) {
+    float e = expf(-c[(size_t)d * P] - m);
+    den += e;
+    num += e * s[d];
+    idx += e * (float)d;
+  }
+  out[(size_t)n * P + p] = num / den;
+  const float expected = idx / den;
+  float conf = NAN;
+  if (expected == expected) {   // (false for NaN: never converted)
+    int i = (int)floorf(expected);
+    i = i < 0 ? 0 : (i > D - 1 ? D - 1 : i);
+    float w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int d = i - 1 + k;
+      const bool in = d >= 0 && d < D;
+      w[k] = in ? c[(size_t)(in ? d : 0) * P] : INFINITY;   // exp(-inf) = 0: a term outside the range
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum += expf(-w[k] - m);
+    conf = sum / den;
+  }
+  confidence[(size_t)n * P + p] = conf;
+}
+
+// min over the S sources of the per-chain confidences (chain n = s * B + b); a NaN in any source gives NaN
+__global__ __launch_bounds__(256) void confidence_fuse_kernel(const float *__restrict__ conf, int S, int B, int P,
+                                                              float *__restrict__ out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (p >= P) return;
+  float acc = conf[(size_t)b * P + p];
+  for (int s = 1; s < S; ++s) {
+    const float v = conf[((size_t)s * B + b) * P + p];
+    acc = (v != v || v < acc) ? v : acc;   // (acc NaN: v < acc is false, it stays)
+  }
+  out[(size_t)b * P + p] = acc;
+}
+
+// out = (conf >= thr) && (valid == null || valid) as 0 / 1 bytes; NaN compares false
+__global__ __launch_bounds__(256) void confidence_mask_kernel(const float *__restrict__ conf,
+                                                              const uint8_t *__restrict__ valid, long count, float thr,
+                                                              uint8_t *__restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const bool keep = conf[i] >= thr && (valid == nullptr || valid[i] != 0);
+  out[i] = keep ? 1 : 0;
+}
+
+// out[i] = maps[view[i] * HW + pixel[i]]; an index outside the maps is never dereferenced (NaN)
+__global__ __launch_bounds__(256) void fusion_gather_kernel(const float *__restrict__ maps, const int *__restrict__ view,
+                                                            const int *__restrict__ pixel, int V, long HW, long count,
+                                                            float *__restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int v = view[i], q = pixel[i];
+  out[i] = (v >= 0 && v < V && q >= 0 && q < HW) ? maps[(size_t)v * HW + q] : NAN;
+}
+
+}  // namespace mvsn
+
+extern "C" int mvsn_soft_argmin_confidence(const float *cost, const float *idepth_samples, int n, int D, int pixels,
+                                           float *idepth, float *confidence, mvsn_stream_t stream) {
+  MVSN_REQUIRE(cost && idepth_samples && idepth && confidence, MVSN_E_BADARG, "mvsn_soft_argmin_confidence: null pointer");
+  MVSN_REQUIRE(n > 0 && D > 0 && pixels > 0 && n <= 65535, MVSN_E_BADARG, "mvsn_soft_argmin_confidence: bad sizes");
+  hipLaunchKernelGGL(mvsn::soft_argmin_confidence_kernel, dim3((pixels + 255) / 256, n), dim3(256), 0,
+                     (hipStream_t)stream, cost, idepth_samples, D, pixels, idepth, confidence);
+  return mvsn::check_launch("mvsn_soft_argmin_confidence");
+}
+
+extern "C" int mvsn_confidence_fuse_sources(const float *confidence, int n_sources, int batch, int pixels, float *out,
+                                            mvsn_stream_t stream) {
+  MVSN_REQUIRE(confidence && out, MVSN_E_BADARG, "mvsn_confidence_fuse_sources: null pointer");
+  MVSN_REQUIRE(n_sources > 0 && batch > 0 && batch <= 65535 && pixels > 0, MVSN_E_BADARG,
+               "mvsn_confidence_fuse_sources: bad sizes");
+  hipLaunchKernelGGL(mvsn::confidence_fuse_kernel, dim3((pixels + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream,
+                     confidence, n_sources, batch, pixels, out);
+  return mvsn::check_launch("mvsn_confidence_fuse_sources");
+}
+
+extern "C" int mvsn_confidence_mask(const float *confidence, const uint8_t *valid, long count, float min_confidence,
+                                    uint8_t *out, mvsn_stream_t stream) {
+  MVSN_REQUIRE(confidence && out, MVSN_E_BADARG, "mvsn_confidence_mask: null pointer");
+  MVSN_REQUIRE(count > 0 && (count + 255) / 256 <= 2147483647L, MVSN_E_BADARG, "mvsn_confidence_mask: bad sizes");
+  MVSN_REQUIRE(min_confidence == min_confidence, MVSN_E_BADARG, "mvsn_confidence_mask: the threshold is NaN");
+  hipLaunchKernelGGL(mvsn::confidence_mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, confidence, valid, count, min_confidence, out);
+  return mvsn::check_launch("mvsn_confidence_mask");
+}
+
+extern "C" int mvsn_fusion_gather(const float *maps, const int *view, const int *pixel, int n_views, long pixels_per_view,
+                                  long count, float *out, mvsn_stream_t stream) {
+  MVSN_REQUIRE(maps && view && pixel && out, MVSN_E_BADARG, "mvsn_fusion_gather: null pointer");
+  MVSN_REQUIRE(n_views > 0 && pixels_per_view > 0 && pixels_per_view <= 2147483647L && count > 0 &&
+                   (count + 255) / 256 <= 2147483647L,
+               MVSN_E_BADARG, "mvsn_fusion_gather: bad sizes");
+  hipLaunchKernelGGL(mvsn::fusion_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     maps, view, pixel, n_views, pixels_per_view, count, out);
+  return mvsn::check_launch("mvsn_fusion_gather");
+}

@@ -3,7 +3,9 @@
 Each reference view's depth is checked against its neighbours' depths; the pixels enough neighbours confirm are
 averaged with the confirming depths and back-projected into world coordinates (DESIGN.md section 10 states the
 semantics; the kernels are csrc/mvsn_fusion.hip).  ``fuse_depthmaps`` runs that on depth maps already on the device,
-``reconstruct`` runs the network over posed frames first, and ``write_ply`` saves the result.
+``reconstruct`` runs the network over posed frames first, and ``write_ply`` saves the result.  A per-pixel confidence
+(``net.options.confidence``) can gate the fusion before the geometric check (``min_confidence``)
+and be read at the kept points (``point_values``).
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -50,7 +52,8 @@ def _check_frames(name, t, V, H, W, channels, dtypes, device):
 def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
                    images: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
                    ref_views: Optional[Sequence[int]] = None, max_reproj_px: float = 1.0,
-                   max_rel_depth: float = 0.01, min_consistent: int = 2) -> FusionResult:
+                   max_rel_depth: float = 0.01, min_consistent: int = 2, confidence: Optional[torch.Tensor] = None,
+                   min_confidence: Optional[float] = None) -> FusionResult:
     """Fuse ``depth`` (V,1,H,W) into a point cloud.
 
     ``neighbours`` is a host (R,M) integer array, 1 <= M <= 32: row i lists the views that check ``ref_views[i]``
@@ -58,7 +61,11 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
     neighbours confirm it (reprojection error < ``max_reproj_px`` pixels and relative depth difference <
     ``max_rel_depth``).  Points come ordered by position in ``ref_views``, then row-major pixel.  Everything is validated
     here, before any launch; the one host synchronisation is the read of the number of kept pixels (to size the
-    outputs)."""
+    outputs).
+
+    ``confidence`` (V,1,H,W) fp32 with ``min_confidence``: the call is this function with ``valid`` and-ed with
+    ``confidence >= min_confidence`` (formed on the device; a pixel at the threshold is kept, a NaN confidence is not).
+    The gate applies, as ``valid`` does, to the candidate pixel and to every neighbour tap."""
     if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
         raise ValueError("depth must be a (V,1,H,W) tensor")
     V, _, H, W = depth.shape
@@ -76,6 +83,12 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
         _check_frames("images", images, V, H, W, 3, (torch.float32,), dev)
     if valid is not None:
         _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
+    if min_confidence is not None and confidence is None:
+        raise ValueError("min_confidence needs the confidence maps")
+    if confidence is not None:
+        _check_frames("confidence", confidence, V, H, W, 1, (torch.float32,), dev)
+    if min_confidence is not None and not float(min_confidence) >= 0:
+        raise ValueError(f"min_confidence must be a non-negative number, got {min_confidence}")
     nb = _host_index_array(neighbours, "neighbours")
     if nb.ndim != 2:
         raise ValueError(f"neighbours must be (R, M), got shape {nb.shape}")
@@ -103,6 +116,13 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
     f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
     depth_c, K_c, T_c = f32(depth), f32(K), f32(T_cam_in_world)
     valid_c = valid.detach().contiguous().view(torch.uint8) if valid is not None else None
+    if confidence is not None and min_confidence is not None:
+        gated = torch.empty((V, 1, H, W), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.mvsn_confidence_mask(_native.ptr(confidence.detach().contiguous()), _native.ptr(valid_c),
+                                                   V * H * W, float(min_confidence), _native.ptr(gated),
+                                                   _native.stream()), "mvsn_confidence_mask")
+        valid_c = gated
     refs_d = torch.from_numpy(refs.astype(np.int32)).to(dev)
     nb_d = torch.from_numpy(np.ascontiguousarray(nb.astype(np.int32))).to(dev)
     ws_bytes = lib.mvsn_fusion_workspace_bytes(R, M, H, W)
@@ -129,6 +149,42 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
     return FusionResult(points, colors, view, pixel, fused, count)
 
 
+def point_values(result: FusionResult, maps: torch.Tensor, ref_views: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The value of ``maps`` (V,1,H,W) fp32 -- a confidence pyramid's level 0, say -- at every point of ``result``:
+    (M,) fp32, ``maps[result.view[i]]`` at row-major pixel ``result.pixel[i]``.  ``ref_views``: the fusion's, when
+    ``maps`` holds only those views, in that order (``maps`` is then (R,1,H,W))."""
+    if not torch.is_tensor(maps) or maps.dim() != 4 or maps.shape[1] != 1:
+        raise ValueError("maps must be a (V,1,H,W) tensor")
+    if maps.dtype != torch.float32:
+        raise ValueError(f"maps must be float32, got {maps.dtype}")
+    if tuple(maps.shape[-2:]) != tuple(result.depth.shape[-2:]):
+        raise ValueError(f"maps are {tuple(maps.shape[-2:])}, the fusion ran on {tuple(result.depth.shape[-2:])}")
+    if maps.device != result.view.device:
+        raise ValueError(f"maps are on {maps.device}, the points on {result.view.device}")
+    view = result.view
+    if ref_views is not None:
+        refs = _host_index_array(ref_views, "ref_views").reshape(-1)
+        if refs.shape[0] != maps.shape[0]:
+            raise ValueError(f"maps hold {maps.shape[0]} views for {refs.shape[0]} reference views")
+        row = np.full(int(refs.max()) + 1 if refs.size else 1, -1, dtype=np.int32)
+        row[refs] = np.arange(refs.shape[0], dtype=np.int32)
+        lut = torch.from_numpy(row).to(view.device)
+        view = lut[view.long().clamp(0, lut.shape[0] - 1)].contiguous()
+    if not maps.is_cuda:
+        raise RuntimeError("point_values runs on HIP devices only (there is no CPU implementation)")
+    M = int(view.shape[0])
+    out = torch.empty((M,), dtype=torch.float32, device=maps.device)
+    if M == 0:
+        return out
+    lib = _native.load()
+    with torch.cuda.device(maps.device):
+        _native.check(lib.mvsn_fusion_gather(_native.ptr(maps.detach().contiguous()), _native.ptr(view.contiguous()),
+                                             _native.ptr(result.pixel.contiguous()), maps.shape[0],
+                                             maps.shape[2] * maps.shape[3], M, _native.ptr(out), _native.stream()),
+                      "mvsn_fusion_gather")
+    return out
+
+
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:
     """T_right_in_left = T_left_in_world^-1 T_right_in_world for every (ref[i], src[i]): (len(ref),1,4,4) fp32, formed
     in fp64 on the host (a handful of 4x4s: the DataLoader-side pose arithmetic)."""
@@ -139,14 +195,19 @@ def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequ
 
 def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
                 num_idepth_samples: int = 64, batch: int = 8, cost_volume_filter: bool = True,
-                refiners: Sequence[bool] = (True,) * 5, **fusion_kwargs):
+                refiners: Sequence[bool] = (True,) * 5, with_confidence: bool = False,
+                min_confidence: Optional[float] = None, **fusion_kwargs):
     """Posed frames -> point cloud: the network's depth map for every view, then ``fuse_depthmaps`` over all of them.
 
     ``images`` (V,3,H,W) fp32 in [-1,1] on the network's device, ``K`` / ``T_cam_in_world`` (V,4,4), ``neighbours`` (V,S)
     without -1: the S source views of each reference view, the first of which sets the baseline (a zero baseline
     raises, as ``multi_view_unpack_batch`` does).  The network runs over the reference views ``batch`` at a time; its
     finest idepth map is converted to depth in the units of the poses (``metrics.idepth_to_depth``).  The same
-    ``neighbours`` (and ``fusion_kwargs``) drive the fusion.  Returns ``(FusionResult, depth (V,1,H,W))``."""
+    ``neighbours`` (and ``fusion_kwargs``) drive the fusion.  Returns ``(FusionResult, depth (V,1,H,W))``.
+
+    ``with_confidence`` or a ``min_confidence``: the forwards run with ``net.options.confidence`` on (restored
+    afterwards, also when a forward raises), the finest confidence map of every view goes, with ``min_confidence``, to
+    the fusion, and the return value is ``(FusionResult, depth, confidence (V,1,H,W))``."""
     from . import metrics
     from . import multi_view_stereonet_utils as snu
 
@@ -169,24 +230,40 @@ def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torc
     Kc = K.detach().to("cpu", torch.float32)
     params = {"num_idepth_samples": int(num_idepth_samples), "cost_volume_filter": bool(cost_volume_filter),
               "refiners": list(refiners)}
-    depths = []
+    want_conf = bool(with_confidence) or min_confidence is not None
+    depths, confs = [], []
+    old_conf = net.options.confidence
+    net.options.confidence = want_conf or old_conf
+    try:
+        with torch.no_grad():
+            for lo in range(0, V, batch):
+                ref = list(range(lo, min(lo + batch, V)))
+                frames = {"left_image": images[ref],
+                          "right_image": [images[nb[ref, s].tolist()] for s in range(nb.shape[1])],
+                          "K": Kc[ref].unsqueeze(1).contiguous(),
+                          "T_right_in_left": [frame_pair_poses(T_cam_in_world, ref, nb[ref, s])
+                                              for s in range(nb.shape[1])]}
+                inputs = snu.multi_view_unpack_batch(frames, dev, net.num_levels)
+                out = snu.multi_view_forward(net, inputs, params)
+                depths.append(metrics.idepth_to_depth(out["left_idepthmap_pyr"][0], inputs["baseline"]))
+                if want_conf:
+                    confs.append(out["left_confidence_pyr"][0])
+    finally:
+        net.options.confidence = old_conf
     with torch.no_grad():
-        for lo in range(0, V, batch):
-            ref = list(range(lo, min(lo + batch, V)))
-            frames = {"left_image": images[ref],
-                      "right_image": [images[nb[ref, s].tolist()] for s in range(nb.shape[1])],
-                      "K": Kc[ref].unsqueeze(1).contiguous(),
-                      "T_right_in_left": [frame_pair_poses(T_cam_in_world, ref, nb[ref, s]) for s in range(nb.shape[1])]}
-            inputs = snu.multi_view_unpack_batch(frames, dev, net.num_levels)
-            out = snu.multi_view_forward(net, inputs, params)
-            depths.append(metrics.idepth_to_depth(out["left_idepthmap_pyr"][0], inputs["baseline"]))
         depth = torch.cat(depths, 0)
-        result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, **fusion_kwargs)
-    return result, depth
+        if not want_conf:
+            result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, **fusion_kwargs)
+            return result, depth
+        confidence = torch.cat(confs, 0)
+        result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, confidence=confidence,
+                                min_confidence=min_confidence, **fusion_kwargs)
+    return result, depth, confidence
 
 
-def write_ply(path: str, points, colors=None) -> None:
-    """Binary little-endian PLY: float x, y, z per vertex, plus uchar red, green, blue when ``colors`` is given."""
+def write_ply(path: str, points, colors=None, confidence=None) -> None:
+    """Binary little-endian PLY: float x, y, z per vertex, plus uchar red, green, blue when ``colors`` is given, plus
+    float confidence (after the colours) when ``confidence`` (N,) is given."""
     pts = (points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)).astype("<f4")
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError("points must be (N,3)")
@@ -196,11 +273,18 @@ def write_ply(path: str, points, colors=None) -> None:
         if col.shape != pts.shape:
             raise ValueError("colors must be (N,3) like points")
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if confidence is not None:
+        conf = (confidence.detach().cpu().numpy() if torch.is_tensor(confidence) else np.asarray(confidence)).astype("<f4")
+        if conf.shape != (pts.shape[0],):
+            raise ValueError("confidence must be (N,) like the points")
+        fields += [("confidence", "<f4")]
     rec = np.empty(pts.shape[0], dtype=fields)
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
     if colors is not None:
         col = col.astype(np.uint8)
         rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    if confidence is not None:
+        rec["confidence"] = conf
     props = "".join(f"property {'float' if t == '<f4' else 'uchar'} {n}\n" for n, t in fields)
     header = f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\n{props}end_header\n"
     with open(path, "wb") as f:

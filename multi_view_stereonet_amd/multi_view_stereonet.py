@@ -158,10 +158,15 @@ class EngineOptions:
         # recomputation when a hand-off timed out -- the forward's outputs are valid either way, without a host round
         # trip.  The module then stops choosing the banded form (see MultiViewStereoNet.check_device_status).
         self.banded_repair = True
+        # Per-pixel confidence next to the idepth maps: the soft-argmin launch is replaced by
+        # mvsn_soft_argmin_confidence (same idepth bits), the per-chain confidences are fused by the minimum over the
+        # sources and upsampled level to level; the forward's dict gains "left_confidence_pyr".  Off: no launch, no
+        # output and no bit of any result differs.
+        self.confidence = False
 
     NAMES = ("split_finalize", "banded_repair", "towers", "plan_max_chains", "plan_graph", "plan_max_bytes", "carry_passes", "carry_min_bytes", "carry_volume_passes", "carry_alternate", "chain_form", "fold_residual_blocks", "conv_precision", "winograd", "winograd_with_input_transform",
              "winograd_volume", "winograd_stride2", "volume_materialise", "trim_tower_ends", "cat_free_heads", "lazy_stats_max_samples",
-             "lazy_stats_max_records")
+             "lazy_stats_max_records", "confidence")
 
 
 class _Records:
@@ -1164,6 +1169,25 @@ class PlaneSweepEngine:
                    N, D, rows * cols, _native.ptr(out), _native.stream(), nbytes=4.0 * (cost.numel() + out.numel()))
         return out
 
+    def soft_argmin_confidence(self, cost: torch.Tensor, samples: torch.Tensor):
+        """soft_argmin (the same bits) and the per-chain confidence (N,1,rows,cols) from the same launch."""
+        N, D, rows, cols = cost.shape
+        out = self.empty((N, 1, rows, cols), dtype=torch.float32, device=cost.device)
+        conf = self.empty((N, 1, rows, cols), dtype=torch.float32, device=cost.device)
+        self._call("mvsn_soft_argmin_confidence", self.lib.mvsn_soft_argmin_confidence, _native.ptr(self.dense(cost)),
+                   _native.ptr(samples), N, D, rows * cols, _native.ptr(out), _native.ptr(conf), _native.stream(),
+                   nbytes=4.0 * (cost.numel() + 2 * out.numel()))
+        return out, conf
+
+    def confidence_fuse_sources(self, conf: torch.Tensor, S: int, B: int) -> torch.Tensor:
+        """Minimum over the S sources of per-chain confidences (S*B,1,rows,cols), chain n = s*B + b -> (B,1,rows,cols)."""
+        N, _, rows, cols = conf.shape
+        assert N == S * B
+        out = self.empty((B, 1, rows, cols), dtype=torch.float32, device=conf.device)
+        self._call("mvsn_confidence_fuse_sources", self.lib.mvsn_confidence_fuse_sources, _native.ptr(self.dense(conf)),
+                   S, B, rows * cols, _native.ptr(out), _native.stream(), nbytes=4.0 * (conf.numel() + out.numel()))
+        return out
+
     def upsample(self, x: torch.Tensor, size) -> torch.Tensor:
         n, c, h, w = x.shape
         out = self.empty((n, c, int(size[0]), int(size[1])), dtype=torch.float32, device=x.device)
@@ -1241,7 +1265,11 @@ class PlaneSweepEngine:
             self._call("mvsn_channel_l2_norm", self.lib.mvsn_channel_l2_norm, _native.ptr(cost), cost.shape[0],
                        cost.shape[1], cost[0, 0].numel(), _native.ptr(filtered), _native.stream(),
                        nbytes=4.0 * (cost.numel() + filtered.numel()))
-        raw = self.soft_argmin(filtered, samples)
+        want_conf = bool(self.confidence)
+        if want_conf:
+            raw, conf_chain = self.soft_argmin_confidence(filtered, samples)
+        else:
+            raw = self.soft_argmin(filtered, samples)
 
         # 6. level-4 refinement per chain, then fuse the sources
         if do_refiners[4]:
@@ -1262,14 +1290,21 @@ class PlaneSweepEngine:
                            warped_fullres=warped0, left_features=left_feats, plane0_features=plane0,
                            cost_volume=cost, mask_volume=mask, feature_volume=fvol, filtered_cost=filtered,
                            raw_per_chain=raw)
+            if want_conf:
+                capture.update(confidence_per_chain=conf_chain)
 
         # 7. coarse-to-fine
         idepth = [None] * 5
         prior = [None] * 5
         masks = [None] * 5
         prior[4], idepth[4], masks[4] = raw4, idepth4, mask4
+        conf = [None] * 5
+        if want_conf:
+            conf[4] = self.confidence_fuse_sources(conf_chain, S, B)
         for lvl in (3, 2, 1, 0):
             size = left_image_pyr[lvl].shape[-2:]
+            if want_conf:
+                conf[lvl] = self.upsample(conf[lvl + 1], size)
             if do_refiners[lvl]:
                 fx = fx_all[lvl]
                 prior[lvl], scaled = self.upsample_prior(idepth[lvl + 1], fx, size)
@@ -1282,7 +1317,10 @@ class PlaneSweepEngine:
                 idepth[lvl] = self.idepth_refiner(lvl, guide, prior[lvl], fx, scaled=scaled)
             else:
                 idepth[lvl] = prior[lvl]
-        return {"left_idepthmap_pyr": idepth, "left_idepthmap_raw_pyr": prior, "left_idepthmap_mask_pyr": masks}
+        out = {"left_idepthmap_pyr": idepth, "left_idepthmap_raw_pyr": prior, "left_idepthmap_mask_pyr": masks}
+        if want_conf:
+            out["left_confidence_pyr"] = conf
+        return out
 
 
 class MultiViewStereoNet(nn.Module):

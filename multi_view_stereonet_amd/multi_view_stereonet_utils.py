@@ -263,11 +263,15 @@ def forward(stereo_network, inputs: Dict[str, object], params: Dict[str, object]
     outputs = {"left_idepthmap_pyr": left["left_idepthmap_pyr"],
                "left_idepthmap_raw_pyr": left["left_idepthmap_raw_pyr"],
                "left_idepthmap_mask_pyr": left["left_idepthmap_mask_pyr"], "stereo_time_ms": ms}
+    if "left_confidence_pyr" in left:            # (net.options.confidence)
+        outputs["left_confidence_pyr"] = left["left_confidence_pyr"]
     if params.get("estimate_right_idepthmap", False):
         right, ms_r = run(inputs["right_image_pyr"], inputs["T_left_in_right"], inputs["left_image_pyr"])
         outputs["right_idepthmap_pyr"] = right["left_idepthmap_pyr"]
         outputs["right_idepthmap_raw_pyr"] = right["left_idepthmap_raw_pyr"]
         outputs["right_idepthmap_mask_pyr"] = right["left_idepthmap_mask_pyr"]
+        if "left_confidence_pyr" in right:
+            outputs["right_confidence_pyr"] = right["left_confidence_pyr"]
         outputs["stereo_time_ms"] = 0.5 * (ms + ms_r)
     return outputs
 
@@ -312,6 +316,11 @@ def _tock(device_is_gpu: bool, a, b) -> float:
     return (time.time() - a) * 1000.0
 
 
+def _confidence_of(out) -> Dict[str, object]:
+    """The confidence pyramid of a forward run with net.options.confidence, passed through; nothing otherwise."""
+    return {"left_confidence_pyr": out["left_confidence_pyr"]} if "left_confidence_pyr" in out else {}
+
+
 def multi_view_forward(stereo_network, inputs: Dict[str, object], params: Dict[str, object],
                        sync_timer: bool = True):
     """Time and run the network exactly as the reference's wrapper does.
@@ -334,7 +343,7 @@ def multi_view_forward(stereo_network, inputs: Dict[str, object], params: Dict[s
         return {"left_idepthmap_pyr": out["left_idepthmap_pyr"],
                 "left_idepthmap_raw_pyr": out["left_idepthmap_raw_pyr"],
                 "left_idepthmap_mask_pyr": out["left_idepthmap_mask_pyr"],
-                "stereo_time_ms": None, "stereo_time_events": (a, b)}
+                "stereo_time_ms": None, "stereo_time_events": (a, b), **_confidence_of(out)}
     a, b = _tick(on_gpu)
     out = stereo_network(inputs["left_image_pyr"], inputs["K_pyr"], inputs["T_right_in_left"],
                          inputs["right_image_pyr"], int(params["num_idepth_samples"]),
@@ -348,4 +357,4 @@ def multi_view_forward(stereo_network, inputs: Dict[str, object], params: Dict[s
     return {"left_idepthmap_pyr": out["left_idepthmap_pyr"],
             "left_idepthmap_raw_pyr": out["left_idepthmap_raw_pyr"],
             "left_idepthmap_mask_pyr": out["left_idepthmap_mask_pyr"],
-            "stereo_time_ms": ms}
+            "stereo_time_ms": ms, **_confidence_of(out)}

@@ -6,7 +6,8 @@ count), warm-up excluded, and the bytes each kernel must move: the consistency k
 writes the fused depth and the count map (its neighbour taps are gathered through L2 / MALL and listed separately as
 the logical gather volume), the emit kernel reads the fused depth and writes the points, colours, view and pixel
 arrays.  Prints one JSON line per scene.  The kernel split comes from a rocprofv3 --kernel-trace --stats run of this
-tool."""
+tool.  --confidence: also times the call gated by a seeded random confidence at min_confidence = 0.25 (one more launch,
+mvsn_confidence_mask, in front of the four) and reports it as "gated"."""
 import argparse
 import json
 import os
@@ -29,24 +30,37 @@ def neighbours(views, slots):
                      for v in range(views)])
 
 
-def run(V, H, W, M, steps, warmup):
-    dev = torch.device("cuda:0")
-    sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
-    nb = neighbours(V, M)
-    args = (sc["depth"], sc["K"], sc["T_cam_in_world"], nb)
+def timed(call, steps, warmup):
     for _ in range(warmup):
-        res = fuse_depthmaps(*args, images=sc["images"])
+        res = call()
     torch.cuda.synchronize()
     times = []
     for _ in range(steps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        res = fuse_depthmaps(*args, images=sc["images"])
+        res = call()
         b.record()
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b))
+    return res, times
+
+
+def run(V, H, W, M, steps, warmup, confidence=False):
+    dev = torch.device("cuda:0")
+    sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
+    nb = neighbours(V, M)
+    args = (sc["depth"], sc["K"], sc["T_cam_in_world"], nb)
+    res, times = timed(lambda: fuse_depthmaps(*args, images=sc["images"]), steps, warmup)
     P, N = H * W, int(res.points.shape[0])
-    return {"scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    gated = {}
+    if confidence:
+        conf = torch.rand(V, 1, H, W, generator=torch.Generator().manual_seed(0)).to(dev)
+        gres, gtimes = timed(lambda: fuse_depthmaps(*args, images=sc["images"], confidence=conf, min_confidence=0.25),
+                             steps, warmup)
+        gated = {"gated": {"min_confidence": 0.25, "ms_per_call_median": float(np.median(gtimes)),
+                           "ms_per_call_min": float(np.min(gtimes)), "points": int(gres.points.shape[0]),
+                           "mask_bytes": 5 * V * P + V * P}}
+    return {**gated, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -58,10 +72,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--confidence", action="store_true", help="also time the call gated by a confidence map")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
-        print(json.dumps(run(V, H, W, M, a.steps, a.warmup)), flush=True)
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence)), flush=True)
 
 
 if __name__ == "__main__":

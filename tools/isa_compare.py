@@ -41,7 +41,7 @@ def compile_asm(tree, name, out):
 
 
 def normalise(line):
-    line = re.sub(r"\bBB\d+_", "BB_", line)
+    line = re.sub(r"(?:\.L|\b)BB\d+_", "BB_", line)      # (.LBB<n>_<k> in code, BB<n>_<k> in comments)
     line = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", line)
     line = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", line)
     return " ".join(line.split())
@@ -60,6 +60,8 @@ def split_symbols(asm):
         body = [normalise(l) for l in lines[i:end]]
         body = [l for l in body if l and not l.startswith("; -- Begin function") and not l.startswith(".protected")
                 and not l.startswith(".globl") and not l.startswith(".p2align")]
+        while body and (body[-1] == ".text" or body[-1].startswith(".section .text")):
+            body.pop()                               # the directive that opens the NEXT function's section
         code_end = next((k for k, l in enumerate(body) if l.startswith(".Lfunc_end") or l.startswith(".amdhsa_kernel")
                          or l.startswith(".section")), len(body))
         insn = [l for l in body[:code_end] if not l.startswith((";", ".")) and not re.match(r"\S+:( ;.*)?$", l)]
