@@ -575,6 +575,39 @@ int mvsn_fusion_emit(const float *fused_depth, const float *images, const int *r
                      int n_slots, const void *workspace, size_t workspace_bytes, long capacity, float *points,
                      uint8_t *colors, int *view, int *pixel, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Voxel-grid merge of a point cloud (multi_view_stereonet_amd/fusion.py: voxel_merge; the semantics are DESIGN.md
+ * section 12): the points of one grid cell become one point.  Per point and axis, in fp32: s = p - origin,
+ * t = s * inv_voxel_size, c = floor(t), f = t - c, q = min(65535, (uint)(f * 65536)).  A point with a non-finite
+ * coordinate or t is dropped; a finite point needs -2^20 <= c < 2^20 on every axis.  The points of equal (cx, cy, cz)
+ * form a voxel; output rows are ordered by the lowest input index of their voxel.
+ *   points (n,3) fp32, colors (n,3) u8 or NULL, 1 <= n <= 2^31 - 1; voxel_size and inv_voxel_size = 1 / voxel_size
+ *   are both formed by the caller, in fp32
+ * mvsn_voxel_assign: hash-grid build, first-point count and scan.
+ *   -> result (2 int64): [0] the number of voxels M, [1] status bits (MVSN_VOXEL_STATUS_*; 0 = fine).  Reading the two
+ *      words back is the one host synchronisation of a merge.
+ *   workspace: mvsn_voxel_workspace_bytes(n) bytes, 16-byte aligned, handed on to mvsn_voxel_merge unchanged: 16 bytes
+ *   per table slot (a power of two >= 2 n slots), 4 bytes per point, 12 bytes per 1024 points.
+ * mvsn_voxel_merge: rank, accumulate, finalise.  capacity = M as read back (0 = no launch: every point was dropped and
+ *   the caller fills `inverse` with -1).  accumulators: capacity * 64 bytes of scratch, 16-byte aligned.
+ *   -> out_points (M,3) fp32: (float)(o + (c + (sum q / count + 0.5) / 65536) * voxel_size) in fp64, one rounding per step
+ *      out_colors (M,3) u8 or NULL (with colors): (2 sum C + count) / (2 count) in integers   count (M) int32
+ *      first (M) int64: the lowest input index among the voxel's points   inverse (n) int64: row of every point, -1 = dropped
+ * Integer atomics only (compare-and-swap on an empty key, minimum, sums): every output is a deterministic function of
+ * the inputs, whatever order the points arrive in.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_VOXEL_STATUS_RANGE 1   /* a finite point's cell lies outside [-2^20, 2^20): voxel size too small */
+#define MVSN_VOXEL_STATUS_TABLE 2   /* a probe sequence visited every slot without finding room (cannot happen
+                                       below 2^30 points: the table is at most half full) */
+size_t mvsn_voxel_workspace_bytes(long n);
+int mvsn_voxel_assign(const float *points, long n, float voxel_size, float inv_voxel_size, float origin_x,
+                      float origin_y, float origin_z, int64_t *result, void *workspace, size_t workspace_bytes,
+                      mvsn_stream_t stream);
+int mvsn_voxel_merge(const float *points, const uint8_t *colors, long n, float voxel_size, float inv_voxel_size,
+                     float origin_x, float origin_y, float origin_z, void *workspace, size_t workspace_bytes,
+                     long capacity, void *accumulators, float *out_points, uint8_t *out_colors, int *count,
+                     int64_t *first, int64_t *inverse, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -116,6 +116,10 @@ SIGNATURES = {
     "mvsn_fusion_consistency": (c_int, [c_void_p] * 6 + [c_int] * 5 + [ctypes.c_float] * 2 + [c_int] + [c_void_p] * 4 +
                                 [c_size_t, c_void_p]),
     "mvsn_fusion_emit": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_size_t, c_long] + [c_void_p] * 4 + [c_void_p]),
+    "mvsn_voxel_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_voxel_assign": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_voxel_merge": (c_int, [c_void_p, c_void_p, c_long] + [ctypes.c_float] * 5 + [c_void_p, c_size_t, c_long] +
+                         [c_void_p] * 6 + [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

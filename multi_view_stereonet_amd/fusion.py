@@ -5,7 +5,8 @@ averaged with the confirming depths and back-projected into world coordinates (D
 semantics; the kernels are csrc/mvsn_fusion.hip).  ``fuse_depthmaps`` runs that on depth maps already on the device,
 ``reconstruct`` runs the network over posed frames first, and ``write_ply`` saves the result.  A per-pixel confidence
 (``net.options.confidence``) can gate the fusion before the geometric check (``min_confidence``)
-and be read at the kept points (``point_values``).
+and be read at the kept points (``point_values``).  ``voxel_merge`` (csrc/mvsn_voxel.hip) merges a
+cloud on a voxel grid: a surface that k views saw is in the fused cloud k times, and in the merged one once.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -183,6 +184,100 @@ def point_values(result: FusionResult, maps: torch.Tensor, ref_views: Optional[S
                                              maps.shape[2] * maps.shape[3], M, _native.ptr(out), _native.stream()),
                       "mvsn_fusion_gather")
     return out
+
+
+class VoxelCloud(NamedTuple):
+    points: torch.Tensor             # (M,3) fp32: mean position of each occupied voxel
+    colors: Optional[torch.Tensor]   # (M,3) uint8 mean colour, or None
+    count: torch.Tensor              # (M,) int32: points merged into the voxel
+    first: torch.Tensor              # (M,) int64: lowest input index among the voxel's points
+    inverse: torch.Tensor            # (N,) int64: output row of every input point, -1 = dropped
+
+
+VOXEL_CELL_LIMIT = 1 << 20           # cells of a finite point lie in [-2^20, 2^20) on every axis
+VOXEL_STATUS_RANGE, VOXEL_STATUS_TABLE = 1, 2
+
+
+def voxel_merge(points: torch.Tensor, voxel_size: float, *, colors: Optional[torch.Tensor] = None,
+                origin: Sequence[float] = (0.0, 0.0, 0.0)) -> VoxelCloud:
+    """Merge ``points`` (N,3) fp32 on a regular grid of ``voxel_size`` anchored at ``origin``: the points of one cell
+    become one point, at the mean of their positions (and of ``colors`` (N,3) uint8), ordered by the lowest input index
+    of each voxel -- a cloud of ``fuse_depthmaps`` keeps its "reference, then row-major pixel" order.  ``first`` and
+    ``inverse`` carry the provenance: ``res.view[vc.first]`` / ``res.pixel[vc.first]`` name a representative pixel,
+    and any per-point attribute reduces through ``inverse`` with ordinary torch.
+
+    The cell of a point is floor((p - origin) * (1 / voxel_size)) in fp32 (DESIGN.md section 12 states every step); a
+    point with a non-finite coordinate is dropped (``inverse`` -1, counted nowhere); a finite point more than 2^20
+    cells from the origin raises ValueError.  Every output is a bitwise-reproducible function of the inputs, and the
+    means do not depend on the order of the points.  Everything is validated here, before any launch; the one host
+    synchronisation is the read of the number of voxels (with the status word beside it)."""
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be an (N,3) tensor")
+    if points.dtype != torch.float32:
+        raise ValueError(f"points must be float32, got {points.dtype}")
+    N, dev = int(points.shape[0]), points.device
+    if N > 2 ** 31 - 1:
+        raise ValueError(f"at most 2^31 - 1 points, got {N}")
+    if colors is not None:
+        if not torch.is_tensor(colors) or tuple(colors.shape) != (N, 3):
+            raise ValueError(f"colors must be an ({N},3) tensor like points")
+        if colors.dtype != torch.uint8:
+            raise ValueError(f"colors must be uint8, got {colors.dtype}")
+        if colors.device != dev:
+            raise ValueError(f"colors are on {colors.device}, points on {dev}")
+    with np.errstate(all="ignore"):
+        try:
+            v = np.float32(voxel_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"voxel_size must be a positive finite number, got {voxel_size!r}") from None
+        inv = np.float32(1) / v
+    if not (np.isfinite(v) and v > 0 and np.isfinite(inv) and inv > 0):
+        raise ValueError(f"voxel_size must be finite and > 0 (in float32, with a finite inverse), got {voxel_size!r}")
+    try:
+        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}") from None
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+
+    def result(m):
+        return VoxelCloud(torch.empty((m, 3), dtype=torch.float32, device=dev),
+                          torch.empty((m, 3), dtype=torch.uint8, device=dev) if colors is not None else None,
+                          torch.empty((m,), dtype=torch.int32, device=dev),
+                          torch.empty((m,), dtype=torch.int64, device=dev),
+                          torch.empty((N,), dtype=torch.int64, device=dev))
+    if N == 0:                         # nothing to merge, nothing to launch: empties on the points' device
+        return result(0)
+    if not points.is_cuda:
+        raise RuntimeError("voxel_merge runs on HIP devices only: move the points to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    pts = points.detach().contiguous()
+    cols = colors.detach().contiguous() if colors is not None else None
+    scalars = (float(v), float(inv), float(o[0]), float(o[1]), float(o[2]))
+    ws_bytes = lib.mvsn_voxel_workspace_bytes(N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_voxel_assign(_native.ptr(pts), N, *scalars, _native.ptr(head), _native.ptr(ws), ws_bytes,
+                                            st), "mvsn_voxel_assign")
+        m, status = head.tolist()      # the one host synchronisation: sizes the outputs, carries the status word
+        if status & VOXEL_STATUS_RANGE:
+            raise ValueError(f"voxel_size too small for the cloud's extent: a point lies 2^20 = {VOXEL_CELL_LIMIT} "
+                             f"cells of {float(v):g} or more from the origin {tuple(float(x) for x in o)}")
+        if status:
+            raise RuntimeError(f"voxel_merge: the hash grid overflowed (status {status})")
+        vc = result(m)
+        if m == 0:                     # every point dropped
+            vc.inverse.fill_(-1)
+            return vc
+        accum = torch.empty((m, 8), dtype=torch.int64, device=dev)
+        _native.check(lib.mvsn_voxel_merge(_native.ptr(pts), _native.ptr(cols), N, *scalars, _native.ptr(ws), ws_bytes,
+                                           m, _native.ptr(accum), _native.ptr(vc.points), _native.ptr(vc.colors),
+                                           _native.ptr(vc.count), _native.ptr(vc.first), _native.ptr(vc.inverse), st),
+                      "mvsn_voxel_merge")
+    return vc
 
 
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:

@@ -7,7 +7,11 @@ writes the fused depth and the count map (its neighbour taps are gathered throug
 the logical gather volume), the emit kernel reads the fused depth and writes the points, colours, view and pixel
 arrays.  Prints one JSON line per scene.  The kernel split comes from a rocprofv3 --kernel-trace --stats run of this
 tool.  --confidence: also times the call gated by a seeded random confidence at min_confidence = 0.25 (one more launch,
-mvsn_confidence_mask, in front of the four) and reports it as "gated"."""
+mvsn_confidence_mask, in front of the four) and reports it as "gated".  --voxel: also merges each scene's cloud on a
+voxel grid (fusion.voxel_merge; the voxel is one pixel's footprint at the median fused depth, about one point per
+surface element of a single view) and reports, as "voxel", N, M and ms per call next to the same merge composed from
+torch ops on the device (torch.unique(dim=0, return_inverse=True) on the integer cells + index_add_), timed the same
+way."""
 import argparse
 import json
 import os
@@ -20,7 +24,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import fuse_depthmaps  # noqa: E402
+from multi_view_stereonet_amd.fusion import fuse_depthmaps, voxel_merge  # noqa: E402
 
 SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
 
@@ -45,7 +49,31 @@ def timed(call, steps, warmup):
     return res, times
 
 
-def run(V, H, W, M, steps, warmup, confidence=False):
+def torch_voxel_merge(points, colors, voxel):
+    """The merge from torch ops: the same fp32 cells, then unique over the int64 cell rows and index_add_ sums (float
+    sums in arrival order, rows in cell order, no `first`: what a caller had to write without voxel_merge)."""
+    cells = torch.floor(points * float(np.float32(1) / np.float32(voxel))).to(torch.int64)
+    uniq, inverse = torch.unique(cells, dim=0, return_inverse=True)
+    m = uniq.shape[0]
+    count = torch.zeros(m, dtype=torch.float32, device=points.device).index_add_(
+        0, inverse, torch.ones(points.shape[0], dtype=torch.float32, device=points.device))
+    pos = torch.zeros(m, 3, dtype=torch.float32, device=points.device).index_add_(0, inverse, points)
+    col = torch.zeros(m, 3, dtype=torch.float32, device=points.device).index_add_(0, inverse, colors.to(torch.float32))
+    return pos / count[:, None], (col / count[:, None] + 0.5).to(torch.uint8), count, inverse
+
+
+def run_voxel(res, fx, steps, warmup):
+    voxel = float(np.float32(float(res.depth[res.depth > 0].median()) / fx))    # one pixel's footprint at the median depth
+    vc, times = timed(lambda: voxel_merge(res.points, voxel, colors=res.colors), steps, warmup)
+    tc, ttimes = timed(lambda: torch_voxel_merge(res.points, res.colors, voxel), steps, warmup)
+    N, M = int(res.points.shape[0]), int(vc.points.shape[0])
+    assert int(tc[0].shape[0]) == M and int(vc.count.sum()) == N
+    return {"voxel": {"voxel_size": voxel, "N": N, "M": M, "ms_per_call_median": float(np.median(times)),
+                      "ms_per_call_min": float(np.min(times)), "torch_ms_per_call_median": float(np.median(ttimes)),
+                      "torch_ms_per_call_min": float(np.min(ttimes))}}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -60,7 +88,8 @@ def run(V, H, W, M, steps, warmup, confidence=False):
         gated = {"gated": {"min_confidence": 0.25, "ms_per_call_median": float(np.median(gtimes)),
                            "ms_per_call_min": float(np.min(gtimes)), "points": int(gres.points.shape[0]),
                            "mask_bytes": 5 * V * P + V * P}}
-    return {**gated, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    merged = run_voxel(res, float(sc["K"][0, 0, 0]), steps, warmup) if voxel else {}
+    return {**gated, **merged, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -73,10 +102,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--confidence", action="store_true", help="also time the call gated by a confidence map")
+    ap.add_argument("--voxel", action="store_true", help="also time voxel_merge of the fused cloud, and its torch form")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
-        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence)), flush=True)
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel)), flush=True)
 
 
 if __name__ == "__main__":
