@@ -9,6 +9,10 @@
 // differently in x and y; pinned by tests/golden/g11 (isotropic, centred) and g12 (all of the others).  Which do not:
 // a K with a shear term or any other entry off that form.  One predicate decides (setup_path below); the kernel and the
 // host query mvsn_plane_sweep_setup_path both call it, so a test can assert the path it means to test.
+// On every path a level-4 pixel whose epipolar line is degenerate (norm < 1e-6) contributes 0 * idepth, as in the
+// reference: where that idepth is 0 / 0 (pure forward motion, the pixel on the epipole) the chain's samples and H4 are
+// NaN.  The fp64 evaluation used to drop such a pixel instead (tests/test_setup_poses_gpu.py); for finite idepths
+// the two are the same bits.
 // include/mvsn_hip.h names the call sites replaced.
 #include "mvsn_common.h"
 
@@ -397,11 +401,13 @@ __global__ __launch_bounds__(SETUP_THREADS) void plane_sweep_setup_kernel(
     double A1 = Kt[1] - Kt[2] * (infy + disp * ey);
     double b0 = i2 * disp * ex, b1 = i2 * disp * ey;
     double idp = (A0 * b0 + A1 * b1) / (A0 * A0 + A1 * A1);
-    float idf = (nrm < 1e-6) ? 0.0f : (float)idp;
-    if (idf > 0.0f) {
-      acc += (double)idf;
-      cnt += 1;
-    }
+    // the reference's two masks are PRODUCTS ((~mask).float() * idepth, (x > 0).float() * x): a pixel on the epipole,
+    // whose idepth is 0 / 0, stays a NaN and makes the mean one, as ref32::max_idepth_pixel does; a finite idepth
+    // that is masked or not positive adds a zero, which changes no bit of the sum
+    float idf = (nrm < 1e-6 ? 0.0f : 1.0f) * (float)idp;
+    idf = (idf > 0.0f ? 1.0f : 0.0f) * idf;
+    acc += (double)idf;
+    cnt += idf > 0.0f ? 1 : 0;
   }
   if (ref_samples) {   // the reference's fp32 program per pixel; the sum below in torch's order
     for (int p = tid; p < P; p += SETUP_THREADS) {
