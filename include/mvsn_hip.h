@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MVSN_ABI_VERSION 5
+#define MVSN_ABI_VERSION 6
 
 #define MVSN_E_BADARG (-1)      /* null pointer, non-positive size, unsupported channel count */
 #define MVSN_E_TOOLARGE (-2)    /* shape exceeds what the kernel's LDS/global plan supports */
@@ -141,9 +141,11 @@ size_t mvsn_incremental_cost_volume_workspace_bytes(int n_chains, int rows, int 
                                                                                              features (always, since ABI 3) + the
                                                                                              activation planes that do not fit LDS */
 int mvsn_incremental_cost_volume_form(int rows, int cols);   /* the fused form of this grid: WINOGRAD or DIRECT */
-/* what MVSN_CHAIN_AUTO resolves to for this many chains on this grid (BANDED, WINOGRAD, STEPWISE or DIRECT) in the
- * entry points that put a repair launch behind a banded call (mvsn_incremental_cost_volume_guarded / _bf16), and the
- * workspace `form` needs for num_idepth_samples planes (AUTO allowed: enough for either entry point).
+/* Which form a call runs, on what workspace, is decided in ONE place, the library's resolver; the functions below are
+ * views of it.  mvsn_incremental_cost_volume_form_for: what MVSN_CHAIN_AUTO resolves to for this many chains on this grid
+ * (BANDED, WINOGRAD, STEPWISE or DIRECT) in the entry points that put a repair launch behind a banded call
+ * (mvsn_incremental_cost_volume_guarded / _bf16); ..._workspace_bytes_for: the workspace `form` needs for
+ * num_idepth_samples planes (AUTO allowed: enough for either entry point).
  * The PLAIN mvsn_incremental_cost_volume has no repair launch, so its AUTO is more conservative: on 30x40 / 32x64 it
  * takes the banded form only while the chains fit ONE thin-band pass (17 / 16 chains on 256 CUs) and the
  * co-residency-free STEPWISE form (DIRECT for cols % 4 != 0) beyond -- the multi-pass slab plan holds the whole device
@@ -152,6 +154,16 @@ int mvsn_incremental_cost_volume_form(int rows, int cols);   /* the fused form o
 int mvsn_incremental_cost_volume_form_for(int n_chains, int rows, int cols);
 size_t mvsn_incremental_cost_volume_workspace_bytes_for(int n_chains, int num_idepth_samples, int rows, int cols,
                                                         int form);
+/* Host only, no device call: the resolver itself (ABI 6).  `form`: the requested form (AUTO allowed); `guarded` != 0: for
+ * the entry points with a repair launch (_guarded / _bf16), 0: for the plain one; `coresident_allowed` == 0: AUTO must not
+ * pick the banded form, whose workgroups have to be co-resident (several calls in flight on the device, another process
+ * holding it) -- it falls back to WINOGRAD, STEPWISE or DIRECT.  An explicit WINOGRAD / STEPWISE request on a grid
+ * without that plan is answered with DIRECT and out[6] = 1 (the entry points themselves refuse such a call).
+ * out = { form that runs, repair form (0: no repair launch), workspace bytes, repair-workspace bytes, status offset and
+ * workgroups per chain (BANDED, else 0), redirected, 0 }.  Returns 1, or 0 when the form has no plan for the grid (the
+ * entry points return MVSN_E_TOOLARGE / MVSN_E_BADARG then) or an argument is out of range. */
+int mvsn_incremental_cost_volume_resolve(int n_chains, int num_idepth_samples, int rows, int cols, int form,
+                                         int coresident_allowed, int guarded, size_t out[8]);
 /* MVSN_CHAIN_BANDED only: byte offset, inside the workspace, of the 32-bit status word the launch leaves behind
  * (0 = every inter-workgroup hand-off completed; non-zero = a bounded wait timed out and the outputs are invalid) */
 size_t mvsn_incremental_cost_volume_status_offset(int n_chains, int rows, int cols);

@@ -38,7 +38,7 @@ class TowerDesc(Structure):
 
 CONV_FP32, CONV_BF16X3, CONV_FP32_WINO, CONV_BF16 = 0, 1, 2, 3
 CHAIN_AUTO, CHAIN_DIRECT, CHAIN_WINOGRAD, CHAIN_STEPWISE, CHAIN_BANDED = 0, 1, 2, 3, 4
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 # name -> (restype, argtypes); mirrors include/mvsn_hip.h one to one
@@ -56,6 +56,7 @@ SIGNATURES = {
     "mvsn_incremental_cost_volume_form": (c_int, [c_int] * 2),
     "mvsn_incremental_cost_volume_form_for": (c_int, [c_int] * 3),
     "mvsn_incremental_cost_volume_workspace_bytes_for": (c_size_t, [c_int] * 5),
+    "mvsn_incremental_cost_volume_resolve": (c_int, [c_int] * 7 + [POINTER(c_size_t * 8)]),
     "mvsn_incremental_cost_volume_status_offset": (c_size_t, [c_int] * 3),
     "mvsn_incremental_cost_volume_banded_groups": (c_int, [c_int] * 3),
     "mvsn_incremental_cost_volume": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 4 + [c_size_t, c_int, c_void_p]),

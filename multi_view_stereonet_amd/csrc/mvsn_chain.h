@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mvsn_common.h"
+
 namespace mvsn {
 
 constexpr int CH_W0_FLOATS = 9 * 9 * 2 * 64;  // direct form, conv0: 35 -> 36 input channels = 9 k-steps per tap
@@ -111,6 +113,11 @@ __device__ __forceinline__ bool chain_gate_closed(const ChainArgs &a) {
       (const void *)(a).packed, (const void *)(a).cost, (const void *)(a).mask, (const void *)(a).fvol,               \
       ((a).gate ? (const void *)(a).gate : (const void *)(a).workspace)
 
+// Where the decisions live: which form a call runs, on what workspace and with which repair launch behind it, is decided
+// by ONE host function, chain_resolve (mvsn_chain.hip) -- the AUTO policy and the fall-back when co-resident launches are
+// not allowed included; the entry points and every planning export are calls into it.  The forms below only say whether
+// they have a plan for a grid and what it needs.
+
 // Winograd form: does this coarse grid have a plan (even rows / cols, <= 128 patches, LDS fits)?
 bool chain_wino_supported(int rows, int cols);
 int chain_wino_launch(const ChainArgs &a, int n_chains, hipStream_t stream);
@@ -120,26 +127,27 @@ bool chain_steps_supported(int rows, int cols);
 size_t chain_steps_workspace_bytes(int n_chains, int D, int rows, int cols);
 int chain_steps_launch(const ChainArgs &a, int n_chains, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
-// Banded form (mvsn_chain_band.hip): one chain on several workgroups; coarse grids 16x32, 30x40, 32x64
-bool chain_band_supported(int rows, int cols);
-int chain_band_groups(int n_chains, int rows, int cols);    // workgroups per chain (0: no plan for this grid)
-int chain_band_chains_per_pass(int rows, int cols);        // chains whose workgroups are co-resident (one per CU)
-size_t chain_band_workspace_bytes(int n_chains, int rows, int cols);
-size_t chain_band_status_offset(int n_chains, int rows, int cols);
+// Banded form: one chain on several co-resident workgroups; coarse grids 16x32, 30x40, 32x64.  Its plans are the rows of
+// ONE table: the thin bands and the half split of mvsn_chain_band.hip (256-thread workgroups) and the slabs of
+// mvsn_chain_slab.hip (a few fat bands per chain, 512-thread workgroups -- what the dispatcher launches once more chains
+// are in flight than ONE pass of the thin bands holds).  A row is looked up by grid and kind.
+enum BandKind { BAND_HALF, BAND_THIN, BAND_SLAB };
+struct BandPlan {
+  int rows, cols, kind;
+  int G, threads;                                   // workgroups per chain, threads per workgroup
+  size_t chain_u64, lds_bytes;                      // granule workspace of one chain (u64 units), dynamic LDS
+  void (*kernel[2])(ChainArgs, int, MVSN_VIS10);    // [1]: storing the cost volume as bf16 (ChainArgs::cost_bf16)
+  mutable LdsOptIn opt[2];                          // the LDS opt-in state of either kernel
+};
+constexpr int CHAIN_SLAB_PLANS = 3;
+extern const BandPlan chain_slab_plans[CHAIN_SLAB_PLANS];   // the slab rows (mvsn_chain_slab.hip)
+
+int chain_band_chains_per_pass(int rows, int cols);   // chains of ONE pass of the grid's thin bands (0: no banded plan)
+// the plan a call with this many chains runs: workgroups per chain, byte offset of the status block inside the workspace
+// (which ends 64 bytes behind it); false: the grid has no banded plan
+bool chain_band_layout(int n_chains, int rows, int cols, int *groups, size_t *status_offset);
 void chain_band_debug_flags(int flags);   // test hook, see mvsn_debug_set_band_flags
 int chain_band_launch(const ChainArgs &a, int n_chains, void *workspace, size_t workspace_bytes, int flags,
                       hipStream_t stream);
-
-// Slab plans of the banded form (mvsn_chain_slab.hip): a few fat bands per chain, 512-thread workgroups -- what the
-// banded dispatcher launches once more chains are in flight than ONE pass of the thin-band plan holds
-struct SlabPlan {
-  int G, threads;
-  size_t chain_u64, lds_bytes;
-  void (*kernel)(ChainArgs, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                 const void *, const void *, const void *, const void *);
-  void (*kernel16)(ChainArgs, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                   const void *, const void *, const void *, const void *);   // ... storing the cost volume as bf16
-};
-bool chain_slab_plan(int rows, int cols, SlabPlan *p);
 
 }  // namespace mvsn

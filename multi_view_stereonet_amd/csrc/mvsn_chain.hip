@@ -20,6 +20,9 @@
 //                       ch 0..2 image plane d, ch 3..34 features, ch 35 zero (K padding).
 // When that exceeds 160 KiB the activation planes move to a per-chain global workspace
 // (L2-resident); the code path is otherwise identical.
+#include <type_traits>
+#include <utility>
+
 #include "mvsn_chain.h"
 #include "mvsn_resident.h"
 #include "mvsn_conv_wino.h"
@@ -569,6 +572,183 @@ static int chain_cs(int rows, int cols) {
   return cs;
 }
 
+// ---- host side: the direct form's plan ----------------------------------------------------------------------------
+struct DirectPlan {
+  int TP;             // 16-pixel tiles per wave
+  bool lds_act, ok;   // activation planes in LDS (else in the global workspace, staged by slabs); the form runs this grid
+  size_t lds_bytes;
+};
+
+static DirectPlan chain_direct_plan(int rows, int cols) {
+  const int P = rows * cols, CS = chain_cs(rows, cols);
+  const int act_floats = (cols + 2) + 36 * CS, slab_floats = (cols + 2) + 4 * CS;
+  DirectPlan p;
+  p.TP = ((P + 15) / 16 + CH_WAVES - 1) / CH_WAVES;
+  p.lds_act = chain_lds_bytes(P, act_floats, true) <= 160 * 1024;
+  p.lds_bytes = chain_lds_bytes(P, act_floats, p.lds_act, slab_floats);
+  p.ok = p.TP <= 8 && (p.lds_act ? p.TP <= 3 : slab_floats <= 9 * CH_THREADS);
+  return p;
+}
+
+// per chain: the step's moved features (32 x P, always) + the activation planes where they do not fit LDS
+static size_t chain_direct_bytes(int n_chains, int rows, int cols) {
+  const size_t act_floats = (cols + 2) + 36 * (size_t)chain_cs(rows, cols), mv_floats = (size_t)32 * rows * cols;
+  return (size_t)n_chains * (mv_floats + (chain_direct_plan(rows, cols).lds_act ? 0 : act_floats)) * sizeof(float);
+}
+
+// ---- the resolver: what a call runs ---------------------------------------------------------------------------------
+struct ChainPlan {
+  bool ok;                  // the form has a plan for this grid (the entry points refuse the call otherwise)
+  bool redirected;          // `redirect` replaced the requested form (see chain_resolve)
+  int form;                 // the form that runs (never AUTO once the sizes are valid)
+  int repair_form;          // the gated single-launch form behind a guarded banded call; 0: no repair launch
+  int groups;               // banded: workgroups per chain of the plan that runs
+  size_t workspace_bytes, repair_workspace_bytes;
+  size_t status_offset;     // banded: byte offset of the status word inside the workspace
+};
+
+// THE place that decides which form a call runs and what it needs -- the entry points, the planning exports and the
+// module all ask here.  `guarded`: a gated repair launch follows a banded call (mvsn_incremental_cost_volume_guarded /
+// _bf16); `coresident_allowed`: AUTO may pick a form whose workgroups must be co-resident (false: lanes on several
+// streams, a latched module, another process owning the device's co-resident launches); `redirect`: the module's
+// rule for an explicit Winograd / stepwise request on a grid without that plan -- the direct form runs (the C entry
+// points pass false and refuse such a call).
+// MVSN_CHAIN_AUTO:
+//   16x32 (plane-resident plan): banded -- several workgroups per chain -- only while all chains fit the chip in ONE
+//     pass (beyond 64 chains the plane-resident kernel is faster), then Winograd;
+//   30x40 / 32x64 (no plane-resident plan), guarded: banded for any number of chains -- thin bands while they fit one
+//     pass, the slab plan beyond; the stepwise form, which sends the plane through HBM every step, is no longer AUTO's
+//     choice there;
+//   ... unguarded (the PLAIN entry point): the multi-pass slab launches need the device to themselves for milliseconds
+//     at a stretch and a time-out without repair would leave a NaN-poisoned cost slice, so beyond ONE thin-band pass
+//     AUTO stays on the co-residency-free forms (the round-4 policy; a caller that wants the slab plan asks for
+//     MVSN_CHAIN_BANDED or uses the guarded entry);
+//   otherwise Winograd, then stepwise -- one plane per round of full-chip launches, whatever the number of chains
+//     (re-measured in round 3 with tools/chain_bench.py: 30x40, 256 / 512 chains 25.4 / 48.0 ms against the direct
+//     form's 41.5 / 86.8) --, then direct (one workgroup per chain, planes in a global workspace: cols % 4 != 0).
+static ChainPlan chain_resolve(int n_chains, int D, int rows, int cols, int requested, bool guarded, bool coresident_allowed,
+                               bool redirect = false) {
+  ChainPlan p = {};
+  p.form = requested;
+  if (n_chains <= 0 || rows <= 0 || cols <= 0 || requested < MVSN_CHAIN_AUTO || requested > MVSN_CHAIN_BANDED) return p;
+  const bool wino = chain_wino_supported(rows, cols), steps = chain_steps_supported(rows, cols);
+  if (requested == MVSN_CHAIN_AUTO) {
+    const int cap = chain_band_chains_per_pass(rows, cols);
+    const bool banded = coresident_allowed && cap > 0 && (n_chains <= cap || (guarded && !wino));
+    p.form = banded ? MVSN_CHAIN_BANDED : wino ? MVSN_CHAIN_WINOGRAD : steps ? MVSN_CHAIN_STEPWISE : MVSN_CHAIN_DIRECT;
+  } else if (redirect && ((requested == MVSN_CHAIN_WINOGRAD && !wino) || (requested == MVSN_CHAIN_STEPWISE && !steps))) {
+    p.form = MVSN_CHAIN_DIRECT, p.redirected = true;
+  }
+  switch (p.form) {
+    case MVSN_CHAIN_WINOGRAD: p.ok = wino; break;
+    case MVSN_CHAIN_STEPWISE: p.ok = steps, p.workspace_bytes = chain_steps_workspace_bytes(n_chains, D, rows, cols); break;
+    case MVSN_CHAIN_BANDED:
+      p.ok = chain_band_layout(n_chains, rows, cols, &p.groups, &p.status_offset);
+      if (p.ok) p.workspace_bytes = p.status_offset + 64;
+      if (guarded) {   // repaired by the plane-resident Winograd kernel where the grid has that plan (16x32), the direct kernel elsewhere
+        p.repair_form = wino ? MVSN_CHAIN_WINOGRAD : MVSN_CHAIN_DIRECT;
+        p.repair_workspace_bytes = wino ? 0 : chain_direct_bytes(n_chains, rows, cols);
+      }
+      break;
+    default: p.ok = chain_direct_plan(rows, cols).ok, p.workspace_bytes = chain_direct_bytes(n_chains, rows, cols); break;
+  }
+  return p;
+}
+
+#ifdef MVSN_CHAIN_STAMPS
+static unsigned long long *g_chain_stamps = nullptr;
+#endif
+
+// f(integral_constant<TP>) for the TP == tp of the list: the fold that turns the run-time tile count into a compile-time one
+template <class F, int... TPS>
+static int chain_with_tp(int tp, std::integer_sequence<int, TPS...>, F &&f) {
+  int rc = MVSN_E_TOOLARGE;
+  (void)((tp == TPS && ((rc = f(std::integral_constant<int, TPS>{})), true)) || ...);
+  return rc;
+}
+
+static int chain_direct_launch(const char *entry, ChainArgs a, int n_chains, void *workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
+  const DirectPlan plan = chain_direct_plan(a.rows, a.cols);
+  MVSN_REQUIRE(plan.TP <= 8, MVSN_E_TOOLARGE, "%s: %dx%d coarse grid (%d px) exceeds the 2048 px plan", entry, a.rows, a.cols,
+               a.rows * a.cols);
+  const size_t need = chain_direct_bytes(n_chains, a.rows, a.cols);
+  MVSN_REQUIRE(workspace && workspace_bytes >= need, MVSN_E_WORKSPACE, "%s: workspace of %zu bytes required", entry, need);
+  MVSN_REQUIRE(plan.ok, MVSN_E_TOOLARGE, "%s: coarse grid too large for the slab staging plan", entry);
+  a.workspace = (float *)workspace;
+  // the kernel of (TP, LDS_ACT, C16): instantiated here, once per combination, with its own LdsOptIn
+  auto launch = [&](auto tp, auto lds_act, auto c16) -> int {
+    const auto kernel = chain_kernel<decltype(tp)::value, decltype(lds_act)::value, decltype(c16)::value>;
+    static LdsOptIn opt;
+    if (int rc = ensure_lds(opt, (const void *)kernel, plan.lds_bytes, entry)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(n_chains), dim3(CH_THREADS), plan.lds_bytes, stream, a, CHAIN_VISIBLE_G(a));
+    return 0;
+  };
+  auto tiled = [&](auto tp, auto lds_act) -> int {   // (bf16 feature tier: its own instantiations)
+    return a.cost_bf16 ? launch(tp, lds_act, std::true_type{}) : launch(tp, lds_act, std::false_type{});
+  };
+  if (int rc = plan.lds_act
+                   ? chain_with_tp(plan.TP, std::integer_sequence<int, 1, 2, 3>{}, [&](auto tp) { return tiled(tp, std::true_type{}); })
+                   : chain_with_tp(plan.TP, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>{},
+                                   [&](auto tp) { return tiled(tp, std::false_type{}); }))
+    return rc;
+  return check_launch(entry);
+}
+
+// One resolved form of the chain; a.gate != null: as a gated repair launch (one of the single-launch forms).
+static int chain_launch(const char *entry, const ChainArgs &a, int n_chains, void *workspace, size_t workspace_bytes,
+                        const ChainPlan &p, hipStream_t stream) {
+  switch (p.form) {
+    case MVSN_CHAIN_WINOGRAD:
+      MVSN_REQUIRE(p.ok, MVSN_E_TOOLARGE, "%s: no Winograd plan for a %dx%d coarse grid", entry, a.rows, a.cols);
+      return chain_wino_launch(a, n_chains, stream);
+    case MVSN_CHAIN_STEPWISE:
+      MVSN_REQUIRE(!a.cost_bf16, MVSN_E_BADARG, "%s: the stepwise form has no bf16 cost-volume variant", entry);
+      return chain_steps_launch(a, n_chains, workspace, workspace_bytes, stream);
+    case MVSN_CHAIN_BANDED:
+      MVSN_REQUIRE(p.ok, MVSN_E_TOOLARGE, "%s: the banded form has no plan for a %dx%d coarse grid (16x32, 30x40, 32x64)",
+                   entry, a.rows, a.cols);
+      return chain_band_launch(a, n_chains, workspace, workspace_bytes, 0, stream);
+    default: return chain_direct_launch(entry, a, n_chains, workspace, workspace_bytes, stream);
+  }
+}
+
+// The C arguments of an entry point as the kernels take them.
+static ChainArgs chain_args(const float *src_image_lvl4, const float *H_lvl4, const float *H_inc, const float *plane0_features,
+                            const float *left_features, const float *refiner_packed, int batch, int num_idepth_samples,
+                            int rows, int cols, void *cost_volume, bool cost_bf16, uint8_t *mask_volume,
+                            float *feature_volume) {
+  ChainArgs a = {};
+  a.src = src_image_lvl4, a.H = H_lvl4, a.Hinc = H_inc, a.f0 = plane0_features, a.fl = left_features;
+  a.packed = refiner_packed, a.cost = (float *)cost_volume, a.mask = mask_volume, a.fvol = feature_volume;
+  a.B = batch, a.D = num_idepth_samples, a.rows = rows, a.cols = cols, a.CS = chain_cs(rows, cols);
+  a.cost_bf16 = cost_bf16 ? 1 : 0;
+#ifdef MVSN_CHAIN_STAMPS   // tuning builds only (tools/chain_phases.py): device pointer to 64 x u64 cycle stamps
+  a.dbg = g_chain_stamps;
+#endif
+  return a;
+}
+
+// The body of the three entry points: the resolved form and, behind a guarded banded call, its gated repair launch.
+static int chain_entry(const char *entry, ChainArgs a, int n_chains, void *workspace, size_t workspace_bytes, int form,
+                       bool guarded, void *repair_workspace, size_t repair_workspace_bytes, unsigned *sticky_status,
+                       mvsn_stream_t stream) {
+  MVSN_REQUIRE(a.src && a.H && a.Hinc && a.f0 && a.fl && a.packed && a.cost && a.mask, MVSN_E_BADARG, "%s: null pointer", entry);
+  MVSN_REQUIRE(n_chains > 0 && a.B > 0 && a.D >= 1 && a.rows > 0 && a.cols > 0, MVSN_E_BADARG, "%s: bad sizes", entry);
+  MVSN_REQUIRE(form >= 0 && form <= 4, MVSN_E_BADARG, "%s: form must be 0 .. 4", entry);
+  const ChainPlan p = chain_resolve(n_chains, a.D, a.rows, a.cols, form, guarded, true);
+  // everything the repair launch needs is validated BEFORE the banded launch is enqueued: an error return must not
+  // leave an unrepaired banded chain (NaN on a time-out) behind on the stream
+  MVSN_REQUIRE(!p.repair_workspace_bytes || (repair_workspace && repair_workspace_bytes >= p.repair_workspace_bytes),
+               MVSN_E_WORKSPACE, "%s: repair workspace of %zu bytes required", entry, p.repair_workspace_bytes);
+  if (int rc = chain_launch(entry, a, n_chains, workspace, workspace_bytes, p, (hipStream_t)stream)) return rc;
+  if (!p.repair_form) return 0;   // (the other forms have no inter-workgroup hand-offs to time out)
+  a.gate = reinterpret_cast<const unsigned *>(static_cast<const char *>(workspace) + p.status_offset);
+  a.sticky = sticky_status;
+  return chain_launch(entry, a, n_chains, repair_workspace, repair_workspace_bytes,
+                      chain_resolve(n_chains, a.D, a.rows, a.cols, p.repair_form, false, true), (hipStream_t)stream);
+}
+
 }  // namespace mvsn
 
 extern "C" size_t mvsn_feature_refiner_packed_floats(void) { return mvsn::PACKED_FLOATS; }
@@ -591,80 +771,50 @@ extern "C" int mvsn_pack_feature_refiner(const float *conv0_w, const float *conv
   return mvsn::wino_pack_2d(final_w, 32, u + mvsn::CS_U0_FLOATS + mvsn::CS_U1_FLOATS, (hipStream_t)stream);
 }
 
+// ---- planning exports: calls into chain_resolve ---------------------------------------------------------------------
+extern "C" int mvsn_incremental_cost_volume_resolve(int n_chains, int num_idepth_samples, int rows, int cols, int form,
+                                                    int coresident_allowed, int guarded, size_t out[8]) {
+  if (!out) return 0;
+  const mvsn::ChainPlan p =
+      mvsn::chain_resolve(n_chains, num_idepth_samples, rows, cols, form, guarded != 0, coresident_allowed != 0, true);
+  out[0] = (size_t)p.form, out[1] = (size_t)p.repair_form, out[2] = p.workspace_bytes, out[3] = p.repair_workspace_bytes;
+  out[4] = p.status_offset, out[5] = (size_t)p.groups, out[6] = p.redirected ? 1 : 0, out[7] = 0;
+  return p.ok ? 1 : 0;
+}
+
 extern "C" int mvsn_incremental_cost_volume_form(int rows, int cols) {
-  return mvsn::chain_wino_supported(rows, cols) ? MVSN_CHAIN_WINOGRAD : MVSN_CHAIN_DIRECT;
+  return mvsn::chain_resolve(1, 1, rows, cols, MVSN_CHAIN_WINOGRAD, false, true).ok ? MVSN_CHAIN_WINOGRAD : MVSN_CHAIN_DIRECT;
 }
 
 extern "C" size_t mvsn_incremental_cost_volume_workspace_bytes(int n_chains, int rows, int cols) {
-  if (n_chains <= 0 || rows <= 0 || cols <= 0) return 0;
-  const int CS = mvsn::chain_cs(rows, cols);
-  const int act_floats = (cols + 2) + 36 * CS;
-  // per chain: the step's moved features (32 x P, always) + the activation planes where they do not fit LDS
-  const size_t mv_floats = (size_t)32 * rows * cols;
-  if (mvsn::chain_lds_bytes(rows * cols, act_floats, true) <= 160 * 1024) return (size_t)n_chains * mv_floats * sizeof(float);
-  return (size_t)n_chains * (act_floats + mv_floats) * sizeof(float);
-}
-
-// What MVSN_CHAIN_AUTO resolves to for this many chains on this coarse grid -- in the entry points that put a gated repair
-// launch behind a banded call (mvsn_incremental_cost_volume_guarded / _bf16; what the module calls).
-static int chain_auto_form(int n_chains, int rows, int cols) {
-  if (mvsn::chain_band_supported(rows, cols)) {
-    // 30x40 / 32x64 (no plane-resident plan): the banded form for any number of chains -- thin bands while they fit one
-    // pass, the slab plan (3 / 4 fat bands per chain resident in LDS, mvsn_chain_slab.hip) beyond; the stepwise form, which
-    // sends the plane through HBM every step, is no longer AUTO's choice there
-    if (!mvsn::chain_wino_supported(rows, cols)) return MVSN_CHAIN_BANDED;
-    // 16x32: several workgroups per chain only while all chains fit the chip in ONE pass (beyond 64 chains the
-    // plane-resident kernel is faster)
-    const int cap = mvsn::chain_band_chains_per_pass(rows, cols);
-    if (cap > 0 && n_chains <= cap) return MVSN_CHAIN_BANDED;
-  }
-  if (mvsn::chain_wino_supported(rows, cols)) return MVSN_CHAIN_WINOGRAD;
-  // no plane-resident plan: one plane per round of full-chip launches, whatever the number of chains (re-measured in
-  // round 3 with tools/chain_bench.py: 30x40, 256 / 512 chains 25.4 / 48.0 ms against the direct form's 41.5 / 86.8;
-  // the direct form -- one workgroup per chain, planes in a global workspace -- remains for cols % 4 != 0)
-  if (mvsn::chain_steps_supported(rows, cols)) return MVSN_CHAIN_STEPWISE;
-  return MVSN_CHAIN_DIRECT;
-}
-
-// ... and in the PLAIN entry point (mvsn_incremental_cost_volume), which has no repair launch behind it: the multi-pass
-// slab launches need the device to themselves for milliseconds at a stretch and a time-out there would leave a
-// NaN-poisoned cost slice, so beyond ONE thin-band pass the plain AUTO stays on the co-residency-free forms (the
-// round-4 policy).  A caller that wants the slab plan asks for MVSN_CHAIN_BANDED or uses the guarded entry.
-static int chain_auto_form_unguarded(int n_chains, int rows, int cols) {
-  const int form = chain_auto_form(n_chains, rows, cols);
-  if (form == MVSN_CHAIN_BANDED && !mvsn::chain_wino_supported(rows, cols)) {
-    const int cap = mvsn::chain_band_chains_per_pass(rows, cols);
-    if (cap <= 0 || n_chains > cap) return mvsn::chain_steps_supported(rows, cols) ? MVSN_CHAIN_STEPWISE : MVSN_CHAIN_DIRECT;
-  }
-  return form;
+  return mvsn::chain_resolve(n_chains, 1, rows, cols, MVSN_CHAIN_DIRECT, false, true).workspace_bytes;
 }
 
 extern "C" int mvsn_incremental_cost_volume_form_for(int n_chains, int rows, int cols) {
   if (n_chains <= 0 || rows <= 0 || cols <= 0) return MVSN_CHAIN_DIRECT;
-  return chain_auto_form(n_chains, rows, cols);
+  return mvsn::chain_resolve(n_chains, 1, rows, cols, MVSN_CHAIN_AUTO, true, true).form;
 }
 
 extern "C" size_t mvsn_incremental_cost_volume_workspace_bytes_for(int n_chains, int num_idepth_samples, int rows,
                                                                    int cols, int form) {
-  if (n_chains <= 0 || rows <= 0 || cols <= 0 || num_idepth_samples <= 0) return 0;
-  if (form == MVSN_CHAIN_AUTO) {      // whichever entry point resolves it (they differ beyond one thin-band pass)
-    const int fg = chain_auto_form(n_chains, rows, cols), fu = chain_auto_form_unguarded(n_chains, rows, cols);
-    const size_t g = mvsn_incremental_cost_volume_workspace_bytes_for(n_chains, num_idepth_samples, rows, cols, fg);
-    const size_t u = fu == fg ? g : mvsn_incremental_cost_volume_workspace_bytes_for(n_chains, num_idepth_samples, rows, cols, fu);
-    return g > u ? g : u;
-  }
-  if (form == MVSN_CHAIN_STEPWISE) return mvsn::chain_steps_workspace_bytes(n_chains, num_idepth_samples, rows, cols);
-  if (form == MVSN_CHAIN_BANDED) return mvsn::chain_band_workspace_bytes(n_chains, rows, cols);
-  if (form == MVSN_CHAIN_WINOGRAD) return 0;
-  return mvsn_incremental_cost_volume_workspace_bytes(n_chains, rows, cols);
+  if (num_idepth_samples <= 0) return 0;
+  const size_t g = mvsn::chain_resolve(n_chains, num_idepth_samples, rows, cols, form, true, true).workspace_bytes;
+  if (form != MVSN_CHAIN_AUTO) return g;
+  // AUTO: enough for whichever entry point resolves it (the plain one differs beyond one thin-band pass)
+  const size_t u = mvsn::chain_resolve(n_chains, num_idepth_samples, rows, cols, form, false, true).workspace_bytes;
+  return g > u ? g : u;
 }
 
 extern "C" size_t mvsn_incremental_cost_volume_status_offset(int n_chains, int rows, int cols) {
-  return n_chains > 0 ? mvsn::chain_band_status_offset(n_chains, rows, cols) : 0;
+  return mvsn::chain_resolve(n_chains, 1, rows, cols, MVSN_CHAIN_BANDED, false, true).status_offset;
 }
 
 extern "C" int mvsn_incremental_cost_volume_banded_groups(int n_chains, int rows, int cols) {
-  return n_chains > 0 ? mvsn::chain_band_groups(n_chains, rows, cols) : 0;
+  return mvsn::chain_resolve(n_chains, 1, rows, cols, MVSN_CHAIN_BANDED, false, true).groups;
+}
+
+extern "C" size_t mvsn_incremental_cost_volume_repair_workspace_bytes(int n_chains, int rows, int cols) {
+  return mvsn::chain_resolve(n_chains, 1, rows, cols, MVSN_CHAIN_BANDED, true, true).repair_workspace_bytes;
 }
 
 extern "C" int mvsn_debug_set_band_flags(int flags) {
@@ -673,144 +823,23 @@ extern "C" int mvsn_debug_set_band_flags(int flags) {
 }
 
 #ifdef MVSN_CHAIN_STAMPS
-static unsigned long long *g_chain_stamps = nullptr;
 extern "C" int mvsn_debug_set_chain_stamps(void *buf) {
-  g_chain_stamps = (unsigned long long *)buf;
+  mvsn::g_chain_stamps = (unsigned long long *)buf;
   return 0;
 }
 #endif
 
-// The chain in `form` (resolved), optionally as a gated repair launch (gate != null: one of the single-launch forms).
-static int chain_run(const float *src_image_lvl4, const float *H_lvl4, const float *H_inc, const float *plane0_features,
-                     const float *left_features, const float *refiner_packed, int n_chains, int batch,
-                     int num_idepth_samples, int rows, int cols, float *cost_volume, uint8_t *mask_volume,
-                     float *feature_volume, void *workspace, size_t workspace_bytes, int form, const unsigned *gate,
-                     unsigned *sticky, mvsn_stream_t stream, int cost_bf16 = 0) {
-  using namespace mvsn;
-  MVSN_REQUIRE(src_image_lvl4 && H_lvl4 && H_inc && plane0_features && left_features && refiner_packed &&
-                   cost_volume && mask_volume,
-               MVSN_E_BADARG, "mvsn_incremental_cost_volume: null pointer");
-  MVSN_REQUIRE(n_chains > 0 && batch > 0 && num_idepth_samples >= 1 && rows > 0 && cols > 0, MVSN_E_BADARG,
-               "mvsn_incremental_cost_volume: bad sizes");
-  MVSN_REQUIRE(form >= 0 && form <= 4, MVSN_E_BADARG, "mvsn_incremental_cost_volume: form must be 0 .. 4");
-  if (form == MVSN_CHAIN_AUTO) form = chain_auto_form_unguarded(n_chains, rows, cols);   // (the guarded entries resolve AUTO themselves)
-  MVSN_REQUIRE(form != MVSN_CHAIN_WINOGRAD || chain_wino_supported(rows, cols), MVSN_E_TOOLARGE,
-               "mvsn_incremental_cost_volume: no Winograd plan for a %dx%d coarse grid", rows, cols);
-  const bool wino = form == MVSN_CHAIN_WINOGRAD || (form == MVSN_CHAIN_AUTO && chain_wino_supported(rows, cols));
-  const int P = rows * cols;
-  const int tiles = (P + 15) / 16;
-  const int TP = (tiles + CH_WAVES - 1) / CH_WAVES;
-  MVSN_REQUIRE(form != MVSN_CHAIN_BANDED || chain_band_supported(rows, cols), MVSN_E_TOOLARGE,
-               "mvsn_incremental_cost_volume: the banded form has no plan for a %dx%d coarse grid (16x32, 30x40, 32x64)", rows, cols);
-  MVSN_REQUIRE(wino || form == MVSN_CHAIN_STEPWISE || form == MVSN_CHAIN_BANDED || TP <= 8, MVSN_E_TOOLARGE,
-               "mvsn_incremental_cost_volume: %dx%d coarse grid (%d px) exceeds the 2048 px plan", rows, cols, P);
-  MVSN_REQUIRE(gate == nullptr || wino || form == MVSN_CHAIN_DIRECT, MVSN_E_BADARG,
-               "mvsn_incremental_cost_volume: a repair launch runs the Winograd or the direct form");
-  MVSN_REQUIRE(!cost_bf16 || form != MVSN_CHAIN_STEPWISE, MVSN_E_BADARG,
-               "mvsn_incremental_cost_volume_bf16: the stepwise form has no bf16 cost-volume variant");
-  ChainArgs a;
-  a.cost_bf16 = cost_bf16 ? 1 : 0;
-  a.chain0 = 0;
-  a.ws_chains = 0;
-  a.gate = gate;
-  a.sticky = sticky;
-  a.src = src_image_lvl4;
-  a.H = H_lvl4;
-  a.Hinc = H_inc;
-  a.f0 = plane0_features;
-  a.fl = left_features;
-  a.packed = refiner_packed;
-  a.cost = cost_volume;
-  a.mask = mask_volume;
-  a.fvol = feature_volume;
-  a.B = batch;
-  a.D = num_idepth_samples;
-  a.rows = rows;
-  a.cols = cols;
-  a.CS = chain_cs(rows, cols);
-  a.dbg = nullptr;
-#ifdef MVSN_CHAIN_STAMPS   // tuning builds only (tools/chain_phases.py): device pointer to 64 x u64 cycle stamps
-  a.dbg = g_chain_stamps;
-#endif
-  if (form == MVSN_CHAIN_STEPWISE) {
-    a.workspace = nullptr;
-    return chain_steps_launch(a, n_chains, workspace, workspace_bytes, (hipStream_t)stream);
-  }
-  if (form == MVSN_CHAIN_BANDED) return chain_band_launch(a, n_chains, workspace, workspace_bytes, 0, (hipStream_t)stream);
-  if (wino) {
-    a.workspace = nullptr;
-    return chain_wino_launch(a, n_chains, (hipStream_t)stream);
-  }
-  const int act_floats = (cols + 2) + 36 * a.CS;
-  const bool lds_act = chain_lds_bytes(P, act_floats, true) <= 160 * 1024;
-  const size_t need = mvsn_incremental_cost_volume_workspace_bytes(n_chains, rows, cols);
-  MVSN_REQUIRE(workspace && workspace_bytes >= need, MVSN_E_WORKSPACE,
-               "mvsn_incremental_cost_volume: workspace of %zu bytes required", need);
-  a.workspace = (float *)workspace;
-  const int slab_floats = (cols + 2) + 4 * a.CS;
-  MVSN_REQUIRE(lds_act || slab_floats <= 9 * CH_THREADS, MVSN_E_TOOLARGE,
-               "mvsn_incremental_cost_volume: coarse grid too large for the slab staging plan");
-  const size_t lds = chain_lds_bytes(P, act_floats, lds_act, slab_floats);
-
-#define MVSN_CHAIN_LAUNCH(TPV, LDSV)                                                                           \
-  do {                                                                                                         \
-    if (a.cost_bf16) {   /* (bf16 feature tier: its own instantiation and LDS opt-in) */                        \
-      auto kern16 = chain_kernel<TPV, LDSV, true>;                                                             \
-      static LdsOptIn opt16;                                                                                   \
-      if (int rc = ensure_lds(opt16, (const void *)kern16, lds, "mvsn_incremental_cost_volume")) return rc;    \
-      hipLaunchKernelGGL(kern16, dim3(n_chains), dim3(CH_THREADS), lds, (hipStream_t)stream, a, CHAIN_VISIBLE_G(a)); \
-      break;                                                                                                   \
-    }                                                                                                          \
-    auto kern = chain_kernel<TPV, LDSV, false>;                                                                \
-    static LdsOptIn opt;                                                                                       \
-    if (int rc = ensure_lds(opt, (const void *)kern, lds, "mvsn_incremental_cost_volume")) return rc;          \
-    hipLaunchKernelGGL(kern, dim3(n_chains), dim3(CH_THREADS), lds, (hipStream_t)stream, a, CHAIN_VISIBLE_G(a));    \
-  } while (0)
-
-  MVSN_REQUIRE(!lds_act || TP <= 3, MVSN_E_TOOLARGE, "mvsn_incremental_cost_volume: internal plan error");
-  if (lds_act) {
-    switch (TP) {
-      case 1: MVSN_CHAIN_LAUNCH(1, true); break;
-      case 2: MVSN_CHAIN_LAUNCH(2, true); break;
-      default: MVSN_CHAIN_LAUNCH(3, true); break;
-    }
-  } else {
-    switch (TP) {
-      case 1: MVSN_CHAIN_LAUNCH(1, false); break;
-      case 2: MVSN_CHAIN_LAUNCH(2, false); break;
-      case 3: MVSN_CHAIN_LAUNCH(3, false); break;
-      case 4: MVSN_CHAIN_LAUNCH(4, false); break;
-      case 5: MVSN_CHAIN_LAUNCH(5, false); break;
-      case 6: MVSN_CHAIN_LAUNCH(6, false); break;
-      case 7: MVSN_CHAIN_LAUNCH(7, false); break;
-      default: MVSN_CHAIN_LAUNCH(8, false); break;
-    }
-  }
-#undef MVSN_CHAIN_LAUNCH
-  return check_launch("mvsn_incremental_cost_volume");
-}
-
+// ---- the entry points (include/mvsn_hip.h) --------------------------------------------------------------------------
 extern "C" int mvsn_incremental_cost_volume(const float *src_image_lvl4, const float *H_lvl4, const float *H_inc,
                                             const float *plane0_features, const float *left_features,
                                             const float *refiner_packed, int n_chains, int batch,
                                             int num_idepth_samples, int rows, int cols, float *cost_volume,
                                             uint8_t *mask_volume, float *feature_volume, void *workspace,
                                             size_t workspace_bytes, int form, mvsn_stream_t stream) {
-  return chain_run(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed, n_chains, batch,
-                   num_idepth_samples, rows, cols, cost_volume, mask_volume, feature_volume, workspace, workspace_bytes,
-                   form, nullptr, nullptr, stream);
-}
-
-// The single-launch form a banded call is repaired with: the plane-resident Winograd kernel where the grid has that plan
-// (16x32), the direct kernel (planes in a global workspace) elsewhere.
-static int chain_repair_form(int rows, int cols) {
-  return mvsn::chain_wino_supported(rows, cols) ? MVSN_CHAIN_WINOGRAD : MVSN_CHAIN_DIRECT;
-}
-
-extern "C" size_t mvsn_incremental_cost_volume_repair_workspace_bytes(int n_chains, int rows, int cols) {
-  if (n_chains <= 0 || rows <= 0 || cols <= 0) return 0;
-  if (chain_repair_form(rows, cols) == MVSN_CHAIN_WINOGRAD) return 0;
-  return mvsn_incremental_cost_volume_workspace_bytes(n_chains, rows, cols);
+  const mvsn::ChainArgs a = mvsn::chain_args(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed,
+                                             batch, num_idepth_samples, rows, cols, cost_volume, false, mask_volume, feature_volume);
+  return mvsn::chain_entry("mvsn_incremental_cost_volume", a, n_chains, workspace, workspace_bytes, form, false, nullptr, 0,
+                           nullptr, stream);
 }
 
 extern "C" int mvsn_incremental_cost_volume_guarded(const float *src_image_lvl4, const float *H_lvl4, const float *H_inc,
@@ -821,26 +850,10 @@ extern "C" int mvsn_incremental_cost_volume_guarded(const float *src_image_lvl4,
                                                     size_t workspace_bytes, int form, void *repair_workspace,
                                                     size_t repair_workspace_bytes, unsigned *sticky_status,
                                                     mvsn_stream_t stream) {
-  using namespace mvsn;
-  if (form == MVSN_CHAIN_AUTO && n_chains > 0 && rows > 0 && cols > 0) form = chain_auto_form(n_chains, rows, cols);
-  // everything the repair launch needs is validated BEFORE the banded launch is enqueued: an error return must not
-  // leave an unrepaired banded chain (NaN on a time-out) behind on the stream
-  size_t need = 0;
-  if (form == MVSN_CHAIN_BANDED && n_chains > 0 && rows > 0 && cols > 0) {
-    need = mvsn_incremental_cost_volume_repair_workspace_bytes(n_chains, rows, cols);
-    MVSN_REQUIRE(need == 0 || (repair_workspace && repair_workspace_bytes >= need), MVSN_E_WORKSPACE,
-                 "mvsn_incremental_cost_volume_guarded: repair workspace of %zu bytes required", need);
-  }
-  if (int rc = chain_run(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed, n_chains, batch,
-                         num_idepth_samples, rows, cols, cost_volume, mask_volume, feature_volume, workspace,
-                         workspace_bytes, form, nullptr, nullptr, stream))
-    return rc;
-  if (form != MVSN_CHAIN_BANDED) return 0;   // the other forms have no inter-workgroup hand-offs to time out
-  const unsigned *gate = reinterpret_cast<const unsigned *>(static_cast<const char *>(workspace) +
-                                                            chain_band_status_offset(n_chains, rows, cols));
-  return chain_run(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed, n_chains, batch,
-                   num_idepth_samples, rows, cols, cost_volume, mask_volume, feature_volume, repair_workspace,
-                   repair_workspace_bytes, chain_repair_form(rows, cols), gate, sticky_status, stream);
+  const mvsn::ChainArgs a = mvsn::chain_args(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed,
+                                             batch, num_idepth_samples, rows, cols, cost_volume, false, mask_volume, feature_volume);
+  return mvsn::chain_entry("mvsn_incremental_cost_volume_guarded", a, n_chains, workspace, workspace_bytes, form, true,
+                           repair_workspace, repair_workspace_bytes, sticky_status, stream);
 }
 
 // The guarded call with the cost volume stored as bf16 (the bf16 feature tier, BASELINE config 5; include/mvsn_hip.h).
@@ -852,24 +865,8 @@ extern "C" int mvsn_incremental_cost_volume_bf16(const float *src_image_lvl4, co
                                                     size_t workspace_bytes, int form, void *repair_workspace,
                                                     size_t repair_workspace_bytes, unsigned *sticky_status,
                                                     mvsn_stream_t stream) {
-  using namespace mvsn;
-  if (form == MVSN_CHAIN_AUTO && n_chains > 0 && rows > 0 && cols > 0) form = chain_auto_form(n_chains, rows, cols);
-  // everything the repair launch needs is validated BEFORE the banded launch is enqueued: an error return must not
-  // leave an unrepaired banded chain (NaN on a time-out) behind on the stream
-  size_t need = 0;
-  if (form == MVSN_CHAIN_BANDED && n_chains > 0 && rows > 0 && cols > 0) {
-    need = mvsn_incremental_cost_volume_repair_workspace_bytes(n_chains, rows, cols);
-    MVSN_REQUIRE(need == 0 || (repair_workspace && repair_workspace_bytes >= need), MVSN_E_WORKSPACE,
-                 "mvsn_incremental_cost_volume_bf16: repair workspace of %zu bytes required", need);
-  }
-  if (int rc = chain_run(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed, n_chains, batch,
-                         num_idepth_samples, rows, cols, (float *)cost_volume_bf16, mask_volume, feature_volume, workspace,
-                         workspace_bytes, form, nullptr, nullptr, stream, 1))
-    return rc;
-  if (form != MVSN_CHAIN_BANDED) return 0;   // the other forms have no inter-workgroup hand-offs to time out
-  const unsigned *gate = reinterpret_cast<const unsigned *>(static_cast<const char *>(workspace) +
-                                                            chain_band_status_offset(n_chains, rows, cols));
-  return chain_run(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed, n_chains, batch,
-                   num_idepth_samples, rows, cols, (float *)cost_volume_bf16, mask_volume, feature_volume, repair_workspace,
-                   repair_workspace_bytes, chain_repair_form(rows, cols), gate, sticky_status, stream, 1);
+  const mvsn::ChainArgs a = mvsn::chain_args(src_image_lvl4, H_lvl4, H_inc, plane0_features, left_features, refiner_packed,
+                                             batch, num_idepth_samples, rows, cols, cost_volume_bf16, true, mask_volume, feature_volume);
+  return mvsn::chain_entry("mvsn_incremental_cost_volume_bf16", a, n_chains, workspace, workspace_bytes, form, true,
+                           repair_workspace, repair_workspace_bytes, sticky_status, stream);
 }

@@ -823,17 +823,22 @@ __global__ __launch_bounds__(256) void band_zero_kernel(u64 *__restrict__ p, siz
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-struct BandPlan {
-  int G, threads, slot;   // workgroups per chain, threads per workgroup, LDS opt-in slot of the kernel
-  size_t chain_u64, lds_bytes;
-  void (*kernel)(ChainArgs, int, MVSN_VIS10);
-  void (*kernel16)(ChainArgs, int, MVSN_VIS10);   // ... storing the cost volume as bf16 (ChainArgs::cost_bf16)
-};
-
+// The plan table (BandPlan, mvsn_chain.h): this file's rows, the slab rows behind them.
 template <class GEO>
-static BandPlan band_plan_of(int slot) {
-  return BandPlan{GEO::G, CB_THREADS, slot, GEO::CHAIN_U64, (size_t)GEO::LDS_FLOATS * sizeof(float), chain_band_kernel<GEO, false>,
-                  chain_band_kernel<GEO, true>};
+static BandPlan band_row(int kind) {
+  return {GEO::rows, GEO::cols, kind, GEO::G, CB_THREADS, GEO::CHAIN_U64, (size_t)GEO::LDS_FLOATS * sizeof(float),
+          {chain_band_kernel<GEO, false>, chain_band_kernel<GEO, true>}, {}};
+}
+
+static const BandPlan band_plans[] = {band_row<Band16x32H>(BAND_HALF), band_row<Band16x32>(BAND_THIN),
+                                      band_row<Band30x40>(BAND_THIN), band_row<Band32x64>(BAND_THIN)};
+
+static const BandPlan *band_find(int rows, int cols, int kind) {   // "the thin row of this grid"; null: there is none
+  for (const BandPlan &p : band_plans)
+    if (p.rows == rows && p.cols == cols && p.kind == kind) return &p;
+  for (const BandPlan &p : chain_slab_plans)
+    if (p.rows == rows && p.cols == cols && p.kind == kind) return &p;
+  return nullptr;
 }
 
 static int g_band_debug_flags = 0;
@@ -845,44 +850,23 @@ void chain_band_debug_flags(int flags) { g_band_debug_flags = flags; }
 // 30x40 / 32x64: the thin-band plan (15 / 16 workgroups per chain) while the chains fit ONE of its passes (17 / 16 chains
 // on 256 CUs: 2.4 / 4.0 ms per pass at D = 96 / 128); beyond that the SLAB plan (mvsn_chain_slab.hip: 3 / 4 fat bands
 // per chain, 85 / 64 chains per pass of 4.4 / 5.9 ms -- less than two thin passes).
-// Debug flag bit 4 (16) pins the slab plan (also on 16x32, where it exists for the tests only), bit 5 (32) the thin one.
-static bool band_plan(int rows, int cols, int n_chains, BandPlan *p) {
-  const bool known = (rows == 16 && cols == 32) || (rows == 30 && cols == 40) || (rows == 32 && cols == 64);
-  if (!known) return false;
-  const int thin_g = rows == 16 ? Band16x32::G : (rows == 30 ? Band30x40::G : Band32x64::G);
-  const bool many = rows != 16 && n_chains > device_cus() / thin_g;
-  if (((g_band_debug_flags & 16) || many) && !(g_band_debug_flags & 32)) {
-    SlabPlan sp;
-    if (chain_slab_plan(rows, cols, &sp)) {
-      *p = BandPlan{sp.G, sp.threads, rows == 16 ? 4 : (rows == 30 ? 5 : 6), sp.chain_u64, sp.lds_bytes, sp.kernel, sp.kernel16};
-      return true;
-    }
-  }
-  if (rows == 16) {
-    if (!(g_band_debug_flags & 4) && n_chains <= device_cus() / Band16x32H::G) *p = band_plan_of<Band16x32H>(3);
-    else *p = band_plan_of<Band16x32>(0);
-  } else if (rows == 30) *p = band_plan_of<Band30x40>(1);
-  else *p = band_plan_of<Band32x64>(2);
-  return true;
-}
-
-bool chain_band_supported(int rows, int cols) {
-  BandPlan p;
-  return band_plan(rows, cols, 1 << 20, &p);
-}
-
-int chain_band_groups(int n_chains, int rows, int cols) {
-  BandPlan p;
-  return band_plan(rows, cols, n_chains, &p) ? p.G : 0;
+// Debug flag bit 4 (16) pins the slab plan (also on 16x32, where it exists for the tests only: the grid with a half
+// split keeps its thin bands at any number of chains), bit 5 (32) the thin one.
+static const BandPlan *band_plan(int rows, int cols, int n_chains) {
+  const BandPlan *thin = band_find(rows, cols, BAND_THIN), *half = band_find(rows, cols, BAND_HALF);
+  if (!thin) return nullptr;
+  const bool many = !half && n_chains > device_cus() / thin->G;
+  if (((g_band_debug_flags & 16) || many) && !(g_band_debug_flags & 32))
+    if (const BandPlan *slab = band_find(rows, cols, BAND_SLAB)) return slab;
+  if (half && !(g_band_debug_flags & 4) && n_chains <= device_cus() / half->G) return half;
+  return thin;
 }
 
 // chains per pass of the THIN-band plan: every workgroup of a pass must be co-resident (one per CU).  (16x32: of the
 // 4-band plan, the largest number a single pass can take on that grid.)
 int chain_band_chains_per_pass(int rows, int cols) {
-  if (rows == 16 && cols == 32) return device_cus() / Band16x32::G;
-  if (rows == 30 && cols == 40) return device_cus() / Band30x40::G;
-  if (rows == 32 && cols == 64) return device_cus() / Band32x64::G;
-  return 0;
+  const BandPlan *thin = band_find(rows, cols, BAND_THIN);
+  return thin ? device_cus() / thin->G : 0;
 }
 
 // How a call's chains are dealt to passes.  Every workgroup of a pass must be co-resident (one per CU): `per` chains per
@@ -893,40 +877,37 @@ int chain_band_chains_per_pass(int rows, int cols) {
 // workspace + ws_chains * CHAIN_U64 (their own ws_chains, their own CHAIN_U64).  Debug flag 16 (slab pinned) keeps the
 // equal passes (A/B, tests).
 struct BandSchedule {
-  BandPlan main, tail;
+  const BandPlan *main, *tail;
   int per, n_main, n_tail;       // chains per main pass; chains of the main passes / of the thin tail pass
   size_t status_u64, tail_u64;   // offset of the status block / of the tail pass's granules (u64 units)
 };
 
 static bool band_schedule(int rows, int cols, int n_chains, BandSchedule *s) {
-  if (!band_plan(rows, cols, n_chains, &s->main)) return false;
-  const int cap = device_cus() / s->main.G;
+  s->main = band_plan(rows, cols, n_chains), s->tail = nullptr;
+  if (!s->main) return false;
+  const int cap = device_cus() / s->main->G;
   s->n_main = n_chains, s->n_tail = 0, s->per = n_chains, s->tail_u64 = 0;
   if (cap >= 1 && n_chains > cap) {
     const int passes = (n_chains + cap - 1) / cap;
     s->per = (n_chains + passes - 1) / passes;
-    const int thin_g = rows == 16 ? 0 : (rows == 30 ? Band30x40::G : Band32x64::G);
+    const BandPlan *thin = band_find(rows, cols, BAND_THIN);
     const int rem = n_chains % cap;
-    if (thin_g && s->main.G < thin_g && !(g_band_debug_flags & 16) && rem > 0 && rem <= device_cus() / thin_g) {
-      const BandPlan thin = rows == 30 ? band_plan_of<Band30x40>(1) : band_plan_of<Band32x64>(2);
-      const size_t main_u64 = (size_t)cap * s->main.chain_u64, tail_need = (size_t)rem * thin.chain_u64;
+    if (s->main->kind == BAND_SLAB && !(g_band_debug_flags & 16) && rem > 0 && rem <= device_cus() / thin->G) {
+      const size_t main_u64 = (size_t)cap * s->main->chain_u64, tail_need = (size_t)rem * thin->chain_u64;
       if (tail_need <= main_u64 && ((main_u64 - tail_need) & 1) == 0) {   // (16-byte publishes: an even u64 offset)
         s->tail = thin, s->per = cap, s->n_main = n_chains - rem, s->n_tail = rem, s->tail_u64 = main_u64 - tail_need;
       }
     }
   }
-  s->status_u64 = (size_t)s->per * s->main.chain_u64;
+  s->status_u64 = (size_t)s->per * s->main->chain_u64;
   return true;
 }
 
-size_t chain_band_workspace_bytes(int n_chains, int rows, int cols) {
+bool chain_band_layout(int n_chains, int rows, int cols, int *groups, size_t *status_offset) {
   BandSchedule s;
-  return band_schedule(rows, cols, n_chains, &s) ? (s.status_u64 + 8) * sizeof(u64) : 0;
-}
-
-size_t chain_band_status_offset(int n_chains, int rows, int cols) {
-  BandSchedule s;
-  return band_schedule(rows, cols, n_chains, &s) ? s.status_u64 * sizeof(u64) : 0;
+  if (!band_schedule(rows, cols, n_chains, &s)) return false;
+  *groups = s.main->G, *status_offset = s.status_u64 * sizeof(u64);
+  return true;
 }
 
 // status word behind the granules: 0 = every hand-off completed; otherwise the code of the hand-off that timed out.
@@ -941,13 +922,12 @@ int chain_band_launch(const ChainArgs &a, int n_chains, void *workspace, size_t 
   const size_t need = (s.status_u64 + 8) * sizeof(u64);
   MVSN_REQUIRE(workspace && workspace_bytes >= need, MVSN_E_WORKSPACE,
                "mvsn_incremental_cost_volume(banded): workspace of %zu bytes required", need);
-  MVSN_REQUIRE(device_cus() / s.main.G >= 1, MVSN_E_TOOLARGE,
-               "mvsn_incremental_cost_volume(banded): %d bands exceed the %d CUs", s.main.G, device_cus());
-  static LdsOptIn opt[2][7];
+  MVSN_REQUIRE(device_cus() / s.main->G >= 1, MVSN_E_TOOLARGE,
+               "mvsn_incremental_cost_volume(banded): %d bands exceed the %d CUs", s.main->G, device_cus());
   const int c16 = a.cost_bf16 ? 1 : 0;
   auto run_pass = [&](const BandPlan &p, int n0, int nn, u64 *ws, int ws_chains, bool with_status) -> int {
-    const auto kern = c16 ? p.kernel16 : p.kernel;
-    if (int rc = ensure_lds(opt[c16][p.slot], (const void *)kern, p.lds_bytes, "mvsn_incremental_cost_volume(banded)")) return rc;
+    const auto kern = p.kernel[c16];
+    if (int rc = ensure_lds(p.opt[c16], (const void *)kern, p.lds_bytes, "mvsn_incremental_cost_volume(banded)")) return rc;
     // every polled word starts from tag 0 (no step carries it): zeroed ahead of each pass -- with the first pass (which
     // fills the workspace) also the status block behind the granules, so that a later pass keeps what an earlier one
     // reported
@@ -968,10 +948,10 @@ int chain_band_launch(const ChainArgs &a, int n_chains, void *workspace, size_t 
   };
   for (int n0 = 0; n0 < s.n_main; n0 += s.per) {
     const int nn = s.n_main - n0 < s.per ? s.n_main - n0 : s.per;   // (the first pass fills the workspace: nn == per)
-    if (int rc = run_pass(s.main, n0, nn, (u64 *)workspace, s.per, n0 == 0)) return rc;
+    if (int rc = run_pass(*s.main, n0, nn, (u64 *)workspace, s.per, n0 == 0)) return rc;
   }
   if (s.n_tail)
-    if (int rc = run_pass(s.tail, s.n_main, s.n_tail, (u64 *)workspace + s.tail_u64, s.n_tail, false)) return rc;
+    if (int rc = run_pass(*s.tail, s.n_main, s.n_tail, (u64 *)workspace + s.tail_u64, s.n_tail, false)) return rc;
   return check_launch("mvsn_incremental_cost_volume(banded)");
 }
 

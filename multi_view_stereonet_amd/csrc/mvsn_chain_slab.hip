@@ -809,19 +809,13 @@ __global__ __launch_bounds__(SB_THREADS) void chain_slab_kernel(ChainArgs a, int
   }
 }
 
-// ---- host side: the slab plans as seen by the banded form's dispatcher (mvsn_chain_band.hip) -------------------------
+// ---- host side: the slab rows of the banded form's plan table (mvsn_chain.h; looked up in mvsn_chain_band.hip) -----------
 template <class GEO>
-static SlabPlan slab_plan_of() {
-  return SlabPlan{GEO::NB, SB_THREADS, GEO::CHAIN_U64, (size_t)GEO::LDS_FLOATS * sizeof(float), chain_slab_kernel<GEO, false>,
-                  chain_slab_kernel<GEO, true>};
+static BandPlan slab_row() {
+  return {GEO::rows, GEO::cols, BAND_SLAB, GEO::NB, SB_THREADS, GEO::CHAIN_U64, (size_t)GEO::LDS_FLOATS * sizeof(float),
+          {chain_slab_kernel<GEO, false>, chain_slab_kernel<GEO, true>}, {}};
 }
 
-bool chain_slab_plan(int rows, int cols, SlabPlan *p) {
-  if (rows == 30 && cols == 40) *p = slab_plan_of<Slab30x40>();
-  else if (rows == 32 && cols == 64) *p = slab_plan_of<Slab32x64>();
-  else if (rows == 16 && cols == 32) *p = slab_plan_of<Slab16x32>();
-  else return false;
-  return true;
-}
+const BandPlan chain_slab_plans[CHAIN_SLAB_PLANS] = {slab_row<Slab16x32>(), slab_row<Slab30x40>(), slab_row<Slab32x64>()};
 
 }  // namespace mvsn

@@ -31,6 +31,8 @@
 //                           Halo rows / columns are zeroed once and never written.
 //                           ch 0..2 image plane d, ch 3..34 features, ch 35 zero (K padding).
 // 16x32: 18432 + 224 + 256 + 512 + 20842 floats = 161,064 bytes of the 163,840.
+#include <type_traits>
+
 #include "mvsn_chain.h"
 #include "mvsn_resident.h"
 
@@ -506,19 +508,20 @@ __global__ __launch_bounds__(CW_THREADS) void chain_wino_kernel(ChainArgs a, MVS
 
 int chain_wino_launch(const ChainArgs &a, int n_chains, hipStream_t stream) {
   const size_t lds = chain_wino_lds_bytes(a.rows, a.cols);
-#define CW_LAUNCH(R, C, C16)                                                                                         \
-  do {                                                                                                               \
-    static LdsOptIn opt;                                                                                             \
-    if (int rc = ensure_lds(opt, (const void *)chain_wino_kernel<R, C, C16>, lds, "mvsn_incremental_cost_volume(winograd)")) \
-      return rc;                                                                                                     \
-    hipLaunchKernelGGL((chain_wino_kernel<R, C, C16>), dim3(n_chains), dim3(CW_THREADS), lds, stream, a, CHAIN_VISIBLE_G(a)); \
-  } while (0)
-  if (a.cost_bf16) {                                     // (bf16 feature tier)
-    if (a.rows == 16 && a.cols == 32) CW_LAUNCH(16, 32, true);
-    else CW_LAUNCH(0, 0, true);
-  } else if (a.rows == 16 && a.cols == 32) CW_LAUNCH(16, 32, false);   // 512x256 frames (BASELINE configs 2, 3 and the headline)
-  else CW_LAUNCH(0, 0, false);
-#undef CW_LAUNCH
+  // the kernel of (R, C, C16): instantiated here, once per combination, with its own LdsOptIn
+  auto launch = [&](auto r, auto c, auto c16) -> int {
+    const auto kernel = chain_wino_kernel<decltype(r)::value, decltype(c)::value, decltype(c16)::value>;
+    static LdsOptIn opt;
+    if (int rc = ensure_lds(opt, (const void *)kernel, lds, "mvsn_incremental_cost_volume(winograd)")) return rc;
+    hipLaunchKernelGGL(kernel, dim3(n_chains), dim3(CW_THREADS), lds, stream, a, CHAIN_VISIBLE_G(a));
+    return 0;
+  };
+  auto sized = [&](auto c16) -> int {   // 16x32: 512x256 frames (BASELINE configs 2, 3 and the headline); else run-time sizes
+    using I = std::integral_constant<int, 0>;
+    return a.rows == 16 && a.cols == 32 ? launch(std::integral_constant<int, 16>{}, std::integral_constant<int, 32>{}, c16)
+                                        : launch(I{}, I{}, c16);
+  };
+  if (int rc = a.cost_bf16 ? sized(std::true_type{}) : sized(std::false_type{})) return rc;   // (true: bf16 feature tier)
   return check_launch("mvsn_incremental_cost_volume(winograd)");
 }
 

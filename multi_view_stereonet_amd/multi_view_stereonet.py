@@ -1102,21 +1102,23 @@ class PlaneSweepEngine:
         B = left_feats.shape[0]
         D = H4.shape[1]
         dev = src4.device
-        form = {"auto": _native.CHAIN_AUTO, "direct": _native.CHAIN_DIRECT, "winograd": _native.CHAIN_WINOGRAD,
-                "stepwise": _native.CHAIN_STEPWISE, "banded": _native.CHAIN_BANDED}[self.chain_form]
-        if form == _native.CHAIN_AUTO:
-            form = self.lib.mvsn_incremental_cost_volume_form_for(N, rows, cols)
-            if form == _native.CHAIN_BANDED and not (self.banded_ok and not self.net_state.banded_latched
-                                                     and _native.coresident_right(dev.index)):
-                # lanes on several streams (see forward), a latched module, or ANOTHER PROCESS owning this device's
-                # co-resident launches (_native.coresident_right): what AUTO picks once the banded form is out of reach
-                form = self.lib.mvsn_incremental_cost_volume_form_for(1 << 20, rows, cols)
-                if form == _native.CHAIN_BANDED:       # (30x40 / 32x64: AUTO is the banded form at any chain count)
-                    form = _native.CHAIN_STEPWISE if cols % 4 == 0 else _native.CHAIN_DIRECT
-        if form == _native.CHAIN_WINOGRAD and self.lib.mvsn_incremental_cost_volume_form(rows, cols) != form:
-            form = _native.CHAIN_DIRECT        # no Winograd plan for this coarse grid
-        if form == _native.CHAIN_STEPWISE and cols % 4 != 0:
-            form = _native.CHAIN_DIRECT        # the Winograd convolutions of the stepwise form need cols % 4 == 0
+        requested = {"auto": _native.CHAIN_AUTO, "direct": _native.CHAIN_DIRECT, "winograd": _native.CHAIN_WINOGRAD,
+                     "stepwise": _native.CHAIN_STEPWISE, "banded": _native.CHAIN_BANDED}[self.chain_form]
+        # the library's resolver decides: the form that runs and both workspace sizes (guarded: a banded launch is followed
+        # by its gated repair launch -- always with the bf16 cost volume, else by EngineOptions.banded_repair)
+        guarded = bool(cost_bf16 or self.banded_repair)
+        out = (ctypes.c_size_t * 8)()
+
+        def resolve(coresident_allowed):
+            self.lib.mvsn_incremental_cost_volume_resolve(N, D, rows, cols, requested, int(coresident_allowed), int(guarded),
+                                                          ctypes.byref(out))
+            return int(out[0]), int(out[2]), int(out[3])
+        form, ws_bytes, rws_bytes = resolve(True)
+        if requested == _native.CHAIN_AUTO and form == _native.CHAIN_BANDED and not (
+                self.banded_ok and not self.net_state.banded_latched and _native.coresident_right(dev.index)):
+            # lanes on several streams (see forward), a latched module, or ANOTHER PROCESS owning this device's
+            # co-resident launches (_native.coresident_right, asked only when AUTO would take them): AUTO without them
+            form, ws_bytes, rws_bytes = resolve(False)
         if cost_bf16 and form == _native.CHAIN_STEPWISE:
             cost, mask, fvol = self.incremental_cost_volume(src4, H4, Hinc, plane0, left_feats, want_features)
             self._aten()                    # (an ATen kernel: a forward being recorded is not replayable)
@@ -1125,7 +1127,6 @@ class PlaneSweepEngine:
         cost = self.empty((N, 32, D, rows, cols), dtype=torch.bfloat16 if cost_bf16 else torch.float32, device=dev)
         mask = self.empty((N, D, rows, cols), dtype=torch.bool, device=dev)
         fvol = self.empty(cost.shape, torch.float32, dev) if want_features else None      # (the features stay fp32)
-        ws_bytes = self.lib.mvsn_incremental_cost_volume_workspace_bytes_for(N, D, rows, cols, form)
         ws = self.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
         self.last_chain_form, self.last_chain_workspace, self.last_chain_shape = form, ws, (N, rows, cols)
         self.last_cost_dtype = cost.dtype
@@ -1135,22 +1136,14 @@ class PlaneSweepEngine:
                   _native.ptr(fvol), _native.ptr(ws), ws_bytes, form)
         acct = dict(flops=N * (D - 1) * 2.0 * 9 * 32 * (35 + 32 + 32) * P,
                     nbytes=N * (4.0 * 67 * P + (64.0 if cost_bf16 else 128.0) * D * P + D * P))  # Kernel A algorithmic bytes
-        if cost_bf16:
-            # (always the guarded call: a banded launch is followed by its gated repair launch)
-            rws_bytes = (self.lib.mvsn_incremental_cost_volume_repair_workspace_bytes(N, rows, cols)
-                         if form == _native.CHAIN_BANDED else 0)
+        entry = self.lib.mvsn_incremental_cost_volume
+        if cost_bf16 or (form == _native.CHAIN_BANDED and self.banded_repair):
+            # bf16 cost volume: always the guarded call; fp32: a banded launch is followed by the gated single-launch form
+            # -- valid outputs even if a hand-off times out (EngineOptions)
+            entry = self.lib.mvsn_incremental_cost_volume_bf16 if cost_bf16 else self.lib.mvsn_incremental_cost_volume_guarded
             rws = self.empty(rws_bytes, dtype=torch.uint8, device=dev) if rws_bytes else None
-            self._call("mvsn_incremental_cost_volume", self.lib.mvsn_incremental_cost_volume_bf16, *common,
-                       _native.ptr(rws), rws_bytes, self.net_state.status_ptr(), _native.stream(), **acct)
-        elif form == _native.CHAIN_BANDED and self.banded_repair:
-            # followed by the gated single-launch form: valid outputs even if a hand-off times out (EngineOptions)
-            rws_bytes = self.lib.mvsn_incremental_cost_volume_repair_workspace_bytes(N, rows, cols)
-            rws = self.empty(rws_bytes, dtype=torch.uint8, device=dev) if rws_bytes else None
-            self._call("mvsn_incremental_cost_volume", self.lib.mvsn_incremental_cost_volume_guarded, *common,
-                       _native.ptr(rws), rws_bytes, self.net_state.status_ptr(), _native.stream(), **acct)
-        else:
-            self._call("mvsn_incremental_cost_volume", self.lib.mvsn_incremental_cost_volume, *common,
-                       _native.stream(), **acct)
+            common += (_native.ptr(rws), rws_bytes, self.net_state.status_ptr())
+        self._call("mvsn_incremental_cost_volume", entry, *common, _native.stream(), **acct)
         return cost, mask, fvol
 
     def chain_status(self) -> int:

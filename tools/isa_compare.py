@@ -59,7 +59,8 @@ def split_symbols(asm):
         end = starts[n + 1][0] if n + 1 < len(starts) else tail
         body = [normalise(l) for l in lines[i:end]]
         body = [l for l in body if l and not l.startswith("; -- Begin function") and not l.startswith(".protected")
-                and not l.startswith(".globl") and not l.startswith(".p2align")]
+                and not l.startswith(".globl") and not l.startswith(".p2align")
+                and not l.startswith(".fill")]       # (.fill: the code-end padding behind the file's LAST function)
         while body and (body[-1] == ".text" or body[-1].startswith(".section .text")):
             body.pop()                               # the directive that opens the NEXT function's section
         code_end = next((k for k, l in enumerate(body) if l.startswith(".Lfunc_end") or l.startswith(".amdhsa_kernel")
@@ -67,6 +68,7 @@ def split_symbols(asm):
         insn = [l for l in body[:code_end] if not l.startswith((";", ".")) and not re.match(r"\S+:( ;.*)?$", l)]
         syms[sym] = {"text": body, "lines": len(insn), "mfma": sum(1 for l in insn if l.startswith("v_mfma"))}
     meta = asm[asm.find("amdhsa.kernels:"):]
+    meta = re.split(r"\namdhsa\.\w+:", meta)[0]      # (the keys behind the list are the file's, not the last kernel's)
     for entry in re.split(r"\n  - ", meta)[1:]:
         entry = "    " + entry
         name = re.search(r"^    \.name:\s+(\S+)", entry, re.M)
