@@ -620,6 +620,35 @@ int mvsn_voxel_merge(const float *points, const uint8_t *colors, long n, float v
                      long capacity, void *accumulators, float *out_points, uint8_t *out_colors, int *count,
                      int64_t *first, int64_t *inverse, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Oriented normals from depth maps (multi_view_stereonet_amd/fusion.py: depth_normals, point_normals, voxel_normals;
+ * the semantics are DESIGN.md section 13).  Pixel (x, y) = (column, row); a pixel is usable when depth > 0 (a NaN is
+ * not) and valid is NULL or non-zero; a neighbour p' of a usable p counts when it is inside the image, usable, and
+ * |d' - d| <= max_rel_step * d in fp32 (subtract, multiply, compare), the difference finite.
+ * mvsn_depth_normals: X = d * K^-1 (x, y, 1) in fp32 (K^-1 formed per view in fp64, rounded once).  The horizontal
+ *   tangent t_u is X(x+1,y) - X(x-1,y) when both neighbours count, the one-sided difference when one does; t_v likewise
+ *   from (x,y-1), (x,y+1); c = t_v x t_u faces the camera (x right, y down, z forward); c <- R c with R the top-left 3x3
+ *   of the view's T_cam_in_world (assumed to be a rotation) when that is given; n = c / |c|.  (0,0,0) where the pixel is
+ *   not usable, a tangent has no neighbour, or |c| is zero or not finite.  Every pixel is written.
+ *   depth (V,rows,cols)  valid (V,rows,cols) u8 or NULL  K (V,4,4), top-left 3x3 used, bottom row (0,0,1) assumed
+ *   T_cam_in_world (V,4,4) or NULL (camera frame)  max_rel_step >= 0, +inf = no step test  ->  normals (V,3,rows,cols)
+ * mvsn_normals_gather: out[i, :] = normals[view[i], :, pixel[i]] for the `count` points of mvsn_fusion_emit (NaN for an
+ *   index outside the maps; count = 0: no launch).   normals (n_views,3,pixels_per_view)  view, pixel (count) int32
+ *   ->  out (count,3)
+ * mvsn_voxel_normals: the mean direction of the points of every row of mvsn_voxel_merge.  Per point each component is
+ *   clamped to [-1,1] and quantised, q = (int64)rintf(c * 2^20); a point is skipped when inverse[i] lies outside
+ *   [0, m), a component is not finite, or q = (0,0,0); the q of a row are summed with 64-bit integer atomics (exact, in
+ *   any order); out = (float)(S / sqrt(Sx^2 + Sy^2 + Sz^2)) in fp64, (0,0,0) where S = 0.  m = 0: no launch.
+ *   normals (n,3)  inverse (n) int64  accumulators: m * 24 bytes of scratch, 8-byte aligned  ->  out (m,3)
+ * Integer atomics only in the third entry, none in the other two: every output is a deterministic function of the inputs.
+ * ------------------------------------------------------------------------------------------- */
+int mvsn_depth_normals(const float *depth, const uint8_t *valid, const float *K, const float *T_cam_in_world,
+                       int n_views, int rows, int cols, float max_rel_step, float *normals, mvsn_stream_t stream);
+int mvsn_normals_gather(const float *normals, const int *view, const int *pixel, int n_views, long pixels_per_view,
+                        long count, float *out, mvsn_stream_t stream);
+int mvsn_voxel_normals(const float *normals, const int64_t *inverse, long n, long m, void *accumulators, float *out,
+                       mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -121,6 +121,9 @@ SIGNATURES = {
     "mvsn_voxel_assign": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_voxel_merge": (c_int, [c_void_p, c_void_p, c_long] + [ctypes.c_float] * 5 + [c_void_p, c_size_t, c_long] +
                          [c_void_p] * 6 + [c_void_p]),
+    "mvsn_depth_normals": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
+    "mvsn_normals_gather": (c_int, [c_void_p] * 3 + [c_int, c_long, c_long, c_void_p, c_void_p]),
+    "mvsn_voxel_normals": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

@@ -7,6 +7,8 @@ semantics; the kernels are csrc/mvsn_fusion.hip).  ``fuse_depthmaps`` runs that 
 (``net.options.confidence``) can gate the fusion before the geometric check (``min_confidence``)
 and be read at the kept points (``point_values``).  ``voxel_merge`` (csrc/mvsn_voxel.hip) merges a
 cloud on a voxel grid: a surface that k views saw is in the fused cloud k times, and in the merged one once.
+``depth_normals`` (csrc/mvsn_normals.hip) gives every pixel of a depth map its normal, facing the
+camera; ``point_normals`` reads those maps at the points of a fused cloud and ``voxel_normals`` takes them through a merge.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -186,6 +188,94 @@ def point_values(result: FusionResult, maps: torch.Tensor, ref_views: Optional[S
     return out
 
 
+def depth_normals(depth: torch.Tensor, K: torch.Tensor, *, valid: Optional[torch.Tensor] = None,
+                  T_cam_in_world: Optional[torch.Tensor] = None, max_rel_step: float = 0.05) -> torch.Tensor:
+    """The normal of every pixel of ``depth`` (V,1,H,W), from differences of its back-projected neighbours: (V,3,H,W)
+    fp32 unit vectors that face the camera (n . X < 0), in the camera frame, or in the world frame when
+    ``T_cam_in_world`` (V,4,4) is given (its top-left 3x3 is taken to be a rotation).
+
+    A pixel is usable when its depth is > 0 (and ``valid`` (V,1,H,W) is set); a neighbour counts when it is usable and
+    its depth differs by at most ``max_rel_step`` of the pixel's (``inf``: no such test), so a depth edge is not
+    differenced across.  Each tangent is the central difference where both neighbours count and the one-sided one where
+    one does; the normal is (0,0,0) where the pixel is not usable or a tangent has no neighbour (DESIGN.md section 13
+    states every step).  Everything is validated here, before the launch; no host synchronisation."""
+    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError("depth must be a (V,1,H,W) tensor")
+    V, _, H, W = depth.shape
+    dev = depth.device
+    if V < 1 or H * W < 1:
+        raise ValueError("depth must hold at least one view of at least one pixel")
+    if depth.dtype != torch.float32:
+        raise ValueError(f"depth must be float32, got {depth.dtype}")
+    if V > 65535 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"at most 65535 views of 2^31 - 1 pixels, got {V} of {H * W}")
+    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+        if m is None and name != "K":
+            continue
+        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
+            raise ValueError(f"{name} must be a ({V},4,4) tensor")
+        if m.device != dev:
+            raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+    if valid is not None:
+        _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
+    try:
+        step = float(max_rel_step)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_rel_step must be a non-negative number, got {max_rel_step!r}") from None
+    if not step >= 0:
+        raise ValueError(f"max_rel_step must be a non-negative number, got {max_rel_step!r}")
+
+    if not depth.is_cuda:
+        raise RuntimeError("depth_normals runs on HIP devices only: move the depth maps to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+    valid_c = valid.detach().contiguous().view(torch.uint8) if valid is not None else None
+    T_c = f32(T_cam_in_world) if T_cam_in_world is not None else None
+    normals = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_depth_normals(_native.ptr(f32(depth)), _native.ptr(valid_c), _native.ptr(f32(K)),
+                                             _native.ptr(T_c), V, H, W, step, _native.ptr(normals), _native.stream()),
+                      "mvsn_depth_normals")
+    return normals
+
+
+def point_normals(result: FusionResult, normals: torch.Tensor, ref_views: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The normal maps ``normals`` (V,3,H,W) fp32 of ``depth_normals`` at every point of ``result``: (M,3) fp32,
+    ``normals[result.view[i], :, pixel]`` at row-major pixel ``result.pixel[i]`` (``point_values`` for a three-channel
+    map).  ``ref_views``: the fusion's, when ``normals`` holds only those views, in that order (then (R,3,H,W))."""
+    if not torch.is_tensor(normals) or normals.dim() != 4 or normals.shape[1] != 3:
+        raise ValueError("normals must be a (V,3,H,W) tensor")
+    if normals.dtype != torch.float32:
+        raise ValueError(f"normals must be float32, got {normals.dtype}")
+    if tuple(normals.shape[-2:]) != tuple(result.depth.shape[-2:]):
+        raise ValueError(f"normals are {tuple(normals.shape[-2:])}, the fusion ran on {tuple(result.depth.shape[-2:])}")
+    if normals.device != result.view.device:
+        raise ValueError(f"normals are on {normals.device}, the points on {result.view.device}")
+    view = result.view
+    if ref_views is not None:
+        refs = _host_index_array(ref_views, "ref_views").reshape(-1)
+        if refs.shape[0] != normals.shape[0]:
+            raise ValueError(f"normals hold {normals.shape[0]} views for {refs.shape[0]} reference views")
+        row = np.full(int(refs.max()) + 1 if refs.size else 1, -1, dtype=np.int32)
+        row[refs] = np.arange(refs.shape[0], dtype=np.int32)
+        lut = torch.from_numpy(row).to(view.device)
+        view = lut[view.long().clamp(0, lut.shape[0] - 1)].contiguous()
+    M = int(view.shape[0])
+    if M == 0:                         # no points: nothing to launch
+        return torch.empty((0, 3), dtype=torch.float32, device=normals.device)
+    if not normals.is_cuda:
+        raise RuntimeError("point_normals runs on HIP devices only (there is no CPU implementation)")
+    out = torch.empty((M, 3), dtype=torch.float32, device=normals.device)
+    lib = _native.load()
+    with torch.cuda.device(normals.device):
+        _native.check(lib.mvsn_normals_gather(_native.ptr(normals.detach().contiguous()), _native.ptr(view.contiguous()),
+                                              _native.ptr(result.pixel.contiguous()), normals.shape[0],
+                                              normals.shape[2] * normals.shape[3], M, _native.ptr(out),
+                                              _native.stream()), "mvsn_normals_gather")
+    return out
+
+
 class VoxelCloud(NamedTuple):
     points: torch.Tensor             # (M,3) fp32: mean position of each occupied voxel
     colors: Optional[torch.Tensor]   # (M,3) uint8 mean colour, or None
@@ -280,6 +370,36 @@ def voxel_merge(points: torch.Tensor, voxel_size: float, *, colors: Optional[tor
     return vc
 
 
+def voxel_normals(vc: VoxelCloud, normals: torch.Tensor) -> torch.Tensor:
+    """The normal of every voxel of ``vc``: (len(vc.count),3) fp32, the direction of the sum of the ``normals`` (N,3)
+    fp32 of its points (N = len(vc.inverse): ``point_normals`` of the cloud that was merged).  Each component is
+    quantised to 2^-20 and the sums are integers, so the result does not depend on the order of the points and is
+    bitwise reproducible.  A point the merge dropped, a non-finite normal and the (0,0,0) of an undefined pixel add
+    nothing; a voxel whose sum is zero gets (0,0,0)."""
+    N, M = int(vc.inverse.shape[0]), int(vc.count.shape[0])
+    dev = vc.inverse.device
+    if not torch.is_tensor(normals) or tuple(normals.shape) != (N, 3):
+        raise ValueError(f"normals must be an ({N},3) tensor, one row per merged point")
+    if normals.dtype != torch.float32:
+        raise ValueError(f"normals must be float32, got {normals.dtype}")
+    if normals.device != dev:
+        raise ValueError(f"normals are on {normals.device}, the cloud on {dev}")
+    if M == 0:                         # no voxels, nothing to launch
+        return torch.empty((0, 3), dtype=torch.float32, device=dev)
+    if N == 0:                         # (voxels without points: not a cloud voxel_merge returns)
+        return torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    if not normals.is_cuda:
+        raise RuntimeError("voxel_normals runs on HIP devices only (there is no CPU implementation)")
+    lib = _native.load()
+    out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    accum = torch.empty((M, 3), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_voxel_normals(_native.ptr(normals.detach().contiguous()),
+                                             _native.ptr(vc.inverse.contiguous()), N, M, _native.ptr(accum),
+                                             _native.ptr(out), _native.stream()), "mvsn_voxel_normals")
+    return out
+
+
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:
     """T_right_in_left = T_left_in_world^-1 T_right_in_world for every (ref[i], src[i]): (len(ref),1,4,4) fp32, formed
     in fp64 on the host (a handful of 4x4s: the DataLoader-side pose arithmetic)."""
@@ -291,7 +411,8 @@ def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequ
 def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
                 num_idepth_samples: int = 64, batch: int = 8, cost_volume_filter: bool = True,
                 refiners: Sequence[bool] = (True,) * 5, with_confidence: bool = False,
-                min_confidence: Optional[float] = None, **fusion_kwargs):
+                min_confidence: Optional[float] = None, with_normals: bool = False,
+                normals_max_rel_step: float = 0.05, **fusion_kwargs):
     """Posed frames -> point cloud: the network's depth map for every view, then ``fuse_depthmaps`` over all of them.
 
     ``images`` (V,3,H,W) fp32 in [-1,1] on the network's device, ``K`` / ``T_cam_in_world`` (V,4,4), ``neighbours`` (V,S)
@@ -302,7 +423,10 @@ def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torc
 
     ``with_confidence`` or a ``min_confidence``: the forwards run with ``net.options.confidence`` on (restored
     afterwards, also when a forward raises), the finest confidence map of every view goes, with ``min_confidence``, to
-    the fusion, and the return value is ``(FusionResult, depth, confidence (V,1,H,W))``."""
+    the fusion, and the return value is ``(FusionResult, depth, confidence (V,1,H,W))``.
+
+    ``with_normals``: the world-frame normals of the points, ``point_normals(result, depth_normals(depth, K,
+    T_cam_in_world=T_cam_in_world, max_rel_step=normals_max_rel_step))`` (M,3), come as one more, last element."""
     from . import metrics
     from . import multi_view_stereonet_utils as snu
 
@@ -349,20 +473,32 @@ def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torc
         depth = torch.cat(depths, 0)
         if not want_conf:
             result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, **fusion_kwargs)
-            return result, depth
-        confidence = torch.cat(confs, 0)
-        result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images, confidence=confidence,
-                                min_confidence=min_confidence, **fusion_kwargs)
-    return result, depth, confidence
+            out = (result, depth)
+        else:
+            confidence = torch.cat(confs, 0)
+            result = fuse_depthmaps(depth, K.to(dev), T_cam_in_world.to(dev), nb, images=images,
+                                    confidence=confidence, min_confidence=min_confidence, **fusion_kwargs)
+            out = (result, depth, confidence)
+        if with_normals:
+            maps = depth_normals(depth, K.to(dev), T_cam_in_world=T_cam_in_world.to(dev),
+                                 max_rel_step=normals_max_rel_step)
+            out += (point_normals(result, maps),)
+    return out
 
 
-def write_ply(path: str, points, colors=None, confidence=None) -> None:
-    """Binary little-endian PLY: float x, y, z per vertex, plus uchar red, green, blue when ``colors`` is given, plus
-    float confidence (after the colours) when ``confidence`` (N,) is given."""
+def write_ply(path: str, points, colors=None, confidence=None, normals=None) -> None:
+    """Binary little-endian PLY: float x, y, z per vertex, plus float nx, ny, nz (right after the position) when
+    ``normals`` (N,3) is given, plus uchar red, green, blue when ``colors`` is given, plus float confidence (after the
+    colours) when ``confidence`` (N,) is given."""
     pts = (points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)).astype("<f4")
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError("points must be (N,3)")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = (normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)).astype("<f4")
+        if nrm.shape != pts.shape:
+            raise ValueError("normals must be (N,3) like points")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         col = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
         if col.shape != pts.shape:
@@ -375,6 +511,8 @@ def write_ply(path: str, points, colors=None, confidence=None) -> None:
         fields += [("confidence", "<f4")]
     rec = np.empty(pts.shape[0], dtype=fields)
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         col = col.astype(np.uint8)
         rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]

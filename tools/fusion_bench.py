@@ -11,7 +11,11 @@ mvsn_confidence_mask, in front of the four) and reports it as "gated".  --voxel:
 voxel grid (fusion.voxel_merge; the voxel is one pixel's footprint at the median fused depth, about one point per
 surface element of a single view) and reports, as "voxel", N, M and ms per call next to the same merge composed from
 torch ops on the device (torch.unique(dim=0, return_inverse=True) on the integer cells + index_add_), timed the same
-way."""
+way.  --normals: also times depth_normals on each scene's depth maps (one launch; world frame) and reports, as
+"normals", ms per call next to the same map composed from torch ops on the device (shifted slices, torch.cross,
+F.normalize), the bytes per second the call achieves against the 16 bytes per pixel the algorithm must move (4 read, 12
+written; 17 with a validity mask), how far the two maps are apart, and ms per point_normals / voxel_normals call on the
+fused cloud."""
 import argparse
 import json
 import os
@@ -24,7 +28,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import fuse_depthmaps, voxel_merge  # noqa: E402
+from multi_view_stereonet_amd.fusion import (depth_normals, fuse_depthmaps, point_normals, voxel_merge,  # noqa: E402
+                                             voxel_normals)
 
 SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
 
@@ -73,7 +78,64 @@ def run_voxel(res, fx, steps, warmup):
                       "torch_ms_per_call_min": float(np.min(ttimes))}}
 
 
-def run(V, H, W, M, steps, warmup, confidence=False, voxel=False):
+def torch_depth_normals(depth, K, T, step):
+    """depth_normals from torch ops: the same neighbour test and tangents on shifted copies of the maps (every
+    intermediate a (V,H,W,3) tensor in HBM: what a caller had to write without the kernel)."""
+    import torch.nn.functional as F
+    V, _, H, W = depth.shape
+    d = depth[:, 0]
+    Ki = torch.linalg.inv(K[:, :3, :3].double()).float()
+    ys, xs = torch.meshgrid(torch.arange(H, device=d.device, dtype=torch.float32),
+                            torch.arange(W, device=d.device, dtype=torch.float32), indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1)
+    X = d[..., None] * torch.einsum("vij,hwj->vhwi", Ki, pix)
+    ok = d > 0
+    bound = step * d
+
+    def neighbour(dy, dx):
+        inside = torch.ones(H, W, dtype=torch.bool, device=d.device)
+        if dx:
+            inside[:, 0 if dx < 0 else W - 1] = False
+        if dy:
+            inside[0 if dy < 0 else H - 1, :] = False
+        dn = torch.roll(d, (-dy, -dx), (1, 2))
+        counts = ok & torch.roll(ok, (-dy, -dx), (1, 2)) & inside & ((dn - d).abs() <= bound)
+        return counts, torch.roll(X, (-dy, -dx), (1, 2))
+
+    (left, Xl), (right, Xr), (up, Xu), (down, Xd) = neighbour(0, -1), neighbour(0, 1), neighbour(-1, 0), neighbour(1, 0)
+    tu = torch.where(right[..., None], Xr, X) - torch.where(left[..., None], Xl, X)
+    tv = torch.where(down[..., None], Xd, X) - torch.where(up[..., None], Xu, X)
+    c = torch.einsum("vij,vhwj->vhwi", T[:, :3, :3], torch.cross(tv, tu, dim=-1))
+    n = F.normalize(c, dim=-1)
+    defined = ok & (left | right) & (up | down) & (c != 0).any(-1)
+    return torch.where(defined[..., None], n, torch.zeros_like(n)).permute(0, 3, 1, 2).contiguous()
+
+
+def run_normals(sc, res, steps, warmup):
+    depth, K, T = sc["depth"], sc["K"], sc["T_cam_in_world"]
+    V, _, H, W = depth.shape
+    maps, times = timed(lambda: depth_normals(depth, K, T_cam_in_world=T), steps, warmup)
+    tmaps, ttimes = timed(lambda: torch_depth_normals(depth, K, T, 0.05), steps, warmup)
+    both = (maps != 0).any(1) & (tmaps != 0).any(1)
+    cosine = (maps * tmaps).sum(1)[both].clamp(-1, 1)
+    pn, gtimes = timed(lambda: point_normals(res, maps), steps, warmup)
+    fx = float(K[0, 0, 0])
+    vc = voxel_merge(res.points, float(np.float32(float(res.depth[res.depth > 0].median()) / fx)), colors=res.colors)
+    vn, vtimes = timed(lambda: voxel_normals(vc, pn), steps, warmup)
+    nbytes = 16 * V * H * W
+    return {"normals": {"ms_per_call_median": float(np.median(times)), "ms_per_call_min": float(np.min(times)),
+                        "torch_ms_per_call_median": float(np.median(ttimes)),
+                        "torch_ms_per_call_min": float(np.min(ttimes)), "algorithmic_bytes": nbytes,
+                        "bytes_per_s_at_median": nbytes / (float(np.median(times)) * 1e-3),
+                        "bytes_per_s_at_min": nbytes / (float(np.min(times)) * 1e-3),
+                        "defined_fraction": float((maps != 0).any(1).float().mean()),
+                        "defined_mask_differs_from_torch": int(((maps != 0).any(1) != (tmaps != 0).any(1)).sum()),
+                        "max_angle_to_torch_rad": float(torch.acos(cosine).max()) if cosine.numel() else 0.0,
+                        "point_normals_ms_median": float(np.median(gtimes)), "points": int(pn.shape[0]),
+                        "voxel_normals_ms_median": float(np.median(vtimes)), "voxels": int(vn.shape[0])}}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -89,7 +151,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False):
                            "ms_per_call_min": float(np.min(gtimes)), "points": int(gres.points.shape[0]),
                            "mask_bytes": 5 * V * P + V * P}}
     merged = run_voxel(res, float(sc["K"][0, 0, 0]), steps, warmup) if voxel else {}
-    return {**gated, **merged, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    oriented = run_normals(sc, res, steps, warmup) if normals else {}
+    return {**gated, **merged, **oriented, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -103,10 +166,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--confidence", action="store_true", help="also time the call gated by a confidence map")
     ap.add_argument("--voxel", action="store_true", help="also time voxel_merge of the fused cloud, and its torch form")
+    ap.add_argument("--normals", action="store_true", help="also time depth_normals, and its torch form")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
-        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel)), flush=True)
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals)), flush=True)
 
 
 if __name__ == "__main__":
