@@ -649,6 +649,36 @@ int mvsn_normals_gather(const float *normals, const int *view, const int *pixel,
 int mvsn_voxel_normals(const float *normals, const int64_t *inverse, long n, long m, void *accumulators, float *out,
                        mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fixed-radius nearest neighbour between two unsorted clouds (multi_view_stereonet_amd/fusion.py: cloud_nearest,
+ * radius_outlier_mask; metrics.py: cloud_metrics; the semantics are DESIGN.md section 14).  With h = max_dist in fp32,
+ * cell = h, inv_cell = 1 / h and r2 = h * h all formed by the caller in fp32: d2(q, p) = (dx dx + dy dy) + dz dz with
+ * dx = qx - px ..., every step one fp32 operation; target p is within when d2 <= r2; the nearest is the within-target of
+ * least d2, ties to the lowest row.  The result is that of the brute force over every target point, exactly.  A target
+ * with a non-finite coordinate is nobody's neighbour; a query with one gets (+inf, -1, 0); a query may lie anywhere.
+ * mvsn_cloud_index_build: the target sorted by cell (section 12's grid: cell size h, origin 0) through the hash table.
+ *   target (n,3) fp32, 1 <= n <= 2^31 - 1
+ *   -> status (1 int64): MVSN_CLOUD_STATUS_* bits, 0 = fine; reading it back is the one host synchronisation of a query
+ *   workspace: mvsn_cloud_workspace_bytes(n) bytes, 16-byte aligned, handed on to mvsn_cloud_nearest unchanged: 20
+ *   bytes per table slot (a power of two >= 2 n slots: key, population, start, cursor), 20 bytes per point (its slot,
+ *   its 16-byte record), 12 bytes per 1024 slots.
+ * mvsn_cloud_nearest: one thread per query point walks the records of the cells within reach.
+ *   query (nq,3) fp32, 1 <= nq <= 2^31 - 1; n_target as given to the build
+ *   -> dist2 (nq) fp32: d2 to the nearest target within max_dist, +inf where none   index (nq) int64: its row, -1
+ *      within (nq) int32: the number of targets with d2 <= r2
+ * Integer atomics only, in the build (compare-and-swap on an empty key, sums, a cursor whose order of arrival no output
+ * depends on): every output is a deterministic function of the inputs.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_CLOUD_STATUS_RANGE 1   /* a finite target's cell lies outside [-2^20, 2^20): max_dist too small */
+#define MVSN_CLOUD_STATUS_TABLE 2   /* a probe sequence visited every slot without finding room (cannot happen
+                                       below 2^30 points: the table is at most half full) */
+size_t mvsn_cloud_workspace_bytes(long n_target);
+int mvsn_cloud_index_build(const float *target, long n, float cell, float inv_cell, int64_t *status, void *workspace,
+                           size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_cloud_nearest(const float *query, long nq, float inv_cell, float r2, const void *workspace,
+                       size_t workspace_bytes, long n_target, float *dist2, int64_t *index, int *within,
+                       mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -124,6 +124,10 @@ SIGNATURES = {
     "mvsn_depth_normals": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
     "mvsn_normals_gather": (c_int, [c_void_p] * 3 + [c_int, c_long, c_long, c_void_p, c_void_p]),
     "mvsn_voxel_normals": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p]),
+    "mvsn_cloud_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_cloud_index_build": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_cloud_nearest": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_size_t, c_long] +
+                           [c_void_p] * 3 + [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

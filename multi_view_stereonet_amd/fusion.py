@@ -9,6 +9,9 @@ and be read at the kept points (``point_values``).  ``voxel_merge`` (DESIGN.md s
 cloud on a voxel grid: a surface that k views saw is in the fused cloud k times, and in the merged one once.
 ``depth_normals`` (csrc/mvsn_normals.hip) gives every pixel of a depth map its normal, facing the
 camera; ``point_normals`` reads those maps at the points of a fused cloud and ``voxel_normals`` takes them through a merge.
+``cloud_nearest`` (csrc/mvsn_cloud.hip) finds, for every point of one cloud, the nearest point of
+another within a radius, exactly; ``radius_outlier_mask`` is the same query of a cloud against itself
+(``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -398,6 +401,107 @@ def voxel_normals(vc: VoxelCloud, normals: torch.Tensor) -> torch.Tensor:
                                              _native.ptr(vc.inverse.contiguous()), N, M, _native.ptr(accum),
                                              _native.ptr(out), _native.stream()), "mvsn_voxel_normals")
     return out
+
+
+class CloudNeighbours(NamedTuple):
+    dist2: torch.Tensor              # (N,) fp32: squared distance to the nearest target point, +inf where none within max_dist
+    index: torch.Tensor              # (N,) int64: that target point's row, -1 where none
+    within: torch.Tensor             # (N,) int32: number of target points within max_dist
+
+
+CLOUD_STATUS_RANGE, CLOUD_STATUS_TABLE = 1, 2
+
+
+def check_cloud(name, t):
+    """ValueError unless ``t`` is an (N,3) float32 tensor of at most 2^31 - 1 rows (any device)."""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be an (N,3) tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if int(t.shape[0]) > 2 ** 31 - 1:
+        raise ValueError(f"at most 2^31 - 1 {name} points, got {int(t.shape[0])}")
+
+
+def cloud_radius_scalars(max_dist, name="max_dist"):
+    """(h, 1/h, h*h) as np.float32, each formed once in fp32 on the host; ValueError unless all three are finite and
+    > 0."""
+    with np.errstate(all="ignore"):
+        try:
+            h = np.float32(max_dist)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a positive finite number, got {max_dist!r}") from None
+        inv, r2 = np.float32(1) / h, h * h
+    if not (np.isfinite(h) and h > 0 and np.isfinite(inv) and inv > 0 and np.isfinite(r2) and r2 > 0):
+        raise ValueError(f"{name} must be finite and > 0 (in float32, with a finite inverse and a finite non-zero "
+                         f"square), got {max_dist!r}")
+    return h, inv, r2
+
+
+def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) -> CloudNeighbours:
+    """For every row of ``query`` (N,3) fp32 the nearest row of ``target`` (T,3) fp32 within ``max_dist``: its squared
+    distance, its row, and how many target points lie within ``max_dist``.  Neither cloud needs any order.
+
+    With h = float32(max_dist) the squared distance is ``(dx*dx + dy*dy) + dz*dz`` of the fp32 differences, each step
+    one fp32 operation; a target is within when that is ``<= h*h``; ties for the nearest go to the lowest target row.
+    The result is exactly that of the brute force over every target point (DESIGN.md section 14 has the proof).  A
+    target with a non-finite coordinate is nobody's neighbour, a query with one gets (+inf, -1, 0), and a query may lie
+    anywhere.  The target goes on a grid of cell size h anchored at (0,0,0): a finite target more than 2^20 cells from
+    the origin raises ValueError.  The time grows with (targets per cell) x (cells visited, 27 almost always): a
+    ``max_dist`` far above the sampling distance is quadratic within a neighbourhood.  Everything is validated here,
+    before any launch; the one host synchronisation is the read of the status word, after the query is enqueued."""
+    check_cloud("query", query)
+    check_cloud("target", target)
+    if query.device != target.device:
+        raise ValueError(f"query is on {query.device}, target on {target.device}")
+    h, inv, r2 = cloud_radius_scalars(max_dist)
+    N, T, dev = int(query.shape[0]), int(target.shape[0]), query.device
+    if N == 0 or T == 0:               # nothing to find, nothing to launch
+        return CloudNeighbours(torch.full((N,), float("inf"), dtype=torch.float32, device=dev),
+                               torch.full((N,), -1, dtype=torch.int64, device=dev),
+                               torch.zeros((N,), dtype=torch.int32, device=dev))
+    if not query.is_cuda:
+        raise RuntimeError("cloud_nearest runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    q, t = query.detach().contiguous(), target.detach().contiguous()
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(T)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    out = CloudNeighbours(torch.empty((N,), dtype=torch.float32, device=dev),
+                          torch.empty((N,), dtype=torch.int64, device=dev),
+                          torch.empty((N,), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), T, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_nearest(_native.ptr(q), N, float(inv), float(r2), _native.ptr(ws), ws_bytes, T,
+                                             _native.ptr(out.dist2), _native.ptr(out.index), _native.ptr(out.within),
+                                             st), "mvsn_cloud_nearest")
+        bits = int(status.item())      # the one host synchronisation (the query never leaves its buffers, whatever the table holds)
+    if bits & CLOUD_STATUS_RANGE:
+        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
+                         f"cells of {float(h):g} or more from the origin")
+    if bits:
+        raise RuntimeError(f"cloud_nearest: the hash grid overflowed (status {bits})")
+    return out
+
+
+def radius_outlier_mask(points: torch.Tensor, radius: float, min_neighbours: int) -> torch.Tensor:
+    """(N,) bool: True where at least ``min_neighbours`` OTHER points of ``points`` (N,3) fp32 lie within ``radius``
+    (``cloud_nearest`` of the cloud against itself; the point itself is not counted, its exact duplicates are).  A
+    point with a non-finite coordinate gets False."""
+    try:
+        k = int(min_neighbours)
+        if k != min_neighbours or isinstance(min_neighbours, bool):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"min_neighbours must be an integer, got {min_neighbours!r}") from None
+    check_cloud("points", points)
+    cloud_radius_scalars(radius, "radius")
+    if int(points.shape[0]) == 0:
+        return torch.zeros((0,), dtype=torch.bool, device=points.device)
+    nn = cloud_nearest(points, points, radius)
+    return (nn.within - 1 >= k) & torch.isfinite(points).all(dim=1)
 
 
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:

@@ -15,6 +15,10 @@ Mirrors, by name and meaning, the evaluation bookkeeping of the reference's ``te
 one HBM pass (``depth_metric_rows`` -> mvsn_depth_metrics: nine doubles per image), nothing is copied back or
 synchronised per image, and the rows are all-gathered once at the end.  The numpy functions are the host form of the
 same arithmetic (CPU devices, and what the device rows are tested against).
+
+``cloud_metrics`` scores a reconstruction cloud against cloud: DTU's accuracy and completeness,
+Tanks and Temples' precision, recall and F-score, on ``fusion.cloud_nearest`` where the clouds live on a HIP device and
+on a chunked torch brute force of the same fp32 arithmetic on the host.
 """
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -189,3 +193,80 @@ def evaluate(stereo_network, batches: Iterable[dict], params: dict, split: str, 
         out["batch_runtime_ms"] = avg[-1]
     out["num_samples"] = int(all_rows.shape[0])
     return out
+
+
+# ---- cloud against cloud ---------------------------------------------------------------------
+CLOUD_METRIC_KEYS = ("accuracy", "completeness", "precision", "recall", "fscore", "n_pred", "n_truth")
+_HOST_CHUNK_ELEMENTS = 1 << 22
+
+
+def _host_nearest_dist2(query: torch.Tensor, target: torch.Tensor, h, inv, r2) -> torch.Tensor:
+    """``fusion.cloud_nearest(...).dist2`` of CPU tensors by brute force: the same fp32 operations in the same order,
+    ``chunk`` query rows against every target row at a time."""
+    from .fusion import VOXEL_CELL_LIMIT
+    q, t = query.detach().contiguous(), target.detach().contiguous()
+    N, T = int(q.shape[0]), int(t.shape[0])
+    out = torch.full((N,), float("inf"), dtype=torch.float32)
+    if N == 0 or T == 0:
+        return out
+    cell = torch.floor(t * float(inv))
+    finite = torch.isfinite(t).all(dim=1)
+    outside = ~(torch.isfinite(cell) & (cell >= -VOXEL_CELL_LIMIT) & (cell < VOXEL_CELL_LIMIT)).all(dim=1)
+    if bool((finite & outside).any()):
+        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
+                         f"cells of {float(h):g} or more from the origin")
+    radius2 = torch.tensor(float(r2), dtype=torch.float32)
+    inf = torch.tensor(float("inf"), dtype=torch.float32)
+    chunk = max(1, _HOST_CHUNK_ELEMENTS // T)
+    tx, ty, tz = t[None, :, 0], t[None, :, 1], t[None, :, 2]
+    for a in range(0, N, chunk):
+        c = q[a:a + chunk]
+        dx, dy, dz = c[:, 0:1] - tx, c[:, 1:2] - ty, c[:, 2:3] - tz
+        d2 = (dx * dx + dy * dy) + dz * dz
+        out[a:a + chunk] = torch.where(d2 <= radius2, d2, inf).min(dim=1).values
+    return out
+
+
+def cloud_metrics(pred: torch.Tensor, truth: torch.Tensor, threshold: float, max_dist: Optional[float] = None
+                  ) -> Dict[str, float]:
+    """Accuracy / completeness (DTU) and precision / recall / F-score at ``threshold`` (Tanks and Temples) of the
+    cloud ``pred`` (N,3) fp32 against ``truth`` (T,3) fp32, computed where the tensors live.
+
+    ``accuracy``: the mean over the finite points of ``pred`` of ``min(distance to the nearest truth point, max_dist)``
+    in fp64 (a capped mean is defined for every cloud; ``max_dist`` defaults to ``threshold`` and must not be below
+    it); ``completeness``: the same from ``truth`` to ``pred``.  ``precision``: the fraction of the finite points of
+    ``pred`` whose squared distance is ``<= float32(threshold)**2`` (rounded once in fp32; the counts are exact
+    integers); ``recall``: the reverse; ``fscore = 2PR/(P+R)``, 0 when both are 0.  ``n_pred`` / ``n_truth`` count the
+    finite points.  The distances are ``fusion.cloud_nearest``'s, exactly the brute force's.  On a HIP device: two
+    ``cloud_nearest`` calls, torch reductions, one host read at the end; on CPU tensors a chunked torch brute force of
+    the same arithmetic."""
+    from . import fusion
+    fusion.check_cloud("pred", pred)
+    fusion.check_cloud("truth", truth)
+    if pred.device != truth.device:
+        raise ValueError(f"pred is on {pred.device}, truth on {truth.device}")
+    tau, _, tau2 = fusion.cloud_radius_scalars(threshold, "threshold")
+    h, inv, r2 = fusion.cloud_radius_scalars(threshold if max_dist is None else max_dist, "max_dist")
+    if h < tau:
+        raise ValueError(f"max_dist ({float(h):g}) must not be below threshold ({float(tau):g})")
+    if pred.is_cuda:
+        d_pt = fusion.cloud_nearest(pred, truth, float(h)).dist2
+        d_tp = fusion.cloud_nearest(truth, pred, float(h)).dist2
+    else:
+        d_pt = _host_nearest_dist2(pred, truth, h, inv, r2)
+        d_tp = _host_nearest_dist2(truth, pred, h, inv, r2)
+
+    def sums(points, d2):
+        finite = torch.isfinite(points).all(dim=1)
+        capped = d2.to(torch.float64).sqrt().clamp(max=float(h))
+        zero = torch.zeros((), dtype=torch.float64, device=points.device)
+        return [finite.sum().to(torch.float64), torch.where(finite, capped, zero).sum(),
+                (finite & (d2 <= float(tau2))).sum().to(torch.float64)]
+
+    n_p, s_p, k_p, n_t, s_t, k_t = torch.stack(sums(pred, d_pt) + sums(truth, d_tp)).tolist()    # the one host read
+    if n_p == 0 or n_t == 0:
+        raise ValueError(f"a cloud has no finite point ({int(n_p)} in pred, {int(n_t)} in truth)")
+    precision, recall = k_p / n_p, k_t / n_t
+    fscore = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {"accuracy": s_p / n_p, "completeness": s_t / n_t, "precision": precision, "recall": recall,
+            "fscore": fscore, "n_pred": int(n_p), "n_truth": int(n_t)}

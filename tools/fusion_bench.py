@@ -15,7 +15,12 @@ way.  --normals: also times depth_normals on each scene's depth maps (one launch
 "normals", ms per call next to the same map composed from torch ops on the device (shifted slices, torch.cross,
 F.normalize), the bytes per second the call achieves against the 16 bytes per pixel the algorithm must move (4 read, 12
 written; 17 with a validity mask), how far the two maps are apart, and ms per point_normals / voxel_normals call on the
-fused cloud."""
+fused cloud.  --cloud-metrics: also fuses each scene's depths with a seeded relative perturbation into a
+prediction, scores it against the cloud of the true depths (metrics.cloud_metrics; threshold = max_dist = one pixel's
+footprint at the median fused depth) and reports, as "cloud", the metrics, ms per cloud_nearest call (prediction against
+truth) with the index build and the query timed separately between device events, and the same query composed from torch
+ops on the device -- torch.cdist + min over chunks of the target -- for the first TORCH_QUERIES queries only (the full
+composition forms N x T distances: 7e13 at these sizes), with its extrapolation to all queries."""
 import argparse
 import json
 import os
@@ -27,9 +32,10 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from multi_view_stereonet_amd import synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (depth_normals, fuse_depthmaps, point_normals, voxel_merge,  # noqa: E402
-                                             voxel_normals)
+from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
+from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, depth_normals,  # noqa: E402
+                                             fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
+from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
 
 SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
 
@@ -135,7 +141,73 @@ def run_normals(sc, res, steps, warmup):
                         "voxel_normals_ms_median": float(np.median(vtimes)), "voxels": int(vn.shape[0])}}
 
 
-def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False):
+TORCH_QUERIES = 1024
+TORCH_TARGET_CHUNK = 1 << 20
+
+
+def torch_cloud_nearest(query, target, max_dist):
+    """The query from torch ops: chunks of the target through torch.cdist, the running minimum and the count (what a
+    caller had to write without cloud_nearest; cdist's own arithmetic, so the last bits of a distance may differ)."""
+    best = torch.full((query.shape[0],), float("inf"), device=query.device)
+    index = torch.full((query.shape[0],), -1, dtype=torch.int64, device=query.device)
+    within = torch.zeros(query.shape[0], dtype=torch.int64, device=query.device)
+    for a in range(0, target.shape[0], TORCH_TARGET_CHUNK):
+        d = torch.cdist(query, target[a:a + TORCH_TARGET_CHUNK])
+        d = torch.where(d <= max_dist, d, torch.full_like(d, float("inf")))
+        within += torch.isfinite(d).sum(dim=1)
+        m, i = d.min(dim=1)
+        closer = m < best
+        best, index = torch.where(closer, m, best), torch.where(closer, i + a, index)
+    return best * best, index, within
+
+
+def run_cloud(sc, nb, res, steps, warmup):
+    steps, warmup = min(steps, 5), min(warmup, 1)           # (the calls are long: milliseconds to seconds)
+    depth, K, T = sc["depth"], sc["K"], sc["T_cam_in_world"]
+    noise = torch.randn(depth.shape, generator=torch.Generator().manual_seed(1)).to(depth.device)
+    pred = fuse_depthmaps(depth * (1.0 + 0.002 * noise), K, T, nb).points
+    truth = res.points
+    threshold = float(np.float32(float(res.depth[res.depth > 0].median()) / float(K[0, 0, 0])))
+    metrics = cloud_metrics(pred, truth, threshold)
+    nn, times = timed(lambda: cloud_nearest(pred, truth, threshold), steps, warmup)
+    # the two entries on their own, between device events
+    lib = _native.load()
+    h, inv, r2 = cloud_radius_scalars(threshold)
+    N, Tn = int(pred.shape[0]), int(truth.shape[0])
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(Tn)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pred.device)
+    status = torch.empty(1, dtype=torch.int64, device=pred.device)
+    out = (torch.empty(N, device=pred.device), torch.empty(N, dtype=torch.int64, device=pred.device),
+           torch.empty(N, dtype=torch.int32, device=pred.device))
+
+    def build():
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(truth), Tn, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(ws), ws_bytes, _native.stream()), "mvsn_cloud_index_build")
+
+    def query():
+        _native.check(lib.mvsn_cloud_nearest(_native.ptr(pred), N, float(inv), float(r2), _native.ptr(ws), ws_bytes, Tn,
+                                             _native.ptr(out[0]), _native.ptr(out[1]), _native.ptr(out[2]),
+                                             _native.stream()), "mvsn_cloud_nearest")
+
+    _, btimes = timed(build, steps, warmup)
+    _, qtimes = timed(query, steps, warmup)
+    assert torch.equal(out[1], nn.index) and torch.equal(out[2], nn.within)
+    sub = pred[:TORCH_QUERIES].contiguous()
+    (tb, ti, tw), ttimes = timed(lambda: torch_cloud_nearest(sub, truth, threshold), steps, 1)
+    found = nn.index[:TORCH_QUERIES] >= 0
+    scale = N / float(sub.shape[0])
+    return {"cloud": {"threshold": threshold, "n_pred": N, "n_truth": Tn, "workspace_bytes": int(ws_bytes),
+                      "metrics": metrics, "within_mean": float(nn.within.float().mean()),
+                      "ms_per_call_median": float(np.median(times)), "ms_per_call_min": float(np.min(times)),
+                      "build_ms_median": float(np.median(btimes)), "query_ms_median": float(np.median(qtimes)),
+                      "torch_queries": int(sub.shape[0]), "torch_ms_median": float(np.median(ttimes)),
+                      "torch_ms_extrapolated_to_all_queries": float(np.median(ttimes)) * scale,
+                      "torch_found_differs": int((found != (ti >= 0)).sum()),
+                      "torch_max_abs_dist2_difference": float((tb - nn.dist2[:TORCH_QUERIES])[found & (ti >= 0)].abs().max())
+                      if bool((found & (ti >= 0)).any()) else 0.0}}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -152,7 +224,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False)
                            "mask_bytes": 5 * V * P + V * P}}
     merged = run_voxel(res, float(sc["K"][0, 0, 0]), steps, warmup) if voxel else {}
     oriented = run_normals(sc, res, steps, warmup) if normals else {}
-    return {**gated, **merged, **oriented, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    scored = run_cloud(sc, nb, res, steps, warmup) if cloud else {}
+    return {**gated, **merged, **oriented, **scored, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -167,10 +240,12 @@ def main():
     ap.add_argument("--confidence", action="store_true", help="also time the call gated by a confidence map")
     ap.add_argument("--voxel", action="store_true", help="also time voxel_merge of the fused cloud, and its torch form")
     ap.add_argument("--normals", action="store_true", help="also time depth_normals, and its torch form")
+    ap.add_argument("--cloud-metrics", action="store_true",
+                    help="also score a perturbed fusion against the true one (cloud_metrics) and time cloud_nearest")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
-        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals)), flush=True)
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics)), flush=True)
 
 
 if __name__ == "__main__":
