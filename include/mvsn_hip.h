@@ -679,6 +679,50 @@ int mvsn_cloud_nearest(const float *query, long nq, float inv_cell, float r2, co
                        size_t workspace_bytes, long n_target, float *dist2, int64_t *index, int *within,
                        mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense TSDF volume: depth maps integrated along the viewing rays, and a mesh taken from the volume by Surface Nets
+ * (multi_view_stereonet_amd/tsdf.py; the semantics, every fp32 step and the error bounds are DESIGN.md section 15).
+ * The state is planar fp32 in the layout (nz,ny,nx), x fastest: sdf_sum = sum w t, weight = sum w, color_sum
+ * (3,nz,ny,nx) = sum w rgb or NULL; at most 2^31 - 1 voxels and 2^24 along an axis (rows and cols of the maps too: every
+ * index is an exact fp32); the centre of voxel (i,j,k) is origin + voxel_size (i,j,k).
+ * mvsn_tsdf_integrate: per voxel centre p and view v in index order, with P_v = K_v T_v^-1 (3x4; fp64, rounded once;
+ *   K's bottom row taken to be (0,0,1)): z = P row 2 . (p,1); skip unless z > min_depth; (u, v) = rows 0, 1 over z;
+ *   col = floor(u + 0.5), row = floor(v + 0.5), skip unless inside the map; D = depth[v,row,col], skip unless D is finite
+ *   and > 0, valid (if given) is non-zero and the weight w (1 without weights) is finite and > 0; sdf = D - z, skip if
+ *   sdf < -trunc; t = min(sdf, trunc); sdf_sum = fma(w, t, sdf_sum), weight += w, color_sum = fma(w, rgb, color_sum).
+ *   The state is read once and written once whatever n_views is; a voxel no view updates keeps its bits; nothing outside
+ *   the maps is read.  One launch, no workspace, no atomics.
+ *   depth (V,rows,cols)  valid (V,rows,cols) u8 or NULL  weights (V,rows,cols) or NULL  images (V,3,rows,cols) with
+ *   color_sum, or both NULL  K, T_cam_in_world (V,4,4)  1 <= V <= 65535
+ * mvsn_tsdf_camera_batch: the number of cameras the integration stages at once (more views loop inside the launch).
+ * mvsn_tsdf_classify / mvsn_tsdf_extract: Surface Nets.  A corner is observed when weight >= min_weight (its sdf_sum is
+ *   read only then) and inside when d = sdf_sum / weight < 0; cell (i,j,k), i < nx - 1 ..., is active when its 8 corners
+ *   are observed and not all of one sign; a grid edge (voxel a, axis) with observed endpoints of different sign emits a
+ *   quad when the 4 cells around it exist and are active.  Dims of at least 2 each.
+ *   classify (two launches and an 8-byte device copy) -> result (2 int64): [0] the number of vertices M, [1] M + the
+ *     number of quads; reading them back is the one host synchronisation of an extraction.
+ *   workspace: mvsn_tsdf_workspace_bytes(nx, ny, nz) bytes, 16-byte aligned, handed on to mvsn_tsdf_extract unchanged:
+ *     5 bytes per voxel (a code byte, the cell -> row int32 map), 24 bytes per 1024 voxels.
+ *   extract (three launches; n_vertices = 0: none) -> vertices (M,3): the mean of the cell's edge crossings
+ *     p0 + d0 / (d0 - d1) along the edge, in a fixed edge order; normals (M,3): the normalised sum of the differences of
+ *     d along the cell's 4 edges of each axis, (0,0,0) where that is zero or not finite; colors (M,3) u8 with color_sum,
+ *     or both NULL; cell (M) int64: the cell's linear index (k ny + j) nx + i, ascending; faces (2 quads,3) int64: two
+ *     triangles per quad, counter-clockwise seen from the positive side, ordered by (linear index of a) * 3 + axis.
+ * No atomics: every output is a deterministic function of the three state tensors.
+ * ------------------------------------------------------------------------------------------- */
+int mvsn_tsdf_camera_batch(void);
+int mvsn_tsdf_integrate(const float *depth, const uint8_t *valid, const float *weights, const float *images,
+                        const float *K, const float *T_cam_in_world, int n_views, int rows, int cols, int nx, int ny,
+                        int nz, float voxel_size, float origin_x, float origin_y, float origin_z, float trunc,
+                        float min_depth, float *sdf_sum, float *weight, float *color_sum, mvsn_stream_t stream);
+size_t mvsn_tsdf_workspace_bytes(int nx, int ny, int nz);
+int mvsn_tsdf_classify(const float *sdf_sum, const float *weight, int nx, int ny, int nz, float min_weight,
+                       int64_t *result, void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_tsdf_extract(const float *sdf_sum, const float *weight, const float *color_sum, int nx, int ny, int nz,
+                      float voxel_size, float origin_x, float origin_y, float origin_z, float min_weight,
+                      const void *workspace, size_t workspace_bytes, long n_vertices, long n_quads, float *vertices,
+                      float *normals, uint8_t *colors, int64_t *faces, int64_t *cell, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -128,6 +128,12 @@ SIGNATURES = {
     "mvsn_cloud_index_build": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_cloud_nearest": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_size_t, c_long] +
                            [c_void_p] * 3 + [c_void_p]),
+    "mvsn_tsdf_camera_batch": (c_int, []),
+    "mvsn_tsdf_integrate": (c_int, [c_void_p] * 6 + [c_int] * 6 + [ctypes.c_float] * 6 + [c_void_p] * 3 + [c_void_p]),
+    "mvsn_tsdf_workspace_bytes": (c_size_t, [c_int] * 3),
+    "mvsn_tsdf_classify": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_tsdf_extract": (c_int, [c_void_p] * 3 + [c_int] * 3 + [ctypes.c_float] * 5 + [c_void_p, c_size_t, c_long, c_long] +
+                          [c_void_p] * 5 + [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

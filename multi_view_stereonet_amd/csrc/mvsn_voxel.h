@@ -1,5 +1,6 @@
 // The hash grid's cell, key and hash, shared by the voxel merge (mvsn_voxel.hip) and the
-// nearest-neighbour index between clouds (mvsn_cloud.hip): both put a point into the same cell of the same grid.
+// nearest-neighbour index between clouds (mvsn_cloud.hip): both put a point into the same cell of the same grid; and the
+// declaration of the merge's scan kernel, which the TSDF extraction (mvsn_tsdf.hip) launches too.
 #pragma once
 #include "mvsn_common.h"
 
@@ -8,6 +9,13 @@ namespace mvsn {
 constexpr unsigned long long VX_EMPTY = ~0ull;          // bit 63 set: no 63-bit key equals it
 constexpr int VX_CELL_BIAS = 1 << 20;                   // cells in [-2^20, 2^20) per axis: 21 bits biased
 enum { VX_KEPT = 0, VX_DROPPED = 1, VX_OUT_OF_RANGE = 2 };
+constexpr int VX_SCAN_THREADS = 1024;                   // the one workgroup of voxel_scan_kernel
+
+// Defined in mvsn_voxel.hip; launch with one workgroup of VX_SCAN_THREADS threads: the exclusive prefix of n
+// per-workgroup counts in index order, and result[0] = their total.
+__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(const int *__restrict__ counts, long n,
+                                                                     int64_t *__restrict__ offsets,
+                                                                     unsigned long long *__restrict__ result);
 
 // Cell and in-cell fraction of one point, every step a single fp32 operation:
 // s = p - o, t = s * inv, c = floor(t), f = t - c, q = min(65535, (uint)(f * 65536)).  Contraction is off for the whole

@@ -32,7 +32,6 @@ namespace mvsn {
 constexpr int VX_THREADS = 256;
 constexpr int VX_PTS = 4;                               // consecutive points per thread in the count / rank kernels
 constexpr int VX_BLOCK_PTS = VX_THREADS * VX_PTS;       // points per workgroup there
-constexpr int VX_SCAN_THREADS = 1024;
 constexpr int VX_INIT_SLOTS = 4;                        // table slots per thread of the init kernel
 constexpr size_t VX_MIN_SLOTS = VX_THREADS * VX_INIT_SLOTS;
 constexpr size_t VX_MAX_SLOTS = (size_t)1 << 31;        // a slot index is an int32

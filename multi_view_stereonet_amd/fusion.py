@@ -11,7 +11,8 @@ cloud on a voxel grid: a surface that k views saw is in the fused cloud k times,
 camera; ``point_normals`` reads those maps at the points of a fused cloud and ``voxel_normals`` takes them through a merge.
 ``cloud_nearest`` (csrc/mvsn_cloud.hip) finds, for every point of one cloud, the nearest point of
 another within a radius, exactly; ``radius_outlier_mask`` is the same query of a cloud against itself
-(``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).
+(``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).  A dense TSDF volume that integrates the same
+depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -590,10 +591,12 @@ def reconstruct(net, images: torch.Tensor, K: torch.Tensor, T_cam_in_world: torc
     return out
 
 
-def write_ply(path: str, points, colors=None, confidence=None, normals=None) -> None:
+def write_ply(path: str, points, colors=None, confidence=None, normals=None, faces=None) -> None:
     """Binary little-endian PLY: float x, y, z per vertex, plus float nx, ny, nz (right after the position) when
     ``normals`` (N,3) is given, plus uchar red, green, blue when ``colors`` is given, plus float confidence (after the
-    colours) when ``confidence`` (N,) is given."""
+    colours) when ``confidence`` (N,) is given.  ``faces`` (F,3) integers (a mesh of ``tsdf.TSDFVolume.extract_mesh``)
+    adds ``element face F`` with ``property list uchar int vertex_indices`` after the vertex block; an index outside
+    [0, N) raises ValueError.  Without ``faces`` the file is what it was before the argument existed, byte for byte."""
     pts = (points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)).astype("<f4")
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError("points must be (N,3)")
@@ -613,6 +616,12 @@ def write_ply(path: str, points, colors=None, confidence=None, normals=None) -> 
         if conf.shape != (pts.shape[0],):
             raise ValueError("confidence must be (N,) like the points")
         fields += [("confidence", "<f4")]
+    if faces is not None:
+        tri = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu":
+            raise ValueError("faces must be (F,3) integers")
+        if tri.size and (tri.min() < 0 or tri.max() >= pts.shape[0]):
+            raise ValueError(f"faces must index the {pts.shape[0]} points: indices in [0, {pts.shape[0]})")
     rec = np.empty(pts.shape[0], dtype=fields)
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
     if normals is not None:
@@ -623,7 +632,12 @@ def write_ply(path: str, points, colors=None, confidence=None, normals=None) -> 
     if confidence is not None:
         rec["confidence"] = conf
     props = "".join(f"property {'float' if t == '<f4' else 'uchar'} {n}\n" for n, t in fields)
-    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\n{props}end_header\n"
+    face_props = f"element face {tri.shape[0]}\nproperty list uchar int vertex_indices\n" if faces is not None else ""
+    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\n{props}{face_props}end_header\n"
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
+        if faces is not None:
+            frec = np.empty(tri.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+            frec["n"], frec["v"] = 3, tri
+            f.write(frec.tobytes())

@@ -1,0 +1,228 @@
+"""A dense TSDF volume on the device: posed depth maps integrated along their viewing rays, and a triangle mesh taken
+from the volume by Surface Nets (DESIGN.md section 15 states the semantics, every fp32 step and the error bounds; the
+kernels are csrc/mvsn_tsdf.hip).
+
+Where ``fusion.fuse_depthmaps`` keeps or drops pixels, the volume averages: every voxel holds the weighted sum of the
+truncated signed distances the views saw at it, so a surface that k views saw is in the result once, free space is
+carved, and the gaps between pixels are filled.  ``TSDFVolume.integrate`` adds views, ``extract_mesh`` gives vertices
+with normals and colours and the triangles between them, and ``fusion.write_ply(..., faces=)`` saves them.
+
+Conventions are ``fusion``'s: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world``
+(V,4,4) maps camera coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel
+centres.  The signed distance is projective (depth minus the voxel's camera z) and positive towards the camera.
+"""
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native
+from .fusion import _check_frames
+
+MAX_VOXELS = 2 ** 31 - 1
+MAX_EXTENT = 2 ** 24                 # voxels along an axis, rows and columns of a map: every index is an exact float32
+
+
+class TSDFMesh(NamedTuple):
+    vertices: torch.Tensor           # (M,3) fp32 world coordinates, one per active cell
+    normals: torch.Tensor            # (M,3) fp32 unit vectors pointing outwards (towards the cameras), or (0,0,0)
+    colors: Optional[torch.Tensor]   # (M,3) uint8, or None for a volume without colour
+    faces: torch.Tensor              # (F,3) int64 rows of `vertices`, counter-clockwise seen from the outside
+    cell: torch.Tensor               # (M,) int64: the cell's linear index (k * Ny + j) * Nx + i, ascending
+
+
+def _positive_f32(value, name):
+    """``value`` as np.float32, formed once on the host; ValueError unless it is finite and > 0 there."""
+    with np.errstate(all="ignore"):
+        try:
+            v = np.float32(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a positive finite number, got {value!r}") from None
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"{name} must be finite and > 0 in float32, got {value!r}")
+    return v
+
+
+def _origin_f32(origin):
+    """``origin`` as three np.float32; ValueError unless they are three finite numbers."""
+    try:
+        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}") from None
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+    return o
+
+
+class TSDFVolume:
+    """``dims`` = (Nx,Ny,Nz) voxels of ``voxel_size`` whose first centre is ``origin``: the centre of voxel (i,j,k) is
+    ``origin + voxel_size * (i,j,k)``.  The state is three planar fp32 tensors in the layout (Nz,Ny,Nx), x fastest:
+    ``sdf_sum`` (sum of w t), ``weight`` (sum of w) and, with ``color=True``, ``color_sum`` (3,Nz,Ny,Nx) (sum of w rgb).
+    The volume stores sums, not a running mean, so views integrated one call at a time give the bits of one call with
+    all of them; the value of a voxel is ``sdf_sum / weight`` (``values()``).  ``trunc`` is the truncation distance."""
+
+    def __init__(self, dims: Sequence[int], voxel_size: float, origin: Sequence[float], trunc: float, device="cuda",
+                 color: bool = False):
+        try:
+            d = tuple(int(x) for x in dims)
+            if len(d) != 3 or any(x != y or isinstance(y, bool) for x, y in zip(d, dims)):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"dims must be three integers (Nx,Ny,Nz), got {dims!r}") from None
+        if min(d) < 1:
+            raise ValueError(f"dims must be at least 1 each, got {d}")
+        if max(d) > MAX_EXTENT:
+            raise ValueError(f"dims must be at most 2^24 each, got {d}")
+        if d[0] * d[1] * d[2] > MAX_VOXELS:
+            raise ValueError(f"at most 2^31 - 1 voxels, got {d[0]} x {d[1]} x {d[2]} = {d[0] * d[1] * d[2]}")
+        self.voxel_size = _positive_f32(voxel_size, "voxel_size")
+        self.trunc = _positive_f32(trunc, "trunc")
+        o = _origin_f32(origin)
+        self.dims, self.origin, self.device = d, o, torch.device(device)
+        nx, ny, nz = d
+        self.sdf_sum = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.color_sum = torch.zeros((3, nz, ny, nx), dtype=torch.float32, device=self.device) if color else None
+        self.device = self.sdf_sum.device          # (with its index: tensors are compared against it)
+
+    def reset(self) -> None:
+        """Zero the volume."""
+        self.sdf_sum.zero_()
+        self.weight.zero_()
+        if self.color_sum is not None:
+            self.color_sum.zero_()
+
+    def values(self) -> torch.Tensor:
+        """(Nz,Ny,Nx) fp32: ``sdf_sum / weight``, NaN where ``weight == 0``."""
+        return torch.where(self.weight == 0, torch.full_like(self.sdf_sum, float("nan")), self.sdf_sum / self.weight)
+
+    def integrate(self, depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, *,
+                  images: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                  weights: Optional[torch.Tensor] = None, min_depth: float = 0.0) -> None:
+        """Integrate ``depth`` (V,1,H,W) fp32, V <= 65535.  For every voxel centre p and every view in index order:
+        Xc = T_cam_in_world^-1 p, skipped unless z = Xc.z > ``min_depth``; the pixel is the one nearest to the projection
+        of Xc, skipped unless it lies in the map; D is the depth there, skipped unless it is finite and > 0, ``valid``
+        (V,1,H,W) bool / uint8 is set and the weight w there (``weights`` (V,1,H,W) fp32; 1 without) is finite and > 0;
+        sdf = D - z, skipped if sdf < -trunc; then ``sdf_sum += w * min(sdf, trunc)``, ``weight += w`` and, with
+        ``images`` (V,3,H,W) fp32 (which needs ``color=True``, and the reverse), ``color_sum += w * rgb``.  A voxel no view
+        updates keeps its bits.  ``K`` and ``T_cam_in_world`` may be of any floating-point dtype: the kernel reads their
+        float32 values (and forms the inverses from those in fp64).  Everything is validated here, before the launch; no
+        host synchronisation."""
+        if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
+            raise ValueError("depth must be a (V,1,H,W) tensor")
+        V, _, H, W = depth.shape
+        dev = depth.device
+        if V < 1 or H * W < 1:
+            raise ValueError("depth must hold at least one view of at least one pixel")
+        if depth.dtype != torch.float32:
+            raise ValueError(f"depth must be float32, got {depth.dtype}")
+        if V > 65535 or H * W > 2 ** 31 - 1 or max(H, W) > MAX_EXTENT:
+            raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
+        if dev != self.device:
+            raise ValueError(f"depth is on {dev}, the volume on {self.device}")
+        for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+            if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
+                raise ValueError(f"{name} must be a ({V},4,4) tensor")
+            if not m.is_floating_point():
+                raise ValueError(f"{name} must be a floating-point tensor, got {m.dtype}")
+            if m.device != dev:
+                raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+        if (images is not None) != (self.color_sum is not None):
+            raise ValueError("images need a volume made with color=True, and such a volume needs images")
+        if images is not None:
+            _check_frames("images", images, V, H, W, 3, (torch.float32,), dev)
+        if valid is not None:
+            _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
+        if weights is not None:
+            _check_frames("weights", weights, V, H, W, 1, (torch.float32,), dev)
+        with np.errstate(all="ignore"):
+            try:
+                md = np.float32(min_depth)
+            except (TypeError, ValueError):
+                raise ValueError(f"min_depth must be a finite number, got {min_depth!r}") from None
+        if not np.isfinite(md):
+            raise ValueError(f"min_depth must be a finite number, got {min_depth!r}")
+
+        if not depth.is_cuda:
+            raise RuntimeError("TSDFVolume.integrate runs on HIP devices only: make the volume and the depth maps on "
+                               "'cuda' (there is no CPU implementation)")
+        lib = _native.load()
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+        valid_c = valid.detach().contiguous().view(torch.uint8) if valid is not None else None
+        nx, ny, nz = self.dims
+        with torch.cuda.device(dev):
+            _native.check(lib.mvsn_tsdf_integrate(
+                _native.ptr(depth.detach().contiguous()), _native.ptr(valid_c),
+                _native.ptr(weights.detach().contiguous() if weights is not None else None),
+                _native.ptr(images.detach().contiguous() if images is not None else None), _native.ptr(f32(K)),
+                _native.ptr(f32(T_cam_in_world)), V, H, W, nx, ny, nz, float(self.voxel_size), float(self.origin[0]),
+                float(self.origin[1]), float(self.origin[2]), float(self.trunc), float(md), _native.ptr(self.sdf_sum),
+                _native.ptr(self.weight), _native.ptr(self.color_sum), _native.stream()), "mvsn_tsdf_integrate")
+
+    def extract_mesh(self, min_weight: float = 1.0) -> TSDFMesh:
+        """The surface of the volume by Surface Nets, a pure function of the state tensors.  A voxel is observed when
+        ``weight >= min_weight`` and inside when its value is < 0 (exactly 0 counts as outside); a cell of 2x2x2 voxels
+        whose corners are all observed and not all of one sign gets one vertex, the mean of the zero crossings on its
+        edges, with the normalised gradient of the values as its normal (pointing outwards, towards the cameras) and the
+        interpolated colour; every grid edge with a sign change whose four cells all have a vertex gives a quad, split
+        into two triangles.  Vertices come ordered by ``cell``, faces by (voxel, axis) of their edge; the outputs are
+        bitwise reproducible.  A volume with a dimension < 2, or with no active cell, gives empties.  The one host
+        synchronisation is the read of the two counts that size the outputs."""
+        return extract_mesh(self.sdf_sum, self.weight, self.color_sum, self.voxel_size, self.origin, min_weight)
+
+
+def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[torch.Tensor], voxel_size: float,
+                 origin: Sequence[float], min_weight: float = 1.0) -> TSDFMesh:
+    """``TSDFVolume.extract_mesh`` on state tensors of any origin: ``sdf_sum`` and ``weight`` (Nz,Ny,Nx) fp32,
+    ``color_sum`` (3,Nz,Ny,Nx) fp32 or None."""
+    if not torch.is_tensor(sdf_sum) or sdf_sum.dim() != 3 or sdf_sum.dtype != torch.float32:
+        raise ValueError("sdf_sum must be a (Nz,Ny,Nx) float32 tensor")
+    nz, ny, nx = (int(x) for x in sdf_sum.shape)
+    dev = sdf_sum.device
+    if not torch.is_tensor(weight) or tuple(weight.shape) != (nz, ny, nx) or weight.dtype != torch.float32:
+        raise ValueError(f"weight must be a ({nz},{ny},{nx}) float32 tensor like sdf_sum")
+    if weight.device != dev:
+        raise ValueError(f"weight is on {weight.device}, sdf_sum on {dev}")
+    if color_sum is not None:
+        if not torch.is_tensor(color_sum) or tuple(color_sum.shape) != (3, nz, ny, nx) or color_sum.dtype != torch.float32:
+            raise ValueError(f"color_sum must be a (3,{nz},{ny},{nx}) float32 tensor")
+        if color_sum.device != dev:
+            raise ValueError(f"color_sum is on {color_sum.device}, sdf_sum on {dev}")
+    if nx * ny * nz > MAX_VOXELS or max(nx, ny, nz) > MAX_EXTENT:
+        raise ValueError(f"at most 2^31 - 1 voxels and 2^24 along an axis, got {nx} x {ny} x {nz}")
+    v = _positive_f32(voxel_size, "voxel_size")
+    mw = _positive_f32(min_weight, "min_weight")
+    o = _origin_f32(origin)
+
+    def mesh(m, f):
+        return TSDFMesh(torch.empty((m, 3), dtype=torch.float32, device=dev),
+                        torch.empty((m, 3), dtype=torch.float32, device=dev),
+                        torch.empty((m, 3), dtype=torch.uint8, device=dev) if color_sum is not None else None,
+                        torch.empty((f, 3), dtype=torch.int64, device=dev),
+                        torch.empty((m,), dtype=torch.int64, device=dev))
+    if min(nx, ny, nz) < 2:            # no cell, nothing to launch: empties on the state's device
+        return mesh(0, 0)
+    if not sdf_sum.is_cuda:
+        raise RuntimeError("extract_mesh runs on HIP devices only: make the volume on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, w = sdf_sum.detach().contiguous(), weight.detach().contiguous()
+    c = color_sum.detach().contiguous() if color_sum is not None else None
+    ws_bytes = lib.mvsn_tsdf_workspace_bytes(nx, ny, nz)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_tsdf_classify(_native.ptr(s), _native.ptr(w), nx, ny, nz, float(mw), _native.ptr(head),
+                                             _native.ptr(ws), ws_bytes, st), "mvsn_tsdf_classify")
+        m, both = head.tolist()        # the one host synchronisation: sizes the outputs
+        quads = both - m
+        out = mesh(m, 2 * quads)
+        if m == 0:                     # no active cell
+            return out
+        _native.check(lib.mvsn_tsdf_extract(_native.ptr(s), _native.ptr(w), _native.ptr(c), nx, ny, nz, float(v),
+                                            float(o[0]), float(o[1]), float(o[2]), float(mw), _native.ptr(ws), ws_bytes,
+                                            m, quads, _native.ptr(out.vertices), _native.ptr(out.normals),
+                                            _native.ptr(out.colors), _native.ptr(out.faces), _native.ptr(out.cell), st),
+                      "mvsn_tsdf_extract")
+    return out

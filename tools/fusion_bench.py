@@ -20,7 +20,14 @@ prediction, scores it against the cloud of the true depths (metrics.cloud_metric
 footprint at the median fused depth) and reports, as "cloud", the metrics, ms per cloud_nearest call (prediction against
 truth) with the index build and the query timed separately between device events, and the same query composed from torch
 ops on the device -- torch.cdist + min over chunks of the target -- for the first TORCH_QUERIES queries only (the full
-composition forms N x T distances: 7e13 at these sizes), with its extrapolation to all queries."""
+composition forms N x T distances: 7e13 at these sizes), with its extrapolation to all queries.  --tsdf: also integrates
+each scene's V views into a 256^3 volume (tsdf.TSDFVolume; 2 cm voxels around the scene, truncation 4 voxels) with and
+without colour and reports, as "tsdf", ms per integrate call next to the same integration composed from torch ops on the
+device (projection, nearest gather, masked accumulate, a view at a time), the bytes of state the call must move (read
+once, written once) over its time as a share of STREAMING_BYTES_PER_S (the 6.3 TB/s a streaming kernel reaches on this
+device) and of DEPTH_NORMALS_BYTES_PER_S (the 2.95 TB/s depth_normals_kernel reached), ms per extract_mesh call with M and F, and the
+mesh vertices scored by metrics.cloud_metrics against the fused cloud of the true depths (points on the analytic
+surfaces; threshold one voxel)."""
 import argparse
 import json
 import os
@@ -36,6 +43,7 @@ from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, depth_normals,  # noqa: E402
                                              fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
+from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
 SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
 
@@ -207,7 +215,76 @@ def run_cloud(sc, nb, res, steps, warmup):
                       if bool((found & (ti >= 0)).any()) else 0.0}}
 
 
-def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False):
+TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN = (256, 256, 256), 0.02, (-2.56, -2.56, 3.2)
+# what a streaming kernel reaches on this device, and what depth_normals_kernel itself reached
+STREAMING_BYTES_PER_S, DEPTH_NORMALS_BYTES_PER_S = 6.3e12, 2.95e12
+
+
+def torch_tsdf_integrate(state, depth, images, K, T, voxel, origin, trunc):
+    """The integration from torch ops, a view at a time: the same projection, nearest gather and masked accumulate, every
+    intermediate a volume-sized tensor in HBM (what a caller had to write without the kernel)."""
+    s, w, c = state
+    nz, ny, nx = s.shape
+    dev = s.device
+    ax = [torch.arange(n, device=dev, dtype=torch.float32) * voxel + o for n, o in zip((nx, ny, nz), origin)]
+    pz, py, px = torch.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    P = (K[:, :3, :3].double() @ torch.linalg.inv(T.double())[:, :3, :]).float()
+    H, W = depth.shape[-2:]
+    for v in range(depth.shape[0]):
+        a = [P[v, r, 0] * px + P[v, r, 1] * py + P[v, r, 2] * pz + P[v, r, 3] for r in range(3)]
+        z = a[2]
+        col, row = torch.floor(a[0] / z + 0.5), torch.floor(a[1] / z + 0.5)
+        ok = (z > 0) & (col >= 0) & (col <= W - 1) & (row >= 0) & (row <= H - 1)
+        pix = torch.where(ok, row * W + col, torch.zeros_like(col)).long()
+        D = depth[v, 0].reshape(-1)[pix]
+        sdf = D - z
+        ok &= (D > 0) & ~(sdf < -trunc)
+        s += torch.where(ok, sdf.clamp(max=trunc), torch.zeros_like(sdf))
+        w += ok
+        if c is not None:
+            c += torch.where(ok, images[v].reshape(3, -1)[:, pix], torch.zeros_like(c))
+
+
+def run_tsdf(sc, res, steps, warmup):
+    steps, warmup = min(steps, 5), min(warmup, 1)           # (the torch composition takes seconds)
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    dev = depth.device
+    trunc = 4 * TSDF_VOXEL
+    out = {"dims": list(TSDF_DIMS), "voxel_size": TSDF_VOXEL, "trunc": trunc, "views": int(depth.shape[0])}
+    n = TSDF_DIMS[0] * TSDF_DIMS[1] * TSDF_DIMS[2]
+    for color in (False, True):
+        vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, trunc, device=dev, color=color)
+        kw = {"images": images} if color else {}
+        _, times = timed(lambda: vol.integrate(depth, K, T, **kw), steps, warmup)
+        state_bytes = 2 * 4 * n * (5 if color else 2)        # every plane read once and written once
+        _, ttimes = timed(lambda: torch_tsdf_integrate(
+            (torch.zeros_like(vol.sdf_sum), torch.zeros_like(vol.weight), torch.zeros_like(vol.color_sum) if color else None),
+            depth, images, K, T, float(vol.voxel_size), [float(x) for x in vol.origin], float(vol.trunc)), 2, 1)
+        # one integration each into fresh volumes: where the two count different views
+        vol.reset()
+        vol.integrate(depth, K, T, **kw)
+        tstate = (torch.zeros_like(vol.sdf_sum), torch.zeros_like(vol.weight),
+                  torch.zeros_like(vol.color_sum) if color else None)
+        torch_tsdf_integrate(tstate, depth, images, K, T, float(vol.voxel_size), [float(x) for x in vol.origin],
+                             float(vol.trunc))
+        differs = float((vol.weight != tstate[1]).float().mean())
+        rate = state_bytes / (float(np.median(times)) * 1e-3)
+        out["colour" if color else "plain"] = {
+            "ms_per_call_median": float(np.median(times)), "ms_per_call_min": float(np.min(times)),
+            "torch_ms_per_call_median": float(np.median(ttimes)), "state_bytes": state_bytes,
+            "state_bytes_per_s_at_median": rate, "share_of_streaming_rate": rate / STREAMING_BYTES_PER_S,
+            "share_of_depth_normals_rate": rate / DEPTH_NORMALS_BYTES_PER_S,
+            "voxels_whose_view_count_differs_from_torch": differs}
+        if color:
+            mesh, etimes = timed(lambda: vol.extract_mesh(), steps, warmup)
+            out["extract"] = {"ms_per_call_median": float(np.median(etimes)), "ms_per_call_min": float(np.min(etimes)),
+                              "M": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0]),
+                              "observed_fraction": float((vol.weight >= 1).float().mean())}
+            out["mesh_against_surface"] = cloud_metrics(mesh.vertices, res.points, TSDF_VOXEL)
+    return {"tsdf": out}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -225,7 +302,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     merged = run_voxel(res, float(sc["K"][0, 0, 0]), steps, warmup) if voxel else {}
     oriented = run_normals(sc, res, steps, warmup) if normals else {}
     scored = run_cloud(sc, nb, res, steps, warmup) if cloud else {}
-    return {**gated, **merged, **oriented, **scored, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    volume = run_tsdf(sc, res, steps, warmup) if tsdf else {}
+    return {**gated, **merged, **oriented, **scored, **volume, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -242,10 +320,13 @@ def main():
     ap.add_argument("--normals", action="store_true", help="also time depth_normals, and its torch form")
     ap.add_argument("--cloud-metrics", action="store_true",
                     help="also score a perturbed fusion against the true one (cloud_metrics) and time cloud_nearest")
+    ap.add_argument("--tsdf", action="store_true",
+                    help="also integrate the views into a 256^3 TSDF volume, extract its mesh and score it")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
-        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics)), flush=True)
+        print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
+                             a.tsdf)), flush=True)
 
 
 if __name__ == "__main__":
