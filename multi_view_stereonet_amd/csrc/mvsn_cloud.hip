@@ -4,12 +4,12 @@
 //
 // mvsn_cloud_index_build: a counting sort of the target by grid cell through section 12's hash table, six launches:
 //   cloud_init_kernel     every key empty, every population and cursor zero; the status word zeroed
-//   cloud_assign_kernel   one thread per target point: cell and key in fp32 (mvsn_voxel.h: the voxel merge's own
-//                         functions, cell size max_dist, origin 0), linear probing with a 64-bit compare-and-swap on
-//                         empty keys only, a no-return atomicAdd of 1 to the slot's population; the point's slot goes
+//   cloud_assign_kernel   one thread per target point: cell, key and insert of mvsn_voxel.h (the voxel merge's own
+//                         functions, cell size max_dist, origin 0: linear probing with a 64-bit compare-and-swap on
+//                         empty keys only), a no-return atomicAdd of 1 to the slot's population; the point's slot goes
 //                         to the workspace (-1 = never a neighbour)
 //   cloud_count_kernel    1024 consecutive slots per workgroup: the sum of their populations
-//   cloud_scan_kernel     one workgroup: exclusive prefix of those sums in a fixed order
+//   geom_scan_kernel      one workgroup: exclusive prefix of those sums in a fixed order (mvsn_geom.h; no total)
 //   cloud_start_kernel    the count kernel's blocking again: the exclusive prefix inside the workgroup -> start[slot]
 //   cloud_scatter_kernel  one thread per target point: a returning atomicAdd on its slot's cursor gives its place among
 //                         the cell's records; one 16-byte record (x, y, z, row as bits) at start[slot] + place
@@ -24,6 +24,7 @@
 // sort; every loop is bounded (a probe sequence visits every slot at most once, then sets a status bit and ends) and
 // nothing waits on another thread.
 #include "mvsn_common.h"
+#include "mvsn_geom.h"
 #include "mvsn_voxel.h"
 
 namespace mvsn {
@@ -31,9 +32,7 @@ namespace mvsn {
 constexpr int CL_THREADS = 256;
 constexpr int CL_SLOTS = 4;                             // table slots per thread of the init / count / start kernels
 constexpr int CL_BLOCK_SLOTS = CL_THREADS * CL_SLOTS;   // slots per workgroup there
-constexpr int CL_SCAN_THREADS = 1024;
 constexpr size_t CL_MIN_SLOTS = CL_BLOCK_SLOTS;
-constexpr size_t CL_MAX_SLOTS = (size_t)1 << 31;        // a slot index is an int32
 
 // byte offsets of the workspace sections (each 256-byte aligned)
 struct CloudLayout {
@@ -42,22 +41,19 @@ struct CloudLayout {
   long blocks;    // workgroups of the count / start kernels
 };
 
-inline size_t cl_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline CloudLayout cloud_layout(long n) {
   CloudLayout l;
-  l.slots = CL_MIN_SLOTS;
-  while (l.slots < 2 * (size_t)n && l.slots < CL_MAX_SLOTS) l.slots <<= 1;
+  l.slots = hash_table_slots(n, CL_MIN_SLOTS);
   l.blocks = (long)(l.slots / CL_BLOCK_SLOTS);
   l.keys = 0;
-  l.pop = cl_align(l.keys + sizeof(unsigned long long) * l.slots);
-  l.start = cl_align(l.pop + sizeof(int) * l.slots);
-  l.cursor = cl_align(l.start + sizeof(int) * l.slots);
-  l.slot = cl_align(l.cursor + sizeof(int) * l.slots);
-  l.records = cl_align(l.slot + sizeof(int) * (size_t)n);
-  l.counts = cl_align(l.records + 16 * (size_t)n);
-  l.offsets = cl_align(l.counts + sizeof(int) * (size_t)l.blocks);
-  l.bytes = cl_align(l.offsets + sizeof(int64_t) * (size_t)l.blocks);
+  l.pop = align256(l.keys + sizeof(unsigned long long) * l.slots);
+  l.start = align256(l.pop + sizeof(int) * l.slots);
+  l.cursor = align256(l.start + sizeof(int) * l.slots);
+  l.slot = align256(l.cursor + sizeof(int) * l.slots);
+  l.records = align256(l.slot + sizeof(int) * (size_t)n);
+  l.counts = align256(l.records + 16 * (size_t)n);
+  l.offsets = align256(l.counts + sizeof(int) * (size_t)l.blocks);
+  l.bytes = align256(l.offsets + sizeof(int64_t) * (size_t)l.blocks);
   return l;
 }
 
@@ -88,18 +84,7 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_assign_kernel(const float *_
   const int state = voxel_cell(p, inv, o, c, q);
   int found = -1;
   if (state == VX_KEPT) {
-    const unsigned long long key = voxel_key(c);
-    const size_t mask = slots - 1;
-    size_t h = (size_t)voxel_hash(key) & mask;
-    for (size_t probe = 0; probe < slots; ++probe) {        // bounded: every slot at most once
-      unsigned long long seen = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (seen == VX_EMPTY) seen = atomicCAS(keys + h, VX_EMPTY, key);
-      if (seen == VX_EMPTY || seen == key) {
-        found = (int)h;
-        break;
-      }
-      h = (h + 1) & mask;
-    }
+    found = hash_insert(keys, slots, voxel_key(c));
     if (found >= 0)
       atomicAdd(pop + found, 1);
     else
@@ -117,37 +102,8 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_count_kernel(const int *__re
   __shared__ int swave[CL_THREADS / 64];
   const size_t s = ((size_t)blockIdx.x * CL_THREADS + threadIdx.x) * CL_SLOTS;
   const int4 w = *reinterpret_cast<const int4 *>(pop + s);
-  int mine = (w.x + w.y) + (w.z + w.w);
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = (swave[0] + swave[1]) + (swave[2] + swave[3]);
-}
-
-// exclusive prefix of n per-workgroup counts, in index order (section 12's scan, restated here so that the voxel
-// merge's device code stays as it is)
-__global__ __launch_bounds__(CL_SCAN_THREADS) void cloud_scan_kernel(const int *__restrict__ counts, long n,
-                                                                     int64_t *__restrict__ offsets) {
-  __shared__ int64_t swave[CL_SCAN_THREADS / 64];
-  const long per = (n + CL_SCAN_THREADS - 1) / CL_SCAN_THREADS;
-  const long lo = min((long)threadIdx.x * per, n), hi = min(lo + per, n);
-  int64_t own = 0;
-  for (long i = lo; i < hi; ++i) own += counts[i];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t incl = own;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int64_t o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) swave[wave] = incl;
-  __syncthreads();
-  int64_t base = 0;
-  for (int w = 0; w < wave; ++w) base += swave[w];
-  int64_t run = base + incl - own;
-  for (long i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
+  const int sum = block_sum_256((w.x + w.y) + (w.z + w.w), swave);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void cloud_start_kernel(const int *__restrict__ pop,
@@ -297,7 +253,8 @@ extern "C" int mvsn_cloud_index_build(const float *target, long n, float cell, f
   if (int e = check_launch("mvsn_cloud_index_build: assign")) return e;
   hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)l.blocks), dim3(CL_THREADS), 0, st, pop, counts);
   if (int e = check_launch("mvsn_cloud_index_build: count")) return e;
-  hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(CL_SCAN_THREADS), 0, st, counts, l.blocks, offsets);
+  hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(GEOM_SCAN_THREADS), 0, st, (const int *)counts, l.blocks, offsets,
+                     (int64_t *)nullptr);
   if (int e = check_launch("mvsn_cloud_index_build: scan")) return e;
   hipLaunchKernelGGL(cloud_start_kernel, dim3((unsigned)l.blocks), dim3(CL_THREADS), 0, st, pop, offsets, start);
   if (int e = check_launch("mvsn_cloud_index_build: start")) return e;

@@ -9,12 +9,13 @@
 //                       pixel and slot: project, bilinear-gather the neighbour's depth (four taps through L2/MALL),
 //                       project back, test; writes the fused depth (0 = not kept), the count map and one kept-pixel
 //                       count per workgroup
-//   scan_kernel         one workgroup: exclusive prefix of those counts in a fixed order, and the total
-//   emit_kernel         the consistency kernel's blocking again: kept pixels ranked inside the workgroup by wave
-//                       ballots + mbcnt and a cross-wave LDS prefix, written at the workgroup's scanned offset
+//   geom_scan_kernel    one workgroup: exclusive prefix of those counts in a fixed order, and the total (mvsn_geom.h)
+//   emit_kernel         the consistency kernel's blocking again: kept pixels ranked inside the workgroup (block_rank
+//                       of mvsn_geom.h), written at the workgroup's scanned offset
 // No atomics anywhere: every output is a deterministic function of the inputs.  The bottom row of every K is taken to be
 // (0, 0, 1) (not checked on the device): the third row of P_rs then yields the neighbour's camera z itself.
 #include "mvsn_common.h"
+#include "mvsn_geom.h"
 
 namespace mvsn {
 
@@ -23,7 +24,6 @@ constexpr int FU_PIX = 4;                               // consecutive pixels pe
 constexpr int FU_BLOCK_PIX = FU_THREADS * FU_PIX;       // pixels per workgroup
 constexpr int FU_MAX_SLOTS = 32;
 constexpr int FU_MAP = 24;                              // floats per slot: P_rs (3x4) then P_sr (3x4)
-constexpr int FU_SCAN_THREADS = 1024;
 
 // byte offsets of the workspace sections (each 256-byte aligned)
 struct FusionLayout {
@@ -31,21 +31,21 @@ struct FusionLayout {
   long blocks;   // pixel blocks per reference view
 };
 
-inline size_t fu_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline FusionLayout fusion_layout(int n_ref, int n_slots, int rows, int cols) {
   FusionLayout l;
   const long P = (long)rows * cols;
   l.blocks = (P + FU_BLOCK_PIX - 1) / FU_BLOCK_PIX;
   l.maps = 0;
-  l.world = fu_align(l.maps + sizeof(float) * FU_MAP * (size_t)n_ref * n_slots);
-  l.counts = fu_align(l.world + sizeof(float) * 12 * (size_t)n_ref);
-  l.offsets = fu_align(l.counts + sizeof(int) * (size_t)n_ref * l.blocks);
-  l.bytes = fu_align(l.offsets + sizeof(int64_t) * (size_t)n_ref * l.blocks);
+  l.world = align256(l.maps + sizeof(float) * FU_MAP * (size_t)n_ref * n_slots);
+  l.counts = align256(l.world + sizeof(float) * 12 * (size_t)n_ref);
+  l.offsets = align256(l.counts + sizeof(int) * (size_t)n_ref * l.blocks);
+  l.bytes = align256(l.offsets + sizeof(int64_t) * (size_t)n_ref * l.blocks);
   return l;
 }
 
-__device__ inline void inv3_d(const float *K, double *o) {   // top-left 3x3 of a row-major 4x4, inverted in fp64
+// top-left 3x3 of a row-major 4x4, inverted in fp64.  Not mvsn_geom.h's inv3_d: this file is compiled with contraction
+// allowed, these products fuse, and the fp32 maps pair_setup_kernel rounds from them are pinned bit for bit by the tests.
+__device__ inline void inv3_fused_d(const float *K, double *o) {
   const double a = K[0], b = K[1], c = K[2], d = K[4], e = K[5], f = K[6], g = K[8], h = K[9], i = K[10];
   const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
   const double det = a * A + b * B + c * C, r = 1.0 / det;
@@ -57,7 +57,7 @@ __device__ inline void inv3_d(const float *K, double *o) {   // top-left 3x3 of 
 // inverse of an affine pose [A t; 0 0 0 1] in fp64: [A^-1, -A^-1 t] (3x4 rows)
 __device__ inline void pose_inv_d(const float *T, double *o) {
   double Ai[9];
-  inv3_d(T, Ai);
+  inv3_fused_d(T, Ai);
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) o[i * 4 + j] = Ai[i * 3 + j];
     o[i * 4 + 3] = -(Ai[i * 3 + 0] * T[3] + Ai[i * 3 + 1] * T[7] + Ai[i * 3 + 2] * T[11]);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void pair_setup_kernel(const float *__restrict_
   if (rv < 0 || rv >= n_views) return;            // (validated on the host; never read out of bounds)
   const float *Kr = K + (size_t)rv * 16, *Tr = T + (size_t)rv * 16;
   double Krinv[9];
-  inv3_d(Kr, Krinv);
+  inv3_fused_d(Kr, Krinv);
   if (j == n_slots) {                               // pixel (x f, y f, f, 1) of the reference -> world
     const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     pair_map(nullptr, I, Tr, Krinv, world + (size_t)r * 12);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64) void pair_setup_kernel(const float *__restrict_
   if (s < 0 || s >= n_views) return;
   const float *Ks = K + (size_t)s * 16, *Ts = T + (size_t)s * 16;
   double Ksinv[9], Trinv[12], Tsinv[12];
-  inv3_d(Ks, Ksinv);
+  inv3_fused_d(Ks, Ksinv);
   pose_inv_d(Tr, Trinv);
   pose_inv_d(Ts, Tsinv);
   float *m = maps + ((size_t)r * n_slots + j) * FU_MAP;
@@ -253,38 +253,8 @@ __global__ __launch_bounds__(FU_THREADS) void consistency_kernel(
         if (p0 + k < P) fo[k] = f[k], co[k] = (uint8_t)cnt[k];
     }
   }
-  for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
-  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = kept;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    block_counts[(size_t)r * gridDim.x + blockIdx.x] = (swave[0] + swave[1]) + (swave[2] + swave[3]);
-}
-
-// exclusive prefix of n per-workgroup counts, in index order, and their total
-__global__ __launch_bounds__(FU_SCAN_THREADS) void scan_kernel(const int *__restrict__ counts, long n,
-                                                               int64_t *__restrict__ offsets,
-                                                               int64_t *__restrict__ total) {
-  __shared__ int64_t swave[FU_SCAN_THREADS / 64];
-  const long per = (n + FU_SCAN_THREADS - 1) / FU_SCAN_THREADS;
-  const long lo = min((long)threadIdx.x * per, n), hi = min(lo + per, n);
-  int64_t own = 0;
-  for (long i = lo; i < hi; ++i) own += counts[i];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t incl = own;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int64_t o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) swave[wave] = incl;
-  __syncthreads();
-  int64_t base = 0;
-  for (int w = 0; w < wave; ++w) base += swave[w];
-  int64_t run = base + incl - own;
-  for (long i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  if (threadIdx.x == FU_SCAN_THREADS - 1) *total = run;
+  kept = block_sum_256(kept, swave);
+  if (threadIdx.x == 0) block_counts[(size_t)r * gridDim.x + blockIdx.x] = kept;
 }
 
 __global__ __launch_bounds__(FU_THREADS) void emit_kernel(const float *__restrict__ fused,
@@ -303,25 +273,16 @@ __global__ __launch_bounds__(FU_THREADS) void emit_kernel(const float *__restric
   const long p0 = ((long)blockIdx.x * FU_THREADS + threadIdx.x) * FU_PIX;
   float f[FU_PIX];
   load_pix(fused + (int64_t)r * P, p0, P, f);
-  // rank among the workgroup's kept pixels: lanes below this one (one ballot per pixel slot, mbcnt), then the
-  // pixels of this lane before each one, then the waves below this one
-  unsigned long long ballot[FU_PIX];
-  int below = 0, wave_total = 0;
+  bool kept[FU_PIX];
 #pragma unroll
-  for (int k = 0; k < FU_PIX; ++k) {
-    ballot[k] = __ballot(p0 + k < P && f[k] > 0.0f);
-    below += __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot[k], 0));
-    wave_total += __popcll(ballot[k]);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) swave[wave] = wave_total;
-  __syncthreads();
-  int64_t idx = offsets[(size_t)r * gridDim.x + blockIdx.x] + below;
-  for (int w = 0; w < wave; ++w) idx += swave[w];
+  for (int k = 0; k < FU_PIX; ++k) kept[k] = p0 + k < P && f[k] > 0.0f;
+  // rank among the workgroup's kept pixels, then the pixels of this thread before each one (the barrier inside also
+  // publishes sw)
+  int64_t idx = offsets[(size_t)r * gridDim.x + blockIdx.x] + block_rank(kept, swave);
   const int rv = ref_views[r];
 #pragma unroll
   for (int k = 0; k < FU_PIX; ++k) {
-    if (!(p0 + k < P && f[k] > 0.0f)) continue;
+    if (!kept[k]) continue;
     if (idx < capacity) {                           // (capacity = the scanned total: always true)
       const long p = p0 + k;
       const float x = (float)(p % cols) * f[k], y = (float)(p / cols) * f[k];
@@ -382,7 +343,8 @@ extern "C" int mvsn_fusion_consistency(const float *depth, const uint8_t *valid,
                      ref_views, neighbours, maps, n_views, n_slots, rows, cols, max_reproj_px, max_rel_depth,
                      min_consistent, fused_depth, count, counts);
   if (int e = check_launch("mvsn_fusion_consistency: consistency")) return e;
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(FU_SCAN_THREADS), 0, st, counts, (long)n_ref * l.blocks, offsets, total);
+  hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(GEOM_SCAN_THREADS), 0, st, (const int *)counts,
+                     (long)n_ref * l.blocks, offsets, total);
   return check_launch("mvsn_fusion_consistency: scan");
 }
 

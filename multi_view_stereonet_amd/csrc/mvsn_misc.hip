@@ -2,6 +2,7 @@
 // resize of idepth maps and hypothesis masks, multi-source fusion.
 #include <type_traits>
 
+#include "mvsn_geom.h"
 #include "mvsn_resident.h"
 
 namespace mvsn {
@@ -1011,16 +1012,6 @@ __global__ __launch_bounds__(256) void confidence_mask_kernel(const float *__res
   out[i] = keep ? 1 : 0;
 }
 
-// out[i] = maps[view[i] * HW + pixel[i]]; an index outside the maps is never dereferenced (NaN)
-__global__ __launch_bounds__(256) void fusion_gather_kernel(const float *__restrict__ maps, const int *__restrict__ view,
-                                                            const int *__restrict__ pixel, int V, long HW, long count,
-                                                            float *__restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const int v = view[i], q = pixel[i];
-  out[i] = (v >= 0 && v < V && q >= 0 && q < HW) ? maps[(size_t)v * HW + q] : NAN;
-}
-
 }  // namespace mvsn
 
 extern "C" int mvsn_soft_argmin_confidence(const float *cost, const float *idepth_samples, int n, int D, int pixels,
@@ -1058,7 +1049,7 @@ extern "C" int mvsn_fusion_gather(const float *maps, const int *view, const int 
   MVSN_REQUIRE(n_views > 0 && pixels_per_view > 0 && pixels_per_view <= 2147483647L && count > 0 &&
                    (count + 255) / 256 <= 2147483647L,
                MVSN_E_BADARG, "mvsn_fusion_gather: bad sizes");
-  hipLaunchKernelGGL(mvsn::fusion_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(mvsn::gather_kernel<1>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      maps, view, pixel, n_views, pixels_per_view, count, out);
   return mvsn::check_launch("mvsn_fusion_gather");
 }

@@ -8,7 +8,7 @@
 //                            Every load is issued before the first use, at an address clamped into the view, with an
 //                            in-range flag kept beside it: never a read outside the maps.  K^-1 (fp64, rounded once) and R
 //                            are formed by the workgroup's first lanes into LDS while those loads are in flight.
-//   normals_gather_kernel    one thread per point: the three planes of the map at (view, pixel)
+//   gather_kernel<3>         mvsn_geom.h: one thread per point, the three planes of the map at (view, pixel)
 //   voxel_normals_*          zero the accumulators / one thread per point: three no-return 64-bit integer atomicAdd of the
 //                            components quantised to 2^-20 / one thread per row: the direction of the sum, in fp64
 // As in mvsn_voxel.hip every atomic is an integer sum, so every output is a deterministic function of the inputs whatever
@@ -19,6 +19,7 @@
 // Where a fused multiply-add is wanted it is written as fmaf.
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
+#include "mvsn_geom.h"
 
 namespace mvsn {
 
@@ -27,14 +28,11 @@ constexpr int NM_PIX = 4;                               // consecutive pixels pe
 constexpr int NM_BLOCK_PIX = NM_THREADS * NM_PIX;       // pixels per workgroup
 constexpr float NM_QUANT = 1048576.0f;                  // 2^20: a unit component is 2^20 steps
 
-// entry `e` of the inverse of the top-left 3x3 of a row-major 4x4, in fp64 (the arithmetic of mvsn_fusion.hip's inv3_d)
+// entry `e` of mvsn_geom.h's inv3_d, one rounding per step (mvsn_fusion.hip's own inverse has the same formulas but
+// is compiled with contraction allowed: its bits can differ)
 __device__ inline double normals_inv3_entry(const float *K, int e) {
-  const double a = K[0], b = K[1], c = K[2], d = K[4], f0 = K[5], f = K[6], g = K[8], h = K[9], i = K[10];
-  const double A = f0 * i - f * h, B = -(d * i - f * g), C = d * h - f0 * g;
-  const double det = a * A + b * B + c * C, r = 1.0 / det;
-  const double o[9] = {A * r, -(b * i - c * h) * r, (b * f - c * f0) * r,
-                       B * r, (a * i - c * g) * r,  -(a * f - c * d) * r,
-                       C * r, -(a * h - b * g) * r, (a * f0 - b * d) * r};
+  double o[9];
+  inv3_d(K, o);
   double v = o[0];
 #pragma unroll
   for (int k = 1; k < 9; ++k) v = e == k ? o[k] : v;    // (a select chain: no runtime-indexed array)
@@ -194,22 +192,6 @@ __global__ __launch_bounds__(NM_THREADS) void depth_normals_kernel(const float *
   }
 }
 
-// out[i, :] = normals[view[i], :, pixel[i]]; an index outside the maps is never dereferenced (NaN)
-__global__ __launch_bounds__(256) void normals_gather_kernel(const float *__restrict__ normals,
-                                                             const int *__restrict__ view,
-                                                             const int *__restrict__ pixel, int V, long HW, long count,
-                                                             float *__restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const int v = view[i], q = pixel[i];
-  float a = NAN, b = NAN, c = NAN;
-  if (v >= 0 && v < V && q >= 0 && q < HW) {
-    const float *src = normals + (size_t)v * 3 * HW + q;
-    a = src[0], b = src[HW], c = src[2 * HW];
-  }
-  out[i * 3 + 0] = a, out[i * 3 + 1] = b, out[i * 3 + 2] = c;
-}
-
 __global__ __launch_bounds__(256) void voxel_normals_zero_kernel(unsigned long long *__restrict__ accum, long words) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < words) accum[i] = 0ull;
@@ -280,7 +262,7 @@ extern "C" int mvsn_normals_gather(const float *normals, const int *view, const 
                MVSN_E_BADARG, "mvsn_normals_gather: bad sizes");
   if (count == 0) return 0;                           // no points: nothing to launch
   MVSN_REQUIRE(normals && view && pixel && out, MVSN_E_BADARG, "mvsn_normals_gather: null pointer");
-  hipLaunchKernelGGL(mvsn::normals_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(mvsn::gather_kernel<3>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, normals, view, pixel, n_views, pixels_per_view, count, out);
   return mvsn::check_launch("mvsn_normals_gather");
 }

@@ -11,8 +11,9 @@
 //   Extraction, five launches and one 8-byte device copy, one host read (M, quads) between the second and the third:
 //   tsdf_classify_kernel    per voxel a: is the cell whose lowest corner is a active, does the grid edge (a, axis) emit a
 //                           quad; one code byte per voxel, and the vertices and quads of the workgroup counted
-//   voxel_scan_kernel       mvsn_voxel.hip's scan, launched from here over [vertex counts | quad counts]
-//   tsdf_rank_kernel        active cells ranked by wave ballots + mbcnt: the cell -> row int32 map (-1 = no vertex)
+//   geom_scan_kernel        mvsn_geom.h's scan, launched from here over [vertex counts | quad counts]
+//   tsdf_rank_kernel        active cells ranked inside the workgroup (block_rank of mvsn_geom.h): the cell -> row int32
+//                           map (-1 = no vertex)
 //   tsdf_faces_kernel       the quads ranked the same way in (voxel, axis) order; two triangles each
 //   tsdf_vertices_kernel    one thread per voxel: the vertex, normal, colour and cell index of an active cell
 // No atomics, no scratch, nothing waits on another workgroup; every loop is bounded and every output is a deterministic
@@ -22,7 +23,7 @@
 // is one fp32 operation.
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
-#include "mvsn_voxel.h"
+#include "mvsn_geom.h"
 
 namespace mvsn {
 
@@ -36,13 +37,8 @@ constexpr int TS_MAX_EXTENT = 1 << 24;                  // rows, cols and dims u
 
 // P = K T^-1 of one view, fp64, rounded once; K's bottom row is taken to be (0,0,1), so row 2 is T^-1's own
 __device__ inline void tsdf_camera(const float *K, const float *T, float *out) {
-  const double a = T[0], b = T[1], c = T[2], d = T[4], e = T[5], f = T[6], g = T[8], h = T[9], i = T[10];
-  const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-  const double det = a * A + b * B + c * C, r = 1.0 / det;
-  const double Ai[9] = {A * r, -(b * i - c * h) * r, (b * f - c * e) * r,
-                        B * r, (a * i - c * g) * r,  -(a * f - c * d) * r,
-                        C * r, -(a * h - b * g) * r, (a * e - b * d) * r};
-  double Ti[12];
+  double Ai[9], Ti[12];
+  inv3_d(T, Ai);
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
 #pragma unroll
@@ -179,16 +175,14 @@ struct TsdfLayout {
   long blocks;    // workgroups of the classify / rank / faces kernels
 };
 
-inline size_t ts_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline TsdfLayout tsdf_layout(long n) {
   TsdfLayout l;
   l.blocks = (n + TS_BLOCK_VOX - 1) / TS_BLOCK_VOX;
   l.code = 0;
-  l.map = ts_align(l.code + (size_t)n);
-  l.counts = ts_align(l.map + sizeof(int) * (size_t)n);
-  l.offsets = ts_align(l.counts + sizeof(int) * 2 * (size_t)l.blocks);
-  l.bytes = ts_align(l.offsets + sizeof(int64_t) * 2 * (size_t)l.blocks);
+  l.map = align256(l.code + (size_t)n);
+  l.counts = align256(l.map + sizeof(int) * (size_t)n);
+  l.offsets = align256(l.counts + sizeof(int) * 2 * (size_t)l.blocks);
+  l.bytes = align256(l.offsets + sizeof(int64_t) * 2 * (size_t)l.blocks);
   return l;
 }
 
@@ -275,29 +269,15 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_classify_kernel(
         (swave[threadIdx.x][0] + swave[threadIdx.x][1]) + (swave[threadIdx.x][2] + swave[threadIdx.x][3]);
 }
 
-__device__ __forceinline__ int tsdf_lanes_below(unsigned long long ballot) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0));
-}
-
 __global__ __launch_bounds__(TS_THREADS) void tsdf_rank_kernel(const uint8_t *__restrict__ code,
                                                                const int64_t *__restrict__ offsets, long n,
                                                                int *__restrict__ map) {
   __shared__ int swave[TS_THREADS / 64];
   const long a0 = ((long)blockIdx.x * TS_THREADS + threadIdx.x) * TS_VOX;
   bool act[TS_VOX];
-  int below = 0, wave_total = 0;
 #pragma unroll
-  for (int q = 0; q < TS_VOX; ++q) {
-    act[q] = a0 + q < n && (code[min(a0 + q, n - 1)] & 1) != 0;
-    const unsigned long long ballot = __ballot(act[q]);
-    below += tsdf_lanes_below(ballot);
-    wave_total += __popcll(ballot);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) swave[wave] = wave_total;
-  __syncthreads();
-  int64_t idx = offsets[blockIdx.x] + below;
-  for (int w = 0; w < wave; ++w) idx += swave[w];
+  for (int q = 0; q < TS_VOX; ++q) act[q] = a0 + q < n && (code[min(a0 + q, n - 1)] & 1) != 0;
+  int64_t idx = offsets[blockIdx.x] + block_rank(act, swave);
 #pragma unroll
   for (int q = 0; q < TS_VOX; ++q) {
     if (a0 + q >= n) break;
@@ -315,23 +295,15 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_faces_kernel(
   __shared__ int swave[TS_THREADS / 64];
   const long a0 = ((long)blockIdx.x * TS_THREADS + threadIdx.x) * TS_VOX;
   int cd[TS_VOX];
-  int below = 0, wave_total = 0;
+  bool quad[TS_VOX * 3];                                            // in (voxel, axis) order
 #pragma unroll
   for (int q = 0; q < TS_VOX; ++q) {
     cd[q] = a0 + q < n ? code[min(a0 + q, n - 1)] >> 1 : 0;
 #pragma unroll
-    for (int axis = 0; axis < 3; ++axis) {
-      const unsigned long long ballot = __ballot((cd[q] >> axis) & 1);
-      below += tsdf_lanes_below(ballot);
-      wave_total += __popcll(ballot);
-    }
+    for (int axis = 0; axis < 3; ++axis) quad[q * 3 + axis] = (cd[q] >> axis) & 1;
   }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) swave[wave] = wave_total;
-  __syncthreads();
   // the quad counts follow the vertex counts in the scanned array: their prefix starts at the vertex total
-  int64_t idx = offsets[blocks + blockIdx.x] - offsets[blocks] + below;
-  for (int w = 0; w < wave; ++w) idx += swave[w];
+  int64_t idx = offsets[blocks + blockIdx.x] - offsets[blocks] + block_rank(quad, swave);
 #pragma unroll
   for (int q = 0; q < TS_VOX; ++q) {
     if (cd[q] == 0) continue;
@@ -511,8 +483,8 @@ extern "C" int mvsn_tsdf_classify(const float *sdf_sum, const float *weight, int
                      (uint8_t *)(ws + l.code), counts, l.blocks);
   if (int e = check_launch("mvsn_tsdf_classify: classify")) return e;
   // one scan over [vertex counts | quad counts]: result[1] = M + quads, and M = the prefix at the first quad count
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, (const int *)counts, 2 * l.blocks, offsets,
-                     (unsigned long long *)result + 1);
+  hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(GEOM_SCAN_THREADS), 0, st, (const int *)counts, 2 * l.blocks, offsets,
+                     result + 1);
   if (int e = check_launch("mvsn_tsdf_classify: scan")) return e;
   const hipError_t e = hipMemcpyAsync(result, offsets + l.blocks, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
   MVSN_REQUIRE(e == hipSuccess, (int)e, "mvsn_tsdf_classify: copy of the vertex total: %s", hipGetErrorString(e));

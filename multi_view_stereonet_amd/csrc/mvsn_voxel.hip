@@ -9,9 +9,10 @@
 //                            with the point's; the point's slot goes to the workspace (-1 = dropped)
 //   voxel_count_kernel       VX_PTS consecutive points per thread: a point is the first of its voxel when it is its
 //                            slot's representative; one count per workgroup
-//   voxel_scan_kernel        one workgroup: exclusive prefix of those counts in a fixed order, and the total M
-//   voxel_rank_kernel        the count kernel's blocking again: first points ranked inside the workgroup by wave ballots
-//                            + mbcnt and a cross-wave LDS prefix; they write their slot's output row, first[row], and the
+//   geom_scan_kernel         one workgroup: exclusive prefix of those counts in a fixed order, and the total M (the scan
+//                            of mvsn_geom.h, defined here; the fusion, the cloud index and the TSDF launch it too)
+//   voxel_rank_kernel        the count kernel's blocking again: first points ranked inside the workgroup (block_rank of
+//                            mvsn_geom.h); they write their slot's output row, first[row], and the
 //                            row's accumulators (zeros and the voxel's key)
 //   voxel_accumulate_kernel  one thread per point: inverse[i] = row of its slot, integer atomicAdd of the 16-bit
 //                            in-cell fractions, the colours and 1 into the row's accumulators
@@ -25,6 +26,7 @@
 // index, sums are exact).  No float atomics, no sort.  Every loop is bounded: a probe sequence visits at most every slot
 // once and then gives up with a status bit; nothing waits on another thread.
 #include "mvsn_common.h"
+#include "mvsn_geom.h"
 #include "mvsn_voxel.h"
 
 namespace mvsn {
@@ -34,7 +36,6 @@ constexpr int VX_PTS = 4;                               // consecutive points pe
 constexpr int VX_BLOCK_PTS = VX_THREADS * VX_PTS;       // points per workgroup there
 constexpr int VX_INIT_SLOTS = 4;                        // table slots per thread of the init kernel
 constexpr size_t VX_MIN_SLOTS = VX_THREADS * VX_INIT_SLOTS;
-constexpr size_t VX_MAX_SLOTS = (size_t)1 << 31;        // a slot index is an int32
 constexpr int VX_ROW_WORDS = 8;                         // accumulator row: sum qx qy qz, sum r g b, count, key
 
 // byte offsets of the workspace sections (each 256-byte aligned)
@@ -44,20 +45,17 @@ struct VoxelLayout {
   long blocks;    // workgroups of the count / rank kernels
 };
 
-inline size_t vx_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline VoxelLayout voxel_layout(long n) {
   VoxelLayout l;
-  l.slots = VX_MIN_SLOTS;
-  while (l.slots < 2 * (size_t)n && l.slots < VX_MAX_SLOTS) l.slots <<= 1;
+  l.slots = hash_table_slots(n, VX_MIN_SLOTS);
   l.blocks = (n + VX_BLOCK_PTS - 1) / VX_BLOCK_PTS;
   l.keys = 0;
-  l.rep = vx_align(l.keys + sizeof(unsigned long long) * l.slots);
-  l.row = vx_align(l.rep + sizeof(int) * l.slots);
-  l.slot = vx_align(l.row + sizeof(int) * l.slots);
-  l.counts = vx_align(l.slot + sizeof(int) * (size_t)n);
-  l.offsets = vx_align(l.counts + sizeof(int) * (size_t)l.blocks);
-  l.bytes = vx_align(l.offsets + sizeof(int64_t) * (size_t)l.blocks);
+  l.rep = align256(l.keys + sizeof(unsigned long long) * l.slots);
+  l.row = align256(l.rep + sizeof(int) * l.slots);
+  l.slot = align256(l.row + sizeof(int) * l.slots);
+  l.counts = align256(l.slot + sizeof(int) * (size_t)n);
+  l.offsets = align256(l.counts + sizeof(int) * (size_t)l.blocks);
+  l.bytes = align256(l.offsets + sizeof(int64_t) * (size_t)l.blocks);
   return l;
 }
 
@@ -87,19 +85,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_assign_kernel(const float *_
   const int state = voxel_cell(points + (size_t)i * 3, inv, o, c, q);
   int found = -1;
   if (state == VX_KEPT) {
-    const unsigned long long key = voxel_key(c);
-    const size_t mask = slots - 1;
-    size_t h = (size_t)voxel_hash(key) & mask;
-    for (size_t probe = 0; probe < slots; ++probe) {        // bounded: every slot at most once
-      // a key never changes once it is set, so a plain look first saves the compare-and-swap on every occupied slot
-      unsigned long long seen = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (seen == VX_EMPTY) seen = atomicCAS(keys + h, VX_EMPTY, key);
-      if (seen == VX_EMPTY || seen == key) {
-        found = (int)h;
-        break;
-      }
-      h = (h + 1) & mask;
-    }
+    found = hash_insert(keys, slots, voxel_key(c));
     if (found >= 0)
       atomicMin(rep + found, (int)i);
     else
@@ -135,19 +121,16 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_count_kernel(const int *__re
   int mine = 0;
 #pragma unroll
   for (int k = 0; k < VX_PTS; ++k) mine += first[k];
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = (swave[0] + swave[1]) + (swave[2] + swave[3]);
+  mine = block_sum_256(mine, swave);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = mine;
 }
 
-// exclusive prefix of n per-workgroup counts, in index order, and their total (the fusion's scan, restated here so
-// that the fusion's device code stays as it is)
-__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(const int *__restrict__ counts, long n,
-                                                                     int64_t *__restrict__ offsets,
-                                                                     unsigned long long *__restrict__ result) {
-  __shared__ int64_t swave[VX_SCAN_THREADS / 64];
-  const long per = (n + VX_SCAN_THREADS - 1) / VX_SCAN_THREADS;
+// exclusive prefix of n per-workgroup counts, in index order, and their total (declared in mvsn_geom.h)
+__global__ __launch_bounds__(GEOM_SCAN_THREADS) void geom_scan_kernel(const int *__restrict__ counts, long n,
+                                                                      int64_t *__restrict__ offsets,
+                                                                      int64_t *__restrict__ total) {
+  __shared__ int64_t swave[GEOM_SCAN_THREADS / 64];
+  const long per = (n + GEOM_SCAN_THREADS - 1) / GEOM_SCAN_THREADS;
   const long lo = min((long)threadIdx.x * per, n), hi = min(lo + per, n);
   int64_t own = 0;
   for (long i = lo; i < hi; ++i) own += counts[i];
@@ -166,7 +149,7 @@ __global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(const int *
     offsets[i] = run;
     run += counts[i];
   }
-  if (threadIdx.x == VX_SCAN_THREADS - 1) result[0] = (unsigned long long)run;
+  if (threadIdx.x == GEOM_SCAN_THREADS - 1 && total) *total = run;
 }
 
 __global__ __launch_bounds__(VX_THREADS) void voxel_rank_kernel(const int *__restrict__ slot,
@@ -181,20 +164,8 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_rank_kernel(const int *__res
   int s[VX_PTS];
   bool first[VX_PTS];
   voxel_firsts(slot, rep, i0, n, s, first);
-  // rank among the workgroup's first points: lanes below this one (one ballot per point slot, mbcnt), then the points
-  // of this lane before each one, then the waves below this one
-  int below = 0, wave_total = 0;
-#pragma unroll
-  for (int k = 0; k < VX_PTS; ++k) {
-    const unsigned long long ballot = __ballot(first[k]);
-    below += __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0));
-    wave_total += __popcll(ballot);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) swave[wave] = wave_total;
-  __syncthreads();
-  int64_t idx = offsets[blockIdx.x] + below;
-  for (int w = 0; w < wave; ++w) idx += swave[w];
+  // rank among the workgroup's first points, then the points of this thread before each one
+  int64_t idx = offsets[blockIdx.x] + block_rank(first, swave);
 #pragma unroll
   for (int k = 0; k < VX_PTS; ++k) {
     if (!first[k]) continue;
@@ -308,7 +279,8 @@ extern "C" int mvsn_voxel_assign(const float *points, long n, float voxel_size, 
   if (int e = check_launch("mvsn_voxel_assign: assign")) return e;
   hipLaunchKernelGGL(voxel_count_kernel, dim3((unsigned)l.blocks), dim3(VX_THREADS), 0, st, slot, rep, n, counts);
   if (int e = check_launch("mvsn_voxel_assign: count")) return e;
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, counts, l.blocks, offsets, res);
+  hipLaunchKernelGGL(geom_scan_kernel, dim3(1), dim3(GEOM_SCAN_THREADS), 0, st, (const int *)counts, l.blocks, offsets,
+                     result);
   return check_launch("mvsn_voxel_assign: scan");
 }
 

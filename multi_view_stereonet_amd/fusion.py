@@ -56,6 +56,61 @@ def _check_frames(name, t, V, H, W, channels, dtypes, device):
         raise ValueError(f"{name} is on {t.device}, depth on {device}")
 
 
+def _check_views(depth, K, T_cam_in_world, *, limits=None, T_optional=False, floating=False):
+    """ValueError unless ``depth`` is a (V,1,H,W) float32 tensor of at least one view of at least one pixel and ``K`` and
+    ``T_cam_in_world`` (which may be None with ``T_optional``) are (V,4,4) tensors on its device (floating-point ones
+    with ``floating``).  ``limits(V, H, W, dev)``: the caller's own size and device limits, checked after the depth and
+    before the matrices.  Returns (V, H, W, dev)."""
+    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError("depth must be a (V,1,H,W) tensor")
+    V, _, H, W = depth.shape
+    dev = depth.device
+    if V < 1 or H * W < 1:
+        raise ValueError("depth must hold at least one view of at least one pixel")
+    if depth.dtype != torch.float32:
+        raise ValueError(f"depth must be float32, got {depth.dtype}")
+    if limits is not None:
+        limits(V, H, W, dev)
+    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+        if m is None and T_optional and name != "K":
+            continue
+        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
+            raise ValueError(f"{name} must be a ({V},4,4) tensor")
+        if floating and not m.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {m.dtype}")
+        if m.device != dev:
+            raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+    return V, H, W, dev
+
+
+def _positive_f32(value, name, inverse=False, square=False):
+    """(v, 1/v, v*v) with v = np.float32(value), each formed once in fp32 on the host, None for what was not asked for;
+    ValueError unless every one of them is finite and > 0."""
+    with np.errstate(all="ignore"):
+        try:
+            v = np.float32(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a positive finite number, got {value!r}") from None
+        inv = np.float32(1) / v if inverse else None
+        sq = v * v if square else None
+    if not all(np.isfinite(x) and x > 0 for x in (v, inv, sq) if x is not None):
+        how = " in float32" if not inverse else " (in float32, with a finite inverse)" if not square else \
+            " (in float32, with a finite inverse and a finite non-zero square)"
+        raise ValueError(f"{name} must be finite and > 0{how}, got {value!r}")
+    return v, inv, sq
+
+
+def _origin_f32(origin):
+    """``origin`` as three np.float32; ValueError unless they are three finite numbers."""
+    try:
+        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}") from None
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+    return o
+
+
 def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, neighbours, *,
                    images: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
                    ref_views: Optional[Sequence[int]] = None, max_reproj_px: float = 1.0,
@@ -73,19 +128,7 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
     ``confidence`` (V,1,H,W) fp32 with ``min_confidence``: the call is this function with ``valid`` and-ed with
     ``confidence >= min_confidence`` (formed on the device; a pixel at the threshold is kept, a NaN confidence is not).
     The gate applies, as ``valid`` does, to the candidate pixel and to every neighbour tap."""
-    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
-        raise ValueError("depth must be a (V,1,H,W) tensor")
-    V, _, H, W = depth.shape
-    dev = depth.device
-    if V < 1 or H * W < 1:
-        raise ValueError("depth must hold at least one view of at least one pixel")
-    if depth.dtype != torch.float32:
-        raise ValueError(f"depth must be float32, got {depth.dtype}")
-    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
-        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
-            raise ValueError(f"{name} must be a ({V},4,4) tensor")
-        if m.device != dev:
-            raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+    V, H, W, dev = _check_views(depth, K, T_cam_in_world)
     if images is not None:
         _check_frames("images", images, V, H, W, 3, (torch.float32,), dev)
     if valid is not None:
@@ -160,35 +203,46 @@ def point_values(result: FusionResult, maps: torch.Tensor, ref_views: Optional[S
     """The value of ``maps`` (V,1,H,W) fp32 -- a confidence pyramid's level 0, say -- at every point of ``result``:
     (M,) fp32, ``maps[result.view[i]]`` at row-major pixel ``result.pixel[i]``.  ``ref_views``: the fusion's, when
     ``maps`` holds only those views, in that order (``maps`` is then (R,1,H,W))."""
-    if not torch.is_tensor(maps) or maps.dim() != 4 or maps.shape[1] != 1:
-        raise ValueError("maps must be a (V,1,H,W) tensor")
+    return _gather_at_points(result, maps, 1, ref_views, "maps")
+
+
+def _gather_at_points(result, maps, channels, ref_views, name):
+    """``point_values`` (channels 1, (M,)) and ``point_normals`` (channels 3, (M,3)): the checks, the table from a view
+    to its row of ``maps`` when ``ref_views`` is given, and the launch.  An empty cloud returns before point_normals asks
+    for a HIP device and after point_values does."""
+    func, entry, empty_first = {1: ("point_values", "mvsn_fusion_gather", False),
+                                3: ("point_normals", "mvsn_normals_gather", True)}[channels]
+    if not torch.is_tensor(maps) or maps.dim() != 4 or maps.shape[1] != channels:
+        raise ValueError(f"{name} must be a (V,{channels},H,W) tensor")
     if maps.dtype != torch.float32:
-        raise ValueError(f"maps must be float32, got {maps.dtype}")
+        raise ValueError(f"{name} must be float32, got {maps.dtype}")
     if tuple(maps.shape[-2:]) != tuple(result.depth.shape[-2:]):
-        raise ValueError(f"maps are {tuple(maps.shape[-2:])}, the fusion ran on {tuple(result.depth.shape[-2:])}")
+        raise ValueError(f"{name} are {tuple(maps.shape[-2:])}, the fusion ran on {tuple(result.depth.shape[-2:])}")
     if maps.device != result.view.device:
-        raise ValueError(f"maps are on {maps.device}, the points on {result.view.device}")
+        raise ValueError(f"{name} are on {maps.device}, the points on {result.view.device}")
     view = result.view
     if ref_views is not None:
         refs = _host_index_array(ref_views, "ref_views").reshape(-1)
         if refs.shape[0] != maps.shape[0]:
-            raise ValueError(f"maps hold {maps.shape[0]} views for {refs.shape[0]} reference views")
+            raise ValueError(f"{name} hold {maps.shape[0]} views for {refs.shape[0]} reference views")
         row = np.full(int(refs.max()) + 1 if refs.size else 1, -1, dtype=np.int32)
         row[refs] = np.arange(refs.shape[0], dtype=np.int32)
         lut = torch.from_numpy(row).to(view.device)
         view = lut[view.long().clamp(0, lut.shape[0] - 1)].contiguous()
-    if not maps.is_cuda:
-        raise RuntimeError("point_values runs on HIP devices only (there is no CPU implementation)")
     M = int(view.shape[0])
-    out = torch.empty((M,), dtype=torch.float32, device=maps.device)
+    shape = (M,) if channels == 1 else (M, channels)
+    if M == 0 and empty_first:         # no points: nothing to launch
+        return torch.empty(shape, dtype=torch.float32, device=maps.device)
+    if not maps.is_cuda:
+        raise RuntimeError(f"{func} runs on HIP devices only (there is no CPU implementation)")
+    out = torch.empty(shape, dtype=torch.float32, device=maps.device)
     if M == 0:
         return out
     lib = _native.load()
     with torch.cuda.device(maps.device):
-        _native.check(lib.mvsn_fusion_gather(_native.ptr(maps.detach().contiguous()), _native.ptr(view.contiguous()),
-                                             _native.ptr(result.pixel.contiguous()), maps.shape[0],
-                                             maps.shape[2] * maps.shape[3], M, _native.ptr(out), _native.stream()),
-                      "mvsn_fusion_gather")
+        _native.check(getattr(lib, entry)(_native.ptr(maps.detach().contiguous()), _native.ptr(view.contiguous()),
+                                          _native.ptr(result.pixel.contiguous()), maps.shape[0],
+                                          maps.shape[2] * maps.shape[3], M, _native.ptr(out), _native.stream()), entry)
     return out
 
 
@@ -203,23 +257,10 @@ def depth_normals(depth: torch.Tensor, K: torch.Tensor, *, valid: Optional[torch
     differenced across.  Each tangent is the central difference where both neighbours count and the one-sided one where
     one does; the normal is (0,0,0) where the pixel is not usable or a tangent has no neighbour (DESIGN.md section 13
     states every step).  Everything is validated here, before the launch; no host synchronisation."""
-    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
-        raise ValueError("depth must be a (V,1,H,W) tensor")
-    V, _, H, W = depth.shape
-    dev = depth.device
-    if V < 1 or H * W < 1:
-        raise ValueError("depth must hold at least one view of at least one pixel")
-    if depth.dtype != torch.float32:
-        raise ValueError(f"depth must be float32, got {depth.dtype}")
-    if V > 65535 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"at most 65535 views of 2^31 - 1 pixels, got {V} of {H * W}")
-    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
-        if m is None and name != "K":
-            continue
-        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
-            raise ValueError(f"{name} must be a ({V},4,4) tensor")
-        if m.device != dev:
-            raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+    def limits(V, H, W, dev):
+        if V > 65535 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"at most 65535 views of 2^31 - 1 pixels, got {V} of {H * W}")
+    V, H, W, dev = _check_views(depth, K, T_cam_in_world, limits=limits, T_optional=True)
     if valid is not None:
         _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
     try:
@@ -248,36 +289,7 @@ def point_normals(result: FusionResult, normals: torch.Tensor, ref_views: Option
     """The normal maps ``normals`` (V,3,H,W) fp32 of ``depth_normals`` at every point of ``result``: (M,3) fp32,
     ``normals[result.view[i], :, pixel]`` at row-major pixel ``result.pixel[i]`` (``point_values`` for a three-channel
     map).  ``ref_views``: the fusion's, when ``normals`` holds only those views, in that order (then (R,3,H,W))."""
-    if not torch.is_tensor(normals) or normals.dim() != 4 or normals.shape[1] != 3:
-        raise ValueError("normals must be a (V,3,H,W) tensor")
-    if normals.dtype != torch.float32:
-        raise ValueError(f"normals must be float32, got {normals.dtype}")
-    if tuple(normals.shape[-2:]) != tuple(result.depth.shape[-2:]):
-        raise ValueError(f"normals are {tuple(normals.shape[-2:])}, the fusion ran on {tuple(result.depth.shape[-2:])}")
-    if normals.device != result.view.device:
-        raise ValueError(f"normals are on {normals.device}, the points on {result.view.device}")
-    view = result.view
-    if ref_views is not None:
-        refs = _host_index_array(ref_views, "ref_views").reshape(-1)
-        if refs.shape[0] != normals.shape[0]:
-            raise ValueError(f"normals hold {normals.shape[0]} views for {refs.shape[0]} reference views")
-        row = np.full(int(refs.max()) + 1 if refs.size else 1, -1, dtype=np.int32)
-        row[refs] = np.arange(refs.shape[0], dtype=np.int32)
-        lut = torch.from_numpy(row).to(view.device)
-        view = lut[view.long().clamp(0, lut.shape[0] - 1)].contiguous()
-    M = int(view.shape[0])
-    if M == 0:                         # no points: nothing to launch
-        return torch.empty((0, 3), dtype=torch.float32, device=normals.device)
-    if not normals.is_cuda:
-        raise RuntimeError("point_normals runs on HIP devices only (there is no CPU implementation)")
-    out = torch.empty((M, 3), dtype=torch.float32, device=normals.device)
-    lib = _native.load()
-    with torch.cuda.device(normals.device):
-        _native.check(lib.mvsn_normals_gather(_native.ptr(normals.detach().contiguous()), _native.ptr(view.contiguous()),
-                                              _native.ptr(result.pixel.contiguous()), normals.shape[0],
-                                              normals.shape[2] * normals.shape[3], M, _native.ptr(out),
-                                              _native.stream()), "mvsn_normals_gather")
-    return out
+    return _gather_at_points(result, normals, 3, ref_views, "normals")
 
 
 class VoxelCloud(NamedTuple):
@@ -319,20 +331,8 @@ def voxel_merge(points: torch.Tensor, voxel_size: float, *, colors: Optional[tor
             raise ValueError(f"colors must be uint8, got {colors.dtype}")
         if colors.device != dev:
             raise ValueError(f"colors are on {colors.device}, points on {dev}")
-    with np.errstate(all="ignore"):
-        try:
-            v = np.float32(voxel_size)
-        except (TypeError, ValueError):
-            raise ValueError(f"voxel_size must be a positive finite number, got {voxel_size!r}") from None
-        inv = np.float32(1) / v
-    if not (np.isfinite(v) and v > 0 and np.isfinite(inv) and inv > 0):
-        raise ValueError(f"voxel_size must be finite and > 0 (in float32, with a finite inverse), got {voxel_size!r}")
-    try:
-        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
-    except (TypeError, ValueError):
-        raise ValueError(f"origin must be three finite numbers, got {origin!r}") from None
-    if o.shape != (3,) or not np.isfinite(o).all():
-        raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+    v, inv, _ = _positive_f32(voxel_size, "voxel_size", inverse=True)
+    o = _origin_f32(origin)
 
     def result(m):
         return VoxelCloud(torch.empty((m, 3), dtype=torch.float32, device=dev),
@@ -426,16 +426,7 @@ def check_cloud(name, t):
 def cloud_radius_scalars(max_dist, name="max_dist"):
     """(h, 1/h, h*h) as np.float32, each formed once in fp32 on the host; ValueError unless all three are finite and
     > 0."""
-    with np.errstate(all="ignore"):
-        try:
-            h = np.float32(max_dist)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be a positive finite number, got {max_dist!r}") from None
-        inv, r2 = np.float32(1) / h, h * h
-    if not (np.isfinite(h) and h > 0 and np.isfinite(inv) and inv > 0 and np.isfinite(r2) and r2 > 0):
-        raise ValueError(f"{name} must be finite and > 0 (in float32, with a finite inverse and a finite non-zero "
-                         f"square), got {max_dist!r}")
-    return h, inv, r2
+    return _positive_f32(max_dist, name, inverse=True, square=True)
 
 
 def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) -> CloudNeighbours:

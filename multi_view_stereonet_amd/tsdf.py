@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .fusion import _check_frames
+from .fusion import _check_frames, _check_views, _origin_f32, _positive_f32
 
 MAX_VOXELS = 2 ** 31 - 1
 MAX_EXTENT = 2 ** 24                 # voxels along an axis, rows and columns of a map: every index is an exact float32
@@ -29,29 +29,6 @@ class TSDFMesh(NamedTuple):
     colors: Optional[torch.Tensor]   # (M,3) uint8, or None for a volume without colour
     faces: torch.Tensor              # (F,3) int64 rows of `vertices`, counter-clockwise seen from the outside
     cell: torch.Tensor               # (M,) int64: the cell's linear index (k * Ny + j) * Nx + i, ascending
-
-
-def _positive_f32(value, name):
-    """``value`` as np.float32, formed once on the host; ValueError unless it is finite and > 0 there."""
-    with np.errstate(all="ignore"):
-        try:
-            v = np.float32(value)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be a positive finite number, got {value!r}") from None
-    if not (np.isfinite(v) and v > 0):
-        raise ValueError(f"{name} must be finite and > 0 in float32, got {value!r}")
-    return v
-
-
-def _origin_f32(origin):
-    """``origin`` as three np.float32; ValueError unless they are three finite numbers."""
-    try:
-        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
-    except (TypeError, ValueError):
-        raise ValueError(f"origin must be three finite numbers, got {origin!r}") from None
-    if o.shape != (3,) or not np.isfinite(o).all():
-        raise ValueError(f"origin must be three finite numbers, got {origin!r}")
-    return o
 
 
 class TSDFVolume:
@@ -75,8 +52,8 @@ class TSDFVolume:
             raise ValueError(f"dims must be at most 2^24 each, got {d}")
         if d[0] * d[1] * d[2] > MAX_VOXELS:
             raise ValueError(f"at most 2^31 - 1 voxels, got {d[0]} x {d[1]} x {d[2]} = {d[0] * d[1] * d[2]}")
-        self.voxel_size = _positive_f32(voxel_size, "voxel_size")
-        self.trunc = _positive_f32(trunc, "trunc")
+        self.voxel_size = _positive_f32(voxel_size, "voxel_size")[0]
+        self.trunc = _positive_f32(trunc, "trunc")[0]
         o = _origin_f32(origin)
         self.dims, self.origin, self.device = d, o, torch.device(device)
         nx, ny, nz = d
@@ -108,25 +85,12 @@ class TSDFVolume:
         updates keeps its bits.  ``K`` and ``T_cam_in_world`` may be of any floating-point dtype: the kernel reads their
         float32 values (and forms the inverses from those in fp64).  Everything is validated here, before the launch; no
         host synchronisation."""
-        if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1:
-            raise ValueError("depth must be a (V,1,H,W) tensor")
-        V, _, H, W = depth.shape
-        dev = depth.device
-        if V < 1 or H * W < 1:
-            raise ValueError("depth must hold at least one view of at least one pixel")
-        if depth.dtype != torch.float32:
-            raise ValueError(f"depth must be float32, got {depth.dtype}")
-        if V > 65535 or H * W > 2 ** 31 - 1 or max(H, W) > MAX_EXTENT:
-            raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
-        if dev != self.device:
-            raise ValueError(f"depth is on {dev}, the volume on {self.device}")
-        for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
-            if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
-                raise ValueError(f"{name} must be a ({V},4,4) tensor")
-            if not m.is_floating_point():
-                raise ValueError(f"{name} must be a floating-point tensor, got {m.dtype}")
-            if m.device != dev:
-                raise ValueError(f"{name} is on {m.device}, depth on {dev}")
+        def limits(V, H, W, dev):
+            if V > 65535 or H * W > 2 ** 31 - 1 or max(H, W) > MAX_EXTENT:
+                raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
+            if dev != self.device:
+                raise ValueError(f"depth is on {dev}, the volume on {self.device}")
+        V, H, W, dev = _check_views(depth, K, T_cam_in_world, limits=limits, floating=True)
         if (images is not None) != (self.color_sum is not None):
             raise ValueError("images need a volume made with color=True, and such a volume needs images")
         if images is not None:
@@ -190,8 +154,8 @@ def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optiona
             raise ValueError(f"color_sum is on {color_sum.device}, sdf_sum on {dev}")
     if nx * ny * nz > MAX_VOXELS or max(nx, ny, nz) > MAX_EXTENT:
         raise ValueError(f"at most 2^31 - 1 voxels and 2^24 along an axis, got {nx} x {ny} x {nz}")
-    v = _positive_f32(voxel_size, "voxel_size")
-    mw = _positive_f32(min_weight, "min_weight")
+    v = _positive_f32(voxel_size, "voxel_size")[0]
+    mw = _positive_f32(min_weight, "min_weight")[0]
     o = _origin_f32(origin)
 
     def mesh(m, f):

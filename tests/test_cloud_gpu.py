@@ -156,6 +156,19 @@ def test_all_1027_targets_in_one_cell():
     assert ref["within"].max() > 500 and (ref["within"] == 0).any()
 
 
+def test_more_slot_block_counts_than_scan_threads():
+    # 2^19 + 1 targets: a table of 2^21 slots, 2048 population sums of 1024 slots each for the scan's 1024 threads (a run
+    # of 2 per thread); 2 targets per cell of h = 0.25 in a cube of 64^3 cells, 1027 queries in and around it
+    nt, nq = 2 ** 19 + 1, 1027
+    rng = np.random.default_rng(44)
+    t = rng.uniform(-8.0, 8.0, (nt, 3)).astype(np.float32)
+    q = rng.uniform(-8.2, 8.2, (nq, 3)).astype(np.float32)
+    q[:8] = t[[0, 1, nt - 1, nt // 2, 1024, 1025, 2 ** 19, 2 ** 18]]    # on top of a target: d2 = 0, that row or a duplicate
+    ref = _check(q, t, 0.25)
+    assert (ref["dist2"][:8] == 0).all() and ref["index"][0] == 0 and ref["index"][2] == nt - 1
+    assert ref["within"].mean() > 4 and (ref["within"] == 0).any()
+
+
 # ---- far from the origin: the widened range, the clip to the grid ----------------------------------------------------
 @pytest.mark.parametrize("axis", [0, 1, 2])
 def test_cluster_at_half_a_million_cells_and_at_the_grids_edge(axis):

@@ -109,6 +109,27 @@ def test_fusion_odd_size_padding_valid_mask_and_ref_subset():
     assert bare.colors is None and torch.equal(bare.points, got.points)
 
 
+def test_fusion_more_workgroup_counts_than_scan_threads():
+    # 88 references x ceil(96 * 128 / 1024) = 88 x 12 = 1056 kept-pixel counts for the scan's 1024 threads: every thread
+    # owns a run of ceil(1056 / 1024) = 2 counts and the last 496 threads own none.  Many views of the first test's
+    # size, not a few large ones: _compare's 1e-5 on the fused depth is a bound for images of this size (the fp32 error
+    # of a projected coordinate grows with the coordinate, and an interpolated depth moves by its slope times that:
+    # 3 views of 600 x 600 reach 1.8e-5 at the sphere's silhouette).  The cameras span the usual arc, so the neighbours
+    # are 17 and 34 views away: the angles of the first test's views.
+    V, H, W = 88, 96, 128
+    sc = synthetic.fusion_scene(V, H, W)
+    nb = np.array([[v + 17, v + 34] if v < V // 2 else [v - 17, v - 34] for v in range(V)])
+    ref = fuse_reference(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    got = fuse_depthmaps(sc["depth"].to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb,
+                         images=sc["images"].to(DEV))
+    assert got.depth.shape == (V, 1, H, W) and V * (-(-H * W // 1024)) == 1056
+    assert got.points.shape[0] == int((got.depth > 0).sum())
+    # (368 margin pixels of 1081344 in the restatement)
+    shared = _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(V), 1e-3)
+    print(f"1056 counts: {shared} shared points of {got.points.shape[0]}, {int(ref['margin'].sum())} margin pixels")
+    assert shared > 0.8 * V * H * W
+
+
 def test_fusion_is_deterministic():
     sc = synthetic.fusion_scene(6, 96, 128, device=DEV)
     nb = nearest_neighbours(6, 4)

@@ -285,6 +285,21 @@ def test_extraction_of_one_cell_and_of_a_long_row():
     assert got["cell"].shape == (0,) and got["faces"].shape == (0, 3)
 
 
+def test_extraction_with_more_workgroup_counts_than_scan_threads():
+    # 132 x 64 x 65 voxels: 537 workgroups, so 1074 counts [vertices | quads] for the scan's 1024 threads: every thread
+    # owns a run of 2 and the last 487 none, and the first quad count (whose prefix is M) is the second count of thread
+    # 268's run.  One slanted plane crosses the volume: few cells are active, most counts are zero.
+    nx, ny, nz = 132, 64, 65
+    assert 2 * -(-nx * ny * nz // 1024) == 1074
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    s = ((0.31 * i + 0.52 * j + 0.80 * k - 55.3) * 0.05).astype(np.float32)
+    w = np.ones(s.shape, np.float32)
+    w[20:30, 10:20, 40:60] = 0.0                                        # a hole in the sheet
+    ref = surface_nets_reference(s, w, None, 1.0, 0.05, (-3.3, -1.6, 2.0))
+    assert 5000 < ref["cell"].shape[0] < 30000 and ref["faces"].shape[0] > 10000
+    _compare_mesh(_device_extract((s, w, None), 1.0, 0.05, (-3.3, -1.6, 2.0)), ref, "132x64x65")
+
+
 def _cells_clear_of(borderline):
     """Per linear voxel index: True where none of the 8 corners of the cell with that lowest corner is borderline."""
     nz, ny, nx = borderline.shape

@@ -111,6 +111,18 @@ def test_many_voxels_uniform_random():
     _check(_merge(pts, 0.01, cols), ref)
 
 
+def test_more_workgroup_counts_than_scan_threads():
+    # 2^20 + 5 points: ceil(N / 1024) = 1025 first-point counts for the scan's 1024 threads, so every thread owns a run
+    # of 2 counts and the threads from 513 on own none; 80^3 cells for a million points: several hundred thousand voxels
+    n = 2 ** 20 + 5
+    rng = np.random.default_rng(8)
+    pts = rng.uniform(-2.0, 2.0, (n, 3)).astype(np.float32)
+    cols = rng.integers(0, 256, (n, 3)).astype(np.uint8)
+    ref = voxel_reference(pts, 0.05, colors=cols)
+    assert -(-n // 1024) > 1024 and 300000 < len(ref["first"]) < 512000
+    _check(_merge(pts, 0.05, cols), ref)
+
+
 def test_many_voxels_on_a_line_of_consecutive_cells():
     # clustered keys: 4096 consecutive cells along x (then along z: the key's low bits), one point each, shuffled
     rng = np.random.default_rng(4)
