@@ -755,6 +755,15 @@ int mvsn_debug_set_wino_rowphase(int mode);
  * own) or, with `carrying`, when none carries. */
 int mvsn_debug_wino_plan(const mvsn_conv_desc *desc, int carrying, int out[8]);
 
+/* Host only, no device call: the kernel form a direct fp32 layer (desc->precision = MVSN_CONV_FP32) runs on, as
+ * mvsn_conv_forward itself selects it for a call in `mode` (0 = plain input, 1 = LReLU(GN(in)) folded into the load,
+ * 2 = + residual / staged output) with 16-byte aligned tensors and no statistics asked for where that matters (the
+ * 3 -> 32 head).  out = { row of the table of forms, kind (0 = register-staged, 1 = LDS-DMA, 2 = the 5x5 stride-2
+ * head), pixel tiles per wave (NPT), staged elements per thread and channel (SE; LDS-DMA: pieces per channel, IPC),
+ * 16-byte staging (V4), cout tiles (CT), bytes of LDS, tiles per sample }.  Returns the number of rows in the table, or
+ * 0 when no direct form runs the layer. */
+int mvsn_debug_conv_plan(const mvsn_conv_desc *desc, int mode, int out[8]);
+
 /* Device self-test of the MFMA fragment mapping the conv kernels rely on (A = 16x4, B = 4x16
  * fp32, asymmetric operands); returns 0 when the on-device result matches the scalar product. */
 int mvsn_selftest_mfma(mvsn_stream_t stream);

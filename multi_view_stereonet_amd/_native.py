@@ -84,6 +84,7 @@ SIGNATURES = {
     "mvsn_debug_set_band_flags": (c_int, [c_int]),
     "mvsn_debug_set_wino_rowphase": (c_int, [c_int]),
     "mvsn_debug_wino_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int * 8)]),
+    "mvsn_debug_conv_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int * 8)]),
     "mvsn_copy_many": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mvsn_conv_to1_block_records": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p]),
     "mvsn_groupnorm_lrelu_apply_records": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 6 + [c_int, c_long, c_void_p, c_void_p]),

@@ -6,6 +6,8 @@
 #include <string.h>
 
 #include <mutex>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/mvsn_hip.h"
 
@@ -44,6 +46,15 @@ inline int ensure_lds(LdsOptIn &state, const void *kernel, size_t lds_bytes, con
   }
   if (cached) state.opted[dev] = lds_bytes;
   return 0;
+}
+
+// f(integral_constant<I>) for the row I == row of a constexpr table of kernel forms: the fold that turns the run-time
+// row into a compile-time one, so a launch function instantiates one kernel per row (each with its own LdsOptIn)
+template <class F, size_t... I>
+inline int with_form_row(int row, std::index_sequence<I...>, F &&f) {
+  int rc = MVSN_E_BADARG;
+  (void)((row == (int)I && ((rc = f(std::integral_constant<int, (int)I>{})), true)) || ...);
+  return rc;
 }
 
 // compute units of the current device (per device, cached)

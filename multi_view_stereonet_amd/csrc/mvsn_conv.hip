@@ -21,19 +21,20 @@ constexpr int CV_THREADS = 256;
 constexpr int CV_WAVES = 4;
 constexpr int CV_TX = 32;   // output columns per tile
 constexpr int CV_CK = 4;    // input channels per staged chunk = one MFMA k-step
-constexpr float CV_EPS = 1e-5f;
 
-// Division by a launch-invariant divisor: q = (mulhi(n, mul) + n) >> shift, exact for 0 <= n < 2^31.
-// The kernels' prologues decompose tile and staging indices with ~30 divisions; as generic integer
-// divisions (~40 instructions each, issued next to three MFMA-bound waves per SIMD) they made the
-// prologue a quarter of a workgroup's lifetime.
 #ifndef MVSN_TALL_TILE_MAX_DIL
 #define MVSN_TALL_TILE_MAX_DIL 8   // 2-D 3x3 layers up to this dilation use 16-row tiles (measured: 2/4/8 within 1.5 %)
 #endif
 #ifndef MVSN_DMA_MAX_DIL
 #define MVSN_DMA_MAX_DIL 8         // 2-D 3x3 layers up to this dilation run on the LDS-DMA kernel (cols % 4 == 0)
 #endif
+constexpr int HD_TY = 8, HD_TX = 32, HD_ROWS = 2 * HD_TY + 3, HD_XS = 2 * HD_TX + 8;   // the 3 -> 32 head: 19 rows of 72 floats
+constexpr int HD_CST = HD_ROWS * HD_XS + 4;                                           // ... channel stride (floats)
 
+// Division by a launch-invariant divisor: q = (mulhi(n, mul) + n) >> shift, exact for 0 <= n < 2^31.
+// The kernels' prologues decompose tile and staging indices with ~30 divisions; as generic integer
+// divisions (~40 instructions each, issued next to three MFMA-bound waves per SIMD) they made the
+// prologue a quarter of a workgroup's lifetime.
 struct FastDiv {
   unsigned mul, shift;
 };
@@ -47,7 +48,7 @@ __device__ __forceinline__ int fdiv(int n, FastDiv f) {
   return (int)((__umulhi((unsigned)n, f.mul) + (unsigned)n) >> f.shift);
 }
 
-struct ConvGeom {
+struct ConvGeom {   // (the kernels' argument block: its layout is part of the compiled kernels)
   FastDiv fd_hx, fd_hy, fd_ntx, fd_nty, fd_ty, fd_gq;
   int n, cin, cout, D, H, W, Do, Ho, Wo;
   int kd, kh, kw, stride, dil, pd, ph, pw;
@@ -60,16 +61,60 @@ struct ConvGeom {
   int ntz, nty, ntx, tiles;
   int ntaps, nchunks;
   int wfloats_chunk;    // ntaps * 2 cout-tiles * 64
-  size_t lds_bytes;
+  size_t spare0;        // (the LDS plans lived here and in spare1; they are ConvForm's now)
   int se;               // staged elements per thread per channel
   // LDS-DMA kernel: rows are staged as whole 16-byte pieces from the aligned column x0 - dpa (dpa = halo
   // rounded up to 4: 40 floats per row for a halo <= 4, 48 for 8), so one DMA instruction moves 1 KB
-  int dma_ok;           // cols % 4 == 0, stride 1, halo <= 8
+  int dma;              // the layer runs on the LDS-DMA kernel: decided once, in make_geom
   int dpa, dq;          // aligned halo, 16-byte pieces per row
-  int dXS, dCST, dipc;  // row stride (4 * dq), channel stride, piece instructions per channel
-  int dma_stage_floats; // floats per pipeline stage without the residual tile
+  int dXS, dCST, dipc, spare1;  // row stride (4 * dq), channel stride, piece instructions per channel
   FastDiv fd_dq;
 };
+
+constexpr int cv_dma_dq(int pw) { return (CV_TX + 2 * ((pw + 3) / 4 * 4)) / 4; }                // LDS-DMA: 16-byte pieces per tile row
+constexpr int cv_dma_ipc(int rows, int pw) { return (rows * cv_dma_dq(pw) + 63) / 64; }         // ... piece instructions per channel
+
+// The kernel forms: one row per instantiated family of conv_mfma_kernel (register-staged), conv_dma_kernel (LDS-DMA) and the 3 -> 32 head, with
+// the kernels' compile-time parameters; CT and MODE are the second axis (conv_ct, conv_mode).  conv_select maps a layer to its row, mvsn_conv_forward
+// instantiates the kernels from the rows.  A row is also the LDS plan: the kernels carve their LDS with its figures, the launch asks for lds_bytes().
+enum { CV_STAGED = 0, CV_DMA = 1, CV_HEAD = 2 };
+struct ConvForm {
+  int kind, npt, kd, kh, stride, se;   // (KW = KH); se: SE, an upper bound on ConvGeom::se -- LDS-DMA: IPC, on ConvGeom::dipc
+  bool v4;
+  constexpr bool dma() const { return kind == CV_DMA; }
+  constexpr int wfl() const { return kd * kh * kh * 128; }                      // weight floats per chunk
+  constexpr int wslot() const { return (wfl() + 255) / 256 * 256; }             // ... in whole DMA runs
+  constexpr int ntiles(int mode) const { return dma() && mode == 2 ? 2 : 1; }  // 4-channel tiles per stage: + the residual's
+  constexpr size_t lds_bytes(const ConvGeom &g, int mode) const {   // one stage (LDS-DMA: two) of [tile(s)][weights], [scale, shift], spare
+    return sizeof(float) * (kind == CV_HEAD ? 2 * 3 * HD_CST   // (its static ring)
+                            : dma() ? 2 * (CV_CK * g.dCST * ntiles(mode) + wslot()) + 64 + 16 : CV_CK * g.CST + wfl() + 64 + 64);
+  }
+  constexpr bool same(const ConvForm &o) const { return kind == o.kind && npt == o.npt && kd == o.kd && kh == o.kh && stride == o.stride && se == o.se && v4 == o.v4; }
+};
+constexpr ConvForm CV_FORMS[] = {   // {kind, npt, kd, kh, stride, se | ipc, v4}
+    {CV_DMA, 8, 1, 3, 1, 4, false},      // 2-D 3x3 stride 1, cols % 4 == 0, dilation <= MVSN_DMA_MAX_DIL: 16-row tiles
+    {CV_DMA, 8, 1, 3, 1, 6, false},      // ... more than 4 pieces per channel (dilation >= 4)
+    {CV_DMA, 4, 1, 3, 1, 4, false},      // ... images of up to 8 rows: 8-row tiles
+    {CV_DMA, 4, 1, 3, 1, 6, false},
+    {CV_STAGED, 8, 1, 3, 1, 3, false},   // 2-D 3x3 stride 1 otherwise: 16-row tiles (dilation <= 2)
+    {CV_STAGED, 4, 1, 3, 1, 3, false},   // ... 8-row tiles
+    {CV_STAGED, 4, 1, 3, 1, 6, false},   // ... with more than 3 x 256 staged elements (dilation >= 5)
+    {CV_STAGED, 8, 3, 3, 1, 2, true},    // 3-D 3x3x3, 2 x 8 x 32 tiles, as 16-byte groups (cols % 4 == 0): 4*10*10 = 400 groups
+    {CV_STAGED, 8, 3, 3, 1, 6, false},   // ... element by element
+    {CV_STAGED, 4, 1, 5, 2, 2, true},    // 2-D 5x5 stride 2 as 16-byte groups: 19 * 18 = 342 groups
+    {CV_STAGED, 4, 1, 5, 2, 6, false},   // ... element by element
+    {CV_HEAD, 4, 1, 5, 2, 0, false},     // the 3 -> 32 5x5 stride-2 head (cols % 8 == 0)
+};
+constexpr int CV_NFORMS = sizeof(CV_FORMS) / sizeof(CV_FORMS[0]);
+constexpr int cv_find_form(const ConvForm &f, int from = 0) {
+  for (int i = from; i < CV_NFORMS; ++i)
+    if (CV_FORMS[i].same(f)) return i;
+  return -1;
+}
+constexpr bool cv_forms_distinct(int i = 0) { return i == CV_NFORMS || (cv_find_form(CV_FORMS[i], i + 1) < 0 && cv_forms_distinct(i + 1)); }
+static_assert(cv_forms_distinct(), "a kernel form is listed twice");
+// (once a run-time test of the launch) the largest 2-D LDS-DMA layer, 16-row tiles at MVSN_DMA_MAX_DIL, stays within IPC 6 (107 KB of LDS)
+static_assert(cv_dma_ipc(16 + 2 * MVSN_DMA_MAX_DIL, MVSN_DMA_MAX_DIL) <= 6, "MVSN_DMA_MAX_DIL: more pieces per channel than an LDS-DMA row takes");
 
 static bool make_geom(const mvsn_conv_desc *d, ConvGeom *g) {
   if (!d || d->n <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->c_out > 32 || d->depth <= 0 || d->rows <= 0 ||
@@ -87,15 +132,12 @@ static bool make_geom(const mvsn_conv_desc *d, ConvGeom *g) {
   g->Wo = (d->cols - 1) / d->stride + 1;
   const bool is3d = d->depth > 1 || d->kd > 1;
   g->TZ = is3d ? 2 : 1;
-  // 2-D 3x3 layers on tall images use 16-row tiles (less halo per output, more MFMAs per staging).  On the
-  // LDS-DMA kernel (cols % 4 == 0) that holds for every dilation (measured on MI355X, B=128: 8/16 rows within
-  // 1.5 % at dilation 4/8); the register-staged kernel keeps 8-row tiles above dilation 2, where the 16-row
-  // halo no longer fits two workgroups' worth of staging registers (10-17 % slower).
-  {
-    const bool dma = d->cols % 4 == 0 && d->dilation <= MVSN_DMA_MAX_DIL;
-    const int tall_dil = dma ? MVSN_TALL_TILE_MAX_DIL : 2;
-    g->TY = (!is3d && d->kh == 3 && d->stride == 1 && d->dilation <= tall_dil && (d->rows - 1) / d->stride + 1 > 8) ? 16 : 8;
-  }
+  // 3x3 stride-1 layers whose rows are whole 16-byte pieces: LDS-DMA (MI355X, B=128: 2-5 % faster than register staging)
+  g->dma = (d->kd == 1 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->cols % 4 == 0 && d->dilation <= MVSN_DMA_MAX_DIL) ? 1 : 0;
+  // 2-D 3x3 layers on tall images use 16-row tiles (less halo per output, more MFMAs per staging).  On the LDS-DMA kernel that
+  // holds for every dilation (measured on MI355X, B=128: 8/16 rows within 1.5 % at dilation 4/8); the register-staged kernel keeps
+  // 8-row tiles above dilation 2, where the 16-row halo no longer fits two workgroups' worth of staging registers (10-17 % slower).
+  g->TY = (!is3d && d->kh == 3 && d->stride == 1 && d->dilation <= (g->dma ? MVSN_TALL_TILE_MAX_DIL : 2) && g->Ho > 8) ? 16 : 8;
   g->HZ = g->TZ + d->kd - 1;
   g->HY = (g->TY - 1) * d->stride + d->dilation * (d->kh - 1) + 1;
   g->HX = (CV_TX - 1) * d->stride + d->dilation * (d->kw - 1) + 1;
@@ -123,26 +165,19 @@ static bool make_geom(const mvsn_conv_desc *d, ConvGeom *g) {
   g->fd_ty = make_fastdiv((unsigned)g->TY);
   g->ntaps = d->kd * d->kh * d->kw;
   g->nchunks = (d->c_in + CV_CK - 1) / CV_CK;
-  g->wfloats_chunk = g->ntaps * 2 * 64;
-  g->lds_bytes = ((size_t)CV_CK * g->CST + g->wfloats_chunk + 64 /*in scale/shift*/ + 64 /*red*/) * sizeof(float);
+  g->wfloats_chunk = g->ntaps * 2 * 64, g->spare0 = 0, g->spare1 = 0;
   g->se = (g->HZ * g->HY * g->HX + CV_THREADS - 1) / CV_THREADS;
-  {
-    const int wslot = ((g->ntaps * 128 + 255) / 256) * 256;
-    g->dma_ok = (d->cols % 4 == 0 && d->stride == 1 && g->pw <= 8 && d->kw == 3) ? 1 : 0;
-    g->dpa = (g->pw + 3) / 4 * 4;
-    g->dq = (CV_TX + 2 * g->dpa) / 4;
-    g->dXS = 4 * g->dq;
-    g->dipc = (g->HZ * g->HY * g->dq + 63) / 64;
-    g->dCST = g->dipc * 256 + 16;                     // = 16 (mod 32): conflict-free 16-column x 4-channel reads
-    g->dma_stage_floats = CV_CK * g->dCST + wslot;    // + CV_CK * dCST more when a residual tile is staged
-    g->fd_dq = make_fastdiv((unsigned)g->dq);
-  }
-  if (g->se > 6) return false;
+  g->dpa = (g->pw + 3) / 4 * 4;
+  g->dq = cv_dma_dq(g->pw);
+  g->dXS = 4 * g->dq;
+  g->dipc = cv_dma_ipc(g->HZ * g->HY, g->pw);
+  g->dCST = g->dipc * 256 + 16;                     // = 16 (mod 32): conflict-free 16-column x 4-channel reads
+  g->fd_dq = make_fastdiv((unsigned)g->dq);
+  if (g->se > 6) return false;   // (no row stages more; with it a register-staged tile and its weights stay under 50 KB)
   const bool k333 = d->kd == 3 && d->kh == 3 && d->kw == 3 && d->stride == 1;
   const bool k133 = d->kd == 1 && d->kh == 3 && d->kw == 3 && d->stride == 1;
   const bool k155 = d->kd == 1 && d->kh == 5 && d->kw == 5 && d->stride == 2 && d->dilation == 1;
-  if (!(k333 || k133 || k155)) return false;
-  return g->lds_bytes <= 160 * 1024;
+  return k333 || k133 || k155;
 }
 
 // packed weights: [chunk of 4 cin][tap][cout-tile 2][lane 64]; lane = k*16 + i holds
@@ -302,8 +337,10 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_mfma_kernel(ConvGeom g, co
                                                                   float *__restrict__ out,
                                                                   float *__restrict__ out_partials) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  static_assert(KW == KH, "ConvForm has square kernels");
+  constexpr ConvForm L{CV_STAGED, NPT, KD, KH, STRIDE, SE, V4};   // (as an LDS plan)
   constexpr int NTAPS = KD * KH * KW;
-  constexpr int WFL = NTAPS * 128;            // weight floats per chunk
+  constexpr int WFL = L.wfl();                // weight floats per chunk
   constexpr int WR = (WFL / 4 + CV_THREADS - 1) / CV_THREADS;  // float4 per thread
   float *tile = smem;                               // CV_CK * CST
   float *wl = tile + (size_t)CV_CK * g.CST;         // WFL
@@ -543,21 +580,19 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_mfma_kernel(ConvGeom g, co
 }
 
 // ---------------------------------------------------------------------------------------------
-// LDS-DMA variant (3x3 / 3x3x3, stride 1): the same implicit GEMM, but the haloed chunk tiles and the
+// LDS-DMA variant (2-D 3x3, stride 1): the same implicit GEMM, but the haloed chunk tiles and the
 // weight fragments go HBM -> LDS with global_load_lds (no VGPR round trip, no LDS store pass) into a
 // two-stage ring, one barrier per chunk.  Wave w owns channel w of every 4-channel chunk: it issues
-// that channel's rows as 16-byte pieces, 1 KB per instruction (per-lane source address from the aligned
-// column x0 - halo (rounded up to 4); pieces outside the image read a zero word; requires cols % 4 == 0, otherwise the
-// register-staged kernel runs), and
-// once its own loads have landed it applies the fused input transform IN LDS on exactly those
-// elements -- LeakyReLU(GN(.)), optionally + residual (a whole SimpleBasicBlock folded into the next
-// layer's load) -- and writes the block output for its own output positions as a by-product.
+// that channel's rows as 16-byte pieces, 1 KB per instruction (per-lane source address from the aligned column x0 - halo (rounded
+// up to 4); pieces outside the image read a zero word; requires cols % 4 == 0, otherwise the register-staged kernel runs), and once
+// its own loads have landed it applies the fused input transform IN LDS on exactly those elements -- LeakyReLU(GN(.)), optionally +
+// residual (a whole SimpleBasicBlock folded into the next layer's load) -- and writes the block output for its own output positions as
+// a by-product.  2-D only: on the 3-D layers that in-LDS pass is exposed (measured 7 % slower than register staging, MI355X, B=128).
 //   MODE 0 plain input, 1 LReLU(GN(in)), 2 in_residual + LReLU(GN(in)) [+ out_staged]
 // ---------------------------------------------------------------------------------------------
 __device__ floatx4 g_zero16 = {0.f, 0.f, 0.f, 0.f};
 
-
-template <int NPT, int KD, int IPC, int CT, int MODE>
+template <int NPT, int IPC, int CT, int MODE>
 __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel(ConvGeom g, const float *__restrict__ in,
                                                                  const float *__restrict__ wpk,
                                                                  const float *__restrict__ bias,
@@ -569,12 +604,12 @@ __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel
                                                                  float *__restrict__ out,
                                                                  float *__restrict__ out_partials) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int NTAPS = KD * 9;
-  constexpr int WFL = NTAPS * 128;
-  constexpr int WSLOT = ((WFL + 255) / 256) * 256;
+  constexpr ConvForm L{CV_DMA, NPT, 1, 3, 1, IPC, false};   // (as an LDS plan)
+  constexpr int NTAPS = 9;
+  constexpr int WFL = L.wfl(), WSLOT = L.wslot(), NT = L.ntiles(MODE);
   constexpr int WRUNS = WSLOT / 256;            // 16-byte DMA runs (256 floats each) per chunk
   const int tile_floats = CV_CK * g.dCST;
-  const int stage_floats = tile_floats * (MODE == 2 ? 2 : 1) + WSLOT;
+  const int stage_floats = tile_floats * NT + WSLOT;
   float *scsh = smem + 2 * stage_floats;        // 64
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -665,7 +700,7 @@ __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel
       }
     }
     const float *wsrc = wpk + (size_t)chunk * WFL;
-    float *wdst = st + tile_floats * (MODE == 2 ? 2 : 1);
+    float *wdst = st + tile_floats * NT;
 #pragma unroll
     for (int r = 0; r < (WRUNS + CV_WAVES - 1) / CV_WAVES; ++r) {
       const int run = r * CV_WAVES + wave;
@@ -721,7 +756,7 @@ __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel
     DMA_STAMP();   // next chunk issued
 
     const float *tile = st;
-    const float *wt = st + tile_floats * (MODE == 2 ? 2 : 1) + lane;
+    const float *wt = st + tile_floats * NT + lane;
     float fw[2][2], fb[2][NPT];
     auto read_tap = [&](int tap, int buf) {
       const int tz = tap / 9, ty = (tap / 3) % 3, tx = tap % 3;
@@ -761,8 +796,6 @@ __global__ __launch_bounds__(CV_THREADS, MODE <= 1 ? 4 : 2) void conv_dma_kernel
 // (3 x 19 x 72 floats) is staged once, and the MFMA loop reads only its A fragments from LDS.
 // A = activations (16 pixels x 4 k), B = weights (4 k x 16 couts), D = pixels x couts as everywhere (16-byte stores).
 // ---------------------------------------------------------------------------------------------
-constexpr int HD_TY = 8, HD_TX = 32, HD_ROWS = 2 * HD_TY + 3, HD_XS = 2 * HD_TX + 8;   // 19 rows of 72 floats
-constexpr int HD_CST = HD_ROWS * HD_XS + 4;                                           // channel stride (floats)
 constexpr int HD_KSTEPS = 19;
 static_assert(3 * HD_CST < 65536, "k-step offsets are packed as 16-bit values");
 
@@ -1041,6 +1074,44 @@ __global__ void mfma_selftest_kernel(int *bad) {
   if (wrong) atomicAdd(bad, wrong);
 }
 
+// The extractor's 3 -> 32 5x5 stride-2 head has a kernel of its own (K = 75 packing; no fused transform or statistics on this
+// layer).  `head_call`: what the call, not the layer, adds -- fp32 precision, no statistics, `in` and `out` 16-byte aligned.
+static bool conv_head_ok(const ConvGeom &g, int mode, bool head_call) {
+  return head_call && mode == 0 && g.cin == 3 && g.cout == 32 && g.kd == 1 && g.kh == 5 && g.kw == 5 && g.stride == 2 &&
+         g.dil == 1 && g.D == 1 && (g.W & 7) == 0 &&
+         // descriptor ranges / 32-bit offsets of the kernel: the input plane AND a sample's full 32-channel output extent
+         // ((int)(32 * oplane * 4) is the output descriptor's range, (cl * oplane + ox) * 4 a store offset)
+         (size_t)g.H * g.W * 4 < ((size_t)1 << 31) && (size_t)32 * g.Ho * g.Wo * 4 < ((size_t)1 << 31);
+}
+
+// The form a layer runs on in `mode` (its row of CV_FORMS; -1: none).  The only place that maps a geometry to a form.
+static int conv_select(const ConvGeom &g, int mode, bool head_call) {
+  if (conv_head_ok(g, mode, head_call)) return cv_find_form(ConvForm{CV_HEAD, 4, 1, 5, 2, 0, false});
+  ConvForm f = {CV_STAGED, g.TY == 16 ? 8 : 4, g.kd, g.kh, g.stride, g.se <= 3 ? 3 : 6, g.v4 != 0};
+  if (g.dma && g.dipc <= 6)   // (more than 6 pieces: only a 1x3x3 kernel on a volume, see the static_assert; register-staged as ever)
+    f.kind = CV_DMA, f.se = g.dipc <= 4 ? 4 : 6;
+  else if (g.kd == 3 || g.kh == 5) f.npt = g.kd == 3 ? 8 : 4, f.se = g.v4 ? 2 : 6;   // (3-D: TZ = 2; 400 / 342 16-byte groups)
+  return cv_find_form(f);
+}
+// CT and MODE of the kernel a call gets: CT 1 for the 3x3 kernels; MODE 1 on LDS-DMA only (register staging: a run-time test), 2 / RES: 2-D 3x3
+constexpr int conv_ct(const ConvForm &f, int cout) { return f.kind != CV_HEAD && f.kh == 3 && cout <= 16 ? 1 : 2; }
+constexpr int conv_mode(const ConvForm &f, int mode) { return f.dma() ? mode : (f.kd == 1 && f.kh == 3 && mode == 2 ? 2 : 0); }
+
+// The tier a descriptor names (Winograd, bf16 / bf16x3 operands, else the direct fp32 kernels), whether it has a form, its geometry
+struct ConvTier {
+  enum Kind { WINO, BF16, DIRECT } kind;
+  bool ok;
+  union { WinoGeom wg; Bf16x3Geom bg; ConvGeom g; };   // of `kind`, where ok
+};
+static ConvTier conv_tier(const mvsn_conv_desc *desc) {
+  ConvTier t{};
+  const int p = desc ? desc->precision : MVSN_CONV_FP32;
+  if (p == MVSN_CONV_FP32_WINO) t.kind = ConvTier::WINO, t.ok = wino_geom(desc, &t.wg);
+  else if (p == MVSN_CONV_BF16X3 || p == MVSN_CONV_BF16) t.kind = ConvTier::BF16, t.ok = bf16x3_geom(desc, &t.bg);
+  else t.kind = ConvTier::DIRECT, t.ok = make_geom(desc, &t.g);
+  return t;
+}
+
 }  // namespace mvsn
 
 extern "C" int mvsn_conv_bf16x3_supported(const mvsn_conv_desc *desc) {
@@ -1073,49 +1144,37 @@ extern "C" int mvsn_conv_winograd_supported(const mvsn_conv_desc *desc) {
 }
 
 extern "C" size_t mvsn_conv_packed_floats(const mvsn_conv_desc *desc) {
-  if (desc && desc->precision == MVSN_CONV_FP32_WINO) {
-    mvsn::WinoGeom wg;
-    return mvsn::wino_geom(desc, &wg) ? wg.packed_floats : 0;
-  }
-  if (desc && (desc->precision == MVSN_CONV_BF16X3 || desc->precision == MVSN_CONV_BF16)) {
-    mvsn::Bf16x3Geom bg;
-    return mvsn::bf16x3_geom(desc, &bg) ? (size_t)desc->kd * 9 * 1024 : 0;   // [tap][2][2][64][8] bf16
-  }
-  mvsn::ConvGeom g;
-  if (!mvsn::make_geom(desc, &g)) return 0;
-  return (size_t)g.nchunks * g.wfloats_chunk;
+  const mvsn::ConvTier t = mvsn::conv_tier(desc);
+  if (!t.ok) return 0;
+  if (t.kind == mvsn::ConvTier::WINO) return t.wg.packed_floats;
+  if (t.kind == mvsn::ConvTier::BF16) return (size_t)desc->kd * 9 * 1024;   // [tap][2][2][64][8] bf16
+  return (size_t)t.g.nchunks * t.g.wfloats_chunk;
 }
 
 extern "C" int mvsn_conv_num_tiles(const mvsn_conv_desc *desc) {
   // number of GroupNorm partial records per sample: one per (tile, wave, 16-lane row)
-  if (desc && desc->precision == MVSN_CONV_FP32_WINO) {
-    mvsn::WinoGeom wg;
-    return mvsn::wino_geom(desc, &wg) ? (int)(mvsn::wino_items(wg) * 32) : 0;   // per (plane,) tile: 8 waves x 4 lane rows
-  }
-  if (desc && (desc->precision == MVSN_CONV_BF16X3 || desc->precision == MVSN_CONV_BF16)) {
-    mvsn::Bf16x3Geom bg;
-    return mvsn::bf16x3_geom(desc, &bg) ? bg.tiles * 4 : 0;
-  }
-  mvsn::ConvGeom g;
-  if (!mvsn::make_geom(desc, &g)) return 0;
-  return g.tiles * 16;   // per tile: 4 waves x 4 lane rows
+  const mvsn::ConvTier t = mvsn::conv_tier(desc);
+  if (!t.ok) return 0;
+  if (t.kind == mvsn::ConvTier::WINO) return (int)(mvsn::wino_items(t.wg) * 32);   // per (plane,) tile: 8 waves x 4 lane rows
+  if (t.kind == mvsn::ConvTier::BF16) return t.bg.tiles * 4;
+  return t.g.tiles * 16;   // per tile: 4 waves x 4 lane rows
 }
 
 extern "C" int mvsn_conv_pack_weights(const mvsn_conv_desc *desc, const float *weight, float *packed,
                                       mvsn_stream_t stream) {
+  using namespace mvsn;
   MVSN_REQUIRE(weight && packed, MVSN_E_BADARG, "mvsn_conv_pack_weights: null pointer");
-  if (desc && desc->precision == MVSN_CONV_FP32_WINO) {
-    mvsn::WinoGeom wg;
-    MVSN_REQUIRE(mvsn::wino_geom(desc, &wg), MVSN_E_BADARG, "mvsn_conv_pack_weights: layer has no Winograd form");
+  const ConvTier t = conv_tier(desc);
+  if (t.kind == ConvTier::WINO) {
+    MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_pack_weights: layer has no Winograd form");
     return mvsn::wino_pack(desc, weight, packed, (hipStream_t)stream);
   }
-  if (desc && (desc->precision == MVSN_CONV_BF16X3 || desc->precision == MVSN_CONV_BF16)) {
-    mvsn::Bf16x3Geom bg;
-    MVSN_REQUIRE(mvsn::bf16x3_geom(desc, &bg), MVSN_E_BADARG, "mvsn_conv_pack_weights: layer has no bf16x3 form");
+  if (t.kind == ConvTier::BF16) {
+    MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_pack_weights: layer has no bf16x3 form");
     return mvsn::bf16x3_pack(desc, weight, packed, (hipStream_t)stream);
   }
-  mvsn::ConvGeom g;
-  MVSN_REQUIRE(mvsn::make_geom(desc, &g), MVSN_E_BADARG, "mvsn_conv_pack_weights: unsupported descriptor");
+  MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_pack_weights: unsupported descriptor");
+  const ConvGeom &g = t.g;
   const int total = g.nchunks * g.ntaps * 128;
   hipLaunchKernelGGL(mvsn::conv_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, weight,
                      g.cin, g.cout, g.ntaps, g.nchunks, packed);
@@ -1157,47 +1216,26 @@ extern "C" int mvsn_conv_forward(const mvsn_conv_desc *desc, const float *in, co
                                  float *out_partials, mvsn_stream_t stream) {
   using namespace mvsn;
   MVSN_REQUIRE(in && weight_packed && out, MVSN_E_BADARG, "mvsn_conv_forward: null pointer");
-  if (desc && desc->precision == MVSN_CONV_FP32_WINO) {
-    WinoGeom wg;
-    MVSN_REQUIRE(wino_geom(desc, &wg), MVSN_E_BADARG, "mvsn_conv_forward: layer has no Winograd form");
+  const ConvTier t = conv_tier(desc);
+  if (t.kind == ConvTier::WINO) {
+    MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_forward: layer has no Winograd form");
     MVSN_REQUIRE(!in_residual && !out_staged, MVSN_E_BADARG, "mvsn_conv_forward: Winograd form has no residual folding");
-    MVSN_REQUIRE(!in_stats || (in_gamma && in_beta && wg.cin == 32), MVSN_E_BADARG,
+    MVSN_REQUIRE(!in_stats || (in_gamma && in_beta && t.wg.cin == 32), MVSN_E_BADARG,
                  "mvsn_conv_forward: input transform needs gamma/beta and 32 channels");
-    MVSN_REQUIRE(wg.n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
-    return wino_launch(wg, in, weight_packed, bias, in_stats, in_gamma, in_beta, out, out_partials,
+    MVSN_REQUIRE(t.wg.n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
+    return wino_launch(t.wg, in, weight_packed, bias, in_stats, in_gamma, in_beta, out, out_partials,
                        (hipStream_t)stream);
   }
-  if (desc && (desc->precision == MVSN_CONV_BF16X3 || desc->precision == MVSN_CONV_BF16)) {
-    Bf16x3Geom bg;
-    MVSN_REQUIRE(bf16x3_geom(desc, &bg), MVSN_E_BADARG, "mvsn_conv_forward: layer has no bf16x3 form");
+  if (t.kind == ConvTier::BF16) {
+    MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_forward: layer has no bf16x3 form");
     MVSN_REQUIRE(!in_residual && !out_staged, MVSN_E_BADARG, "mvsn_conv_forward: bf16x3 has no residual folding");
     MVSN_REQUIRE(!in_stats || (in_gamma && in_beta), MVSN_E_BADARG, "mvsn_conv_forward: input transform needs gamma/beta");
-    MVSN_REQUIRE(bg.n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
-    return bf16x3_launch(bg, in, weight_packed, bias, in_stats, in_gamma, in_beta, out, out_partials,
+    MVSN_REQUIRE(t.bg.n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
+    return bf16x3_launch(t.bg, in, weight_packed, bias, in_stats, in_gamma, in_beta, out, out_partials,
                          (hipStream_t)stream);
   }
-  ConvGeom g;
-  MVSN_REQUIRE(make_geom(desc, &g), MVSN_E_BADARG, "mvsn_conv_forward: unsupported descriptor");
-  // ---- the extractor's 3 -> 32 5x5 stride-2 head: K = 75 packing (no fused transform / statistics on this layer) ----
-  if (desc->precision == MVSN_CONV_FP32 && desc->c_in == 3 && desc->c_out == 32 && desc->kd == 1 && desc->kh == 5 &&
-      desc->kw == 5 && desc->stride == 2 && desc->dilation == 1 && desc->depth == 1 && (desc->cols & 7) == 0 &&
-      // descriptor ranges / 32-bit offsets of the kernel: the input plane AND a sample's full 32-channel output extent
-      // ((int)(32 * oplane * 4) is the output descriptor's range, (cl * oplane + ox) * 4 a store offset)
-      (size_t)desc->rows * desc->cols * 4 < ((size_t)1 << 31) &&
-      (size_t)32 * ((desc->rows - 1) / 2 + 1) * ((desc->cols - 1) / 2 + 1) * 4 < ((size_t)1 << 31) &&
-      !in_stats && !in_residual && !out_staged && !out_partials && ((size_t)in & 15) == 0 && ((size_t)out & 15) == 0) {
-    MVSN_REQUIRE(desc->n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
-    const int Ho = (desc->rows - 1) / 2 + 1, Wo = (desc->cols - 1) / 2 + 1;
-    const int nty = (Ho + HD_TY - 1) / HD_TY, ntx = (Wo + HD_TX - 1) / HD_TX, tiles = nty * ntx;
-    // (persistent workgroups, MVSN_HEAD_WGS_PER_CU per CU -- three without a spill -- that cover each other's barrier and
-    // store tails; each walks its tiles through a two-slot DMA ring)
-    MVSN_REQUIRE((long long)tiles * desc->n < (1ll << 31) - 65536, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
-    const int total = tiles * desc->n;
-    const int gx = std::min(total, MVSN_HEAD_WGS_PER_CU * device_cus());
-    hipLaunchKernelGGL(conv5x5s2_head_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, in, weight_packed, bias,
-                       desc->rows, desc->cols, Ho, Wo, ntx, tiles, total, out);
-    return check_launch("mvsn_conv_forward(5x5 stride-2 head)");
-  }
+  const ConvGeom &g = t.g;
+  MVSN_REQUIRE(t.ok, MVSN_E_BADARG, "mvsn_conv_forward: unsupported descriptor");
   MVSN_REQUIRE(!in_stats || (in_gamma && in_beta), MVSN_E_BADARG, "mvsn_conv_forward: input transform needs gamma/beta");
   MVSN_REQUIRE(!in_stats || g.cin == 32, MVSN_E_BADARG, "mvsn_conv_forward: input transform needs 32 channels");
   MVSN_REQUIRE(!out_partials || g.cout == 32, MVSN_E_BADARG, "mvsn_conv_forward: partials need 32 output channels");
@@ -1205,86 +1243,47 @@ extern "C" int mvsn_conv_forward(const mvsn_conv_desc *desc, const float *in, co
   MVSN_REQUIRE(!(in_residual || out_staged) || (g.kd == 1 && g.kh == 3 && g.stride == 1), MVSN_E_BADARG,
                "mvsn_conv_forward: residual / staged output only for 2-D 3x3 stride-1 layers");
   MVSN_REQUIRE(g.n <= 65535, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
-  dim3 grid(g.tiles, g.n);
+  const int mode = (in_residual || out_staged) ? 2 : (in_stats ? 1 : 0);
+  const int row = conv_select(g, mode, desc->precision == MVSN_CONV_FP32 && !out_partials && (((size_t)in | (size_t)out) & 15) == 0);
+  MVSN_REQUIRE(row >= 0, MVSN_E_BADARG, "mvsn_conv_forward: no kernel form for this layer");
   static_assert(CV_CK == CV_WAVES, "one DMA channel per wave");
-  // ---- LDS-DMA pipeline for the 2-D 3x3 stride-1 layers with dilation <= 4 ---------------------
-  // (measured on MI355X, B=128: 2-5 % faster than register staging there, 7 % slower on the 3-D
-  // layers where the in-LDS transform pass is exposed, and 8 % slower at dilation 8)
-  if (g.kd == 1 && g.kh == 3 && g.stride == 1 && g.dil <= MVSN_DMA_MAX_DIL && g.dma_ok) {
-    const int mode = (in_residual || out_staged) ? 2 : (in_stats ? 1 : 0);
-    const size_t stage = (size_t)g.dma_stage_floats + (mode == 2 ? (size_t)CV_CK * g.dCST : 0);
-    const size_t lds = (2 * stage + 64 + 16) * sizeof(float);
-    const bool one = g.cout <= 16;
-#define MVSN_DMA_LAUNCH(...)                                                                                      \
-  do {                                                                                                            \
-    auto kern = conv_dma_kernel<__VA_ARGS__>;                                                                     \
-    static LdsOptIn opt;                                                                                          \
-    if (int rc = ensure_lds(opt, (const void *)kern, lds, "mvsn_conv_forward(dma)")) return rc;                   \
-    hipLaunchKernelGGL(kern, grid, dim3(CV_THREADS), lds, (hipStream_t)stream, g, in, weight_packed, bias, in_stats, \
-                       in_gamma, in_beta, in_residual, out_staged, out, out_partials);                            \
-    return check_launch("mvsn_conv_forward(dma)");                                                                \
-  } while (0)
-#define MVSN_DMA_MODES(NPTV, KDV, IPCV)                                                          \
-  do {                                                                                           \
-    if (one) {                                                                                   \
-      if (mode == 0) MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 1, 0);                                     \
-      else if (mode == 1) MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 1, 1);                                \
-      else MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 1, 2);                                               \
-    } else {                                                                                     \
-      if (mode == 0) MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 2, 0);                                     \
-      else if (mode == 1) MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 2, 1);                                \
-      else MVSN_DMA_LAUNCH(NPTV, KDV, IPCV, 2, 2);                                               \
-    }                                                                                            \
-  } while (0)
-    if (lds <= 160 * 1024 && g.dipc <= 6) {
-      if (g.TY == 16) {
-        if (g.dipc <= 4) MVSN_DMA_MODES(8, 1, 4);
-        else MVSN_DMA_MODES(8, 1, 6);
-      } else {
-        if (g.dipc <= 4) MVSN_DMA_MODES(4, 1, 4);
-        else MVSN_DMA_MODES(4, 1, 6);
-      }
+  // the kernel of (row, CT, MODE), folded over K = (row * 2 + CT - 1) * 3 + MODE: instantiated here, once per
+  // combination the row exists in (the others return at the first `if constexpr`), with its own LdsOptIn
+  const int kernel = (row * 2 + conv_ct(CV_FORMS[row], g.cout) - 1) * 3 + conv_mode(CV_FORMS[row], mode);
+  return with_form_row(kernel, std::make_index_sequence<CV_NFORMS * 6>{}, [&](auto K) -> int {
+    constexpr ConvForm F = CV_FORMS[K / 6];   // K = (row * 2 + CT - 1) * 3 + MODE, taken apart again
+    constexpr int CT = K / 3 % 2 + 1, MODE = K % 3;
+    if constexpr (conv_ct(F, CT == 1 ? 16 : 32) != CT || conv_mode(F, MODE) != MODE) return MVSN_E_BADARG;   // (no such kernel)
+    else if constexpr (F.kind == CV_HEAD) {   // persistent workgroups, MVSN_HEAD_WGS_PER_CU per CU (three without a spill)
+      MVSN_REQUIRE((long long)g.tiles * g.n < (1ll << 31) - 65536, MVSN_E_TOOLARGE, "mvsn_conv_forward: batch too large for one launch");
+      const int total = g.tiles * g.n, gx = std::min(total, MVSN_HEAD_WGS_PER_CU * device_cus());
+      hipLaunchKernelGGL(conv5x5s2_head_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, in, weight_packed, bias, g.H, g.W,
+                         g.Ho, g.Wo, g.ntx, g.tiles, total, out);
+      return check_launch("mvsn_conv_forward(5x5 stride-2 head)");
+    } else {
+      static LdsOptIn opt;
+      const size_t lds = F.lds_bytes(g, MODE);
+      auto run = [&](auto kern, const char *what) -> int {
+        if (int rc = ensure_lds(opt, (const void *)kern, lds, what)) return rc;
+        hipLaunchKernelGGL(kern, dim3(g.tiles, g.n), dim3(CV_THREADS), lds, (hipStream_t)stream, g, in, weight_packed, bias,
+                           in_stats, in_gamma, in_beta, in_residual, out_staged, out, out_partials);
+        return check_launch(what);
+      };
+      if constexpr (F.dma()) return run(conv_dma_kernel<F.npt, F.se, CT, MODE>, "mvsn_conv_forward(dma)");
+      else return run(conv_mfma_kernel<F.npt, F.kd, F.kh, F.kh, F.stride, F.se, CT, MODE == 2, F.v4>, "mvsn_conv_forward");
     }
-#undef MVSN_DMA_MODES
-#undef MVSN_DMA_LAUNCH
-  }
-#define MVSN_CONV_LAUNCH(...)                                                                                    \
-  do {                                                                                                           \
-    auto kern = conv_mfma_kernel<__VA_ARGS__>;                                                                   \
-    static LdsOptIn opt;                                                                                         \
-    if (int rc = ensure_lds(opt, (const void *)kern, g.lds_bytes, "mvsn_conv_forward")) return rc;               \
-    hipLaunchKernelGGL(kern, grid, dim3(CV_THREADS), g.lds_bytes, (hipStream_t)stream, g, in, weight_packed, bias, \
-                       in_stats, in_gamma, in_beta, in_residual, out_staged, out, out_partials);                 \
-  } while (0)
-  const bool one_tile = g.cout <= 16;
-  const bool se3 = g.se <= 3;
-  const bool res = in_residual != nullptr || out_staged != nullptr;
-#define MVSN_CONV_2D(NPTV)                                                                      \
-  do {                                                                                          \
-    if (one_tile) {                                                                             \
-      if (se3) { if (res) MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 3, 1, true); else MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 3, 1, false); } \
-      else     { if (res) MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 6, 1, true); else MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 6, 1, false); } \
-    } else {                                                                                    \
-      if (se3) { if (res) MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 3, 2, true); else MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 3, 2, false); } \
-      else     { if (res) MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 6, 2, true); else MVSN_CONV_LAUNCH(NPTV, 1, 3, 3, 1, 6, 2, false); } \
-    }                                                                                           \
-  } while (0)
-  if (g.kd == 3 && g.v4) {               // 3-D 3x3x3 staged as 16-byte groups: 4*10*10 = 400 groups -> 2 per thread
-    if (one_tile) MVSN_CONV_LAUNCH(8, 3, 3, 3, 1, 2, 1, false, true); else MVSN_CONV_LAUNCH(8, 3, 3, 3, 1, 2, 2, false, true);
-  } else if (g.kd == 3) {                // 3-D 3x3x3, TZ=2 TY=8 -> NPT 8, SE 6
-    if (one_tile) MVSN_CONV_LAUNCH(8, 3, 3, 3, 1, 6, 1, false); else MVSN_CONV_LAUNCH(8, 3, 3, 3, 1, 6, 2, false);
-  } else if (g.kh == 5 && g.v4) {        // 2-D 5x5 stride 2 staged as 16-byte groups: 19 * 18 = 342 groups -> 2 per thread
-    MVSN_CONV_LAUNCH(4, 1, 5, 5, 2, 2, 2, false, true);
-  } else if (g.kh == 5) {                // 2-D 5x5 stride 2, TY=8 -> NPT 4
-    MVSN_CONV_LAUNCH(4, 1, 5, 5, 2, 6, 2, false);
-  } else if (g.TY == 16) {               // 2-D 3x3, NPT 8
-    MVSN_CONV_2D(8);
-  } else {                               // 2-D 3x3, NPT 4
-    MVSN_CONV_2D(4);
-  }
-#undef MVSN_CONV_2D
-#undef MVSN_CONV_LAUNCH
-  return check_launch("mvsn_conv_forward");
+  });
+}
+
+// host only: what conv_select, conv_ct and the form's LDS plan say about a layer (no logic of its own)
+extern "C" int mvsn_debug_conv_plan(const mvsn_conv_desc *desc, int mode, int out[8]) {
+  const mvsn::ConvTier t = mvsn::conv_tier(desc);
+  const int row = out && t.kind == mvsn::ConvTier::DIRECT && t.ok ? mvsn::conv_select(t.g, mode, desc->precision == MVSN_CONV_FP32) : -1;
+  if (row < 0) return 0;
+  const mvsn::ConvForm &f = mvsn::CV_FORMS[row];
+  out[0] = row, out[1] = f.kind, out[2] = f.npt, out[3] = f.se, out[4] = f.v4, out[5] = mvsn::conv_ct(f, t.g.cout);
+  out[6] = (int)f.lds_bytes(t.g, mvsn::conv_mode(f, mode)), out[7] = t.g.tiles;
+  return mvsn::CV_NFORMS;
 }
 
 #ifdef MVSN_DMA_STAMPS

@@ -1704,14 +1704,6 @@ bool wino_can_carry(const WinoGeom &g, const mvsn_apply_job *job) {
   return units <= capacity && capacity < (1L << 31) && units < (1L << 30);
 }
 
-// f(integral_constant<I>) for the row I == row: the fold that turns the run-time row into a compile-time one
-template <class F, size_t... I>
-static int wn_with_row(int row, std::index_sequence<I...>, F &&f) {
-  int rc = MVSN_E_BADARG;
-  (void)((row == (int)I && ((rc = f(std::integral_constant<int, (int)I>{})), true)) || ...);
-  return rc;
-}
-
 int wino_launch(const WinoGeom &g, const float *in, const float *upk, const float *bias, const float *in_stats,
                 const float *in_gamma, const float *in_beta, float *out, float *out_partials, hipStream_t stream,
                 const WinoBlocks *blocks, const mvsn_apply_job *job) {
@@ -1777,7 +1769,7 @@ int wino_launch(const WinoGeom &g, const float *in, const float *upk, const floa
     return 0;
   };
   const bool xf = in_stats != nullptr;
-  if (int rc = wn_with_row(row, std::make_index_sequence<WN_NFORMS>{}, [&](auto I) {
+  if (int rc = with_form_row(row, std::make_index_sequence<WN_NFORMS>{}, [&](auto I) {
         return xf ? launch(std::integral_constant<int, 1>{}, I) : launch(std::integral_constant<int, 0>{}, I);
       }))
     return rc;

@@ -170,6 +170,41 @@ def test_winograd_form_selection_is_pinned_host_side():
         lib.mvsn_debug_set_wino_rowphase(old)
 
 
+def test_direct_form_selection_is_pinned_host_side():
+    """Which kernel form every direct fp32 layer runs on -- row of the table, kind, pixel tiles per wave, staged elements
+    or DMA pieces, 16-byte staging, cout tiles -- its LDS bytes and tiles per sample, through mvsn_debug_conv_plan (host
+    only).  The expected plans (conv_form_cases.py) are the geometry and launch ladder of the code before the forms became
+    one table; together the cases name every row, so a new row cannot arrive unpinned."""
+    import conv_form_cases as cf
+    lib = _native.load()
+    hit, nrows = set(), set()
+    for c in cf.CASES + [cf.PADDED_CHUNK]:
+        got, n = cf.plan(lib, _native, c)
+        assert got == c.plan, (cf.case_id(c), got, c.plan)
+        if got is not None:
+            hit.add(got[0])
+            nrows.add(n)
+            # partial records per sample: tiles x 4 waves x 4 lane rows; the batch changes nothing
+            d = _native.ConvDesc(1, c.cin, c.cout, c.depth, c.rows, c.cols, c.kd, c.k, c.k, c.stride, c.dil)
+            assert lib.mvsn_conv_num_tiles(ctypes.byref(d)) == got[7] * 16
+            assert cf.plan(lib, _native, c, n=5)[0] == got
+        else:
+            assert n == 0
+    assert nrows == {12} and hit == set(range(12)), (nrows, sorted(hit))
+    # written out once: the 16-row LDS-DMA tile at dilation 8 with a residual tile, and the register-staged 3x3x3 tile
+    big, = [c for c in cf.CASES if (c.rows, c.cols, c.dil, c.mode, c.cout) == (17, 36, 8, 2, 8)]
+    assert big.plan[6] == (2 * (2 * 4 * (6 * 256 + 16) + 1280) + 80) * 4 == 109888
+    assert cf._staged_lds(25, 27) == (4 * 1616 + 3456 + 128) * 4 == 40192
+    # the head needs cols % 8 == 0 and a plain call; a Winograd or bf16 descriptor has no direct plan
+    out = (ctypes.c_int * 8)()
+    head = _native.ConvDesc(1, 3, 32, 1, 17, 72, 1, 5, 5, 2, 1)
+    assert lib.mvsn_debug_conv_plan(ctypes.byref(head), 1, ctypes.byref(out)) == 12 and out[0] == cf.S2_V4
+    for prec in (_native.CONV_FP32_WINO, _native.CONV_BF16X3):
+        d = _native.ConvDesc(1, 32, 32, 1, 17, 36, 1, 3, 3, 1, 1, prec)
+        assert lib.mvsn_debug_conv_plan(ctypes.byref(d), 0, ctypes.byref(out)) == 0
+    assert lib.mvsn_debug_conv_plan(None, 0, ctypes.byref(out)) == 0
+
+
 def test_banded_plan_selection_host_logic():
     """Which plan a banded call runs, and what it needs, from the host side alone (no device: the library assumes 256
     CUs): thin bands while the chains fit one of their passes, slabs beyond (mvsn_chain_slab.hip); passes of equal size, or

@@ -562,6 +562,72 @@ def test_conv_with_folded_residual_block(rows, cols, dil, cout):
     close(out2, F.conv2d(x0_ref, w, b, padding=dil, dilation=dil), rtol=1e-4, atol=2e-4)
 
 
+import conv_form_cases as _cf
+
+DIRECT_ROW_CASES = [c for c in _cf.CASES if c.plan is not None] + [_cf.PADDED_CHUNK]
+
+
+@pytest.mark.parametrize("case", DIRECT_ROW_CASES, ids=_cf.case_id)
+def test_conv_direct_every_row(case):
+    """Every row of the direct fp32 kernels' table of forms (LDS-DMA, register-staged, the 3 -> 32 head), in every mode
+    the row has kernels for, against ATen on the CPU with Winograd off: plain input, LReLU(GN(r)) folded into the tile
+    load, and x + LReLU(GN(r)) with the staged tensor written out (statistics formed in fp64).  Each layer first resolves,
+    host side, to the row it is meant for."""
+    from multi_view_stereonet_amd.multi_view_stereonet import _Conv, _Norm
+    eng = net_for("gta_sfm_150epochs").engine()
+    c, n = case, 2
+    got_plan, nrows = _cf.plan(eng.lib, _native, c, n=n)
+    assert got_plan == c.plan and nrows == 12, (got_plan, c.plan)
+    g = torch.Generator().manual_seed(c.rows * 100 + c.cols + c.dil + 7 * c.mode)
+    vol = c.kd == 3
+    shape = (n, c.cin, c.depth, c.rows, c.cols) if vol else (n, c.cin, c.rows, c.cols)
+    r = torch.randn(shape, generator=g) * 1.5 + 0.3
+    x = torch.randn(shape, generator=g)
+    w = torch.randn((c.cout, c.cin) + ((3,) if vol else ()) + (c.k, c.k), generator=g) * 0.05
+    b = torch.randn(c.cout, generator=g) * 0.1
+    gamma, beta = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1
+
+    class P:
+        weight, bias = gamma.to(DEV), beta.to(DEV)
+    pad = c.dil * (c.k // 2)
+    conv = (lambda t_: F.conv3d(t_, w, b, padding=(1, pad, pad))) if vol else \
+        (lambda t_: F.conv2d(t_, w, b, stride=c.stride, padding=pad, dilation=c.dil))
+    layer = _Conv(eng.lib, w.to(DEV), b.to(DEV), stride=c.stride, dilation=c.dil)
+    want_stats = c.cout == 32 and c.plan[1] != _cf.HEAD_KIND     # (the head's kernel takes no statistics)
+    stats_in = None
+    if c.mode:
+        rg = r.reshape(n, 4, -1).double()
+        stats_in = torch.stack([rg.mean(2), 1.0 / (rg.var(2, unbiased=False) + 1e-5).sqrt()], 2).float().contiguous().to(DEV)
+        xin = F.leaky_relu(F.group_norm(r, 4, gamma, beta, 1e-5), 0.2) + (x if c.mode == 2 else 0.0)
+    else:
+        xin = r
+    ref = conv(xin)
+    old = eng.winograd
+    eng.winograd = False
+    try:
+        if c.mode == 2:
+            out, stats, staged = eng.conv(layer, r.to(DEV), in_stats=stats_in, in_norm=_Norm(P), in_residual=x.to(DEV),
+                                          write_staged=True, want_stats=want_stats)
+            close(staged, xin, rtol=1e-4, atol=1e-4)
+        elif c.mode == 1:
+            out, stats = eng.conv(layer, r.to(DEV), in_stats=stats_in, in_norm=_Norm(P), want_stats=want_stats)
+        else:
+            out, stats = eng.conv(layer, r.to(DEV), want_stats=want_stats)
+    finally:
+        eng.winograd = old
+    close(out, ref, rtol=1e-4, atol=2e-4 if c.mode else 1e-4)
+    if want_stats:
+        rg = ref.reshape(n, 4, -1).double()
+        close(stats[:, :, 0], rg.mean(2), rtol=1e-4, atol=1e-5)
+        close(stats[:, :, 1], 1.0 / (rg.var(2, unbiased=False) + 1e-5).sqrt(), rtol=1e-4, atol=1e-5)
+
+
+def test_conv_direct_every_row_cases_name_every_row():
+    """The cases of test_conv_direct_every_row name every row of the table but the head's kernel on its own shapes (that
+    is test_conv_5x5_stride2_head_persistent_kernel) -- the head row is among them all the same."""
+    assert {c.plan[0] for c in DIRECT_ROW_CASES} >= set(range(12)) - {_cf.HEAD}
+
+
 @pytest.mark.parametrize("dims,depth,rows,cols,n", [(2, 1, 16, 32, 2), (2, 1, 37, 68, 1), (2, 1, 256, 512, 1), (2, 1, 5, 4, 3),
                                                     (3, 8, 4, 8, 2), (3, 12, 16, 32, 1), (3, 5, 30, 40, 1),
                                                     (3, 64, 16, 32, 2), (3, 96, 30, 40, 1), (3, 7, 32, 64, 1), (3, 1, 16, 32, 1),
