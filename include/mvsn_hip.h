@@ -723,6 +723,38 @@ int mvsn_tsdf_extract(const float *sdf_sum, const float *weight, const float *co
                       const void *workspace, size_t workspace_bytes, long n_vertices, long n_quads, float *vertices,
                       float *normals, uint8_t *colors, int64_t *faces, int64_t *cell, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ray-cast of the TSDF volume: the surface as cameras (K, T_cam_in_world) see it (tsdf.TSDFVolume.raycast; the
+ * semantics, every fp32 step and the error bounds are DESIGN.md section 16).  The state is mvsn_tsdf_integrate's, dims of
+ * at least 2 each; K, T_cam_in_world (V,4,4), K's bottom row taken to be (0,0,1); 1 <= V <= 65535, rows, cols <= 2^24,
+ * rows * cols <= 2^31 - 1; pixel (x, y) = (column, row), integer at the centre.
+ * Per view A = R K^-1 / voxel_size and g0 = (t - origin) / voxel_size (fp64, each number rounded once); per pixel
+ *   dir_a = fma(A_a0, x, fma(A_a1, y, A_a2)); sample k >= 1 at t_k = (float)k * step takes part iff min_depth < t_k <=
+ *   max_depth (max_depth may be +infinity); g = fma(t_k, dir, g0), cell c = floor(g), in range iff 0 <= c_a <= N_a - 2;
+ *   the sample is defined iff it is in range and the 8 corners of c have weight >= min_weight, and its value is the
+ *   trilinear interpolant (x, then y, then z, each lerp fma(fr, hi - lo, lo)) of d = sdf_sum / weight.  The hit is the
+ *   first k with samples k - 1 and k defined, f_{k-1} >= 0 and f_k < 0: depth = fma(step, f_{k-1} / (f_{k-1} - f_k),
+ *   t_{k-1}); a pair with f_{k-1} < 0 <= f_k ends the ray without a hit; an undefined sample resets the pair.  At the hit
+ *   point, if its cell is defined: weight_out = the interpolant of weight, colors = that of color_sum / weight, normals =
+ *   the normalised analytic gradient of the interpolant of d (world frame, pointing to free space; (0,0,0) where its
+ *   length is 0 or not finite).  A pixel without a hit gets zeros in all four maps; every pixel is written once.
+ *   depth (V,rows,cols)  normals (V,3,rows,cols)  colors (V,3,rows,cols) with color_sum, or both NULL
+ *   weight_out (V,rows,cols)
+ *   workspace: mvsn_tsdf_raycast_workspace_bytes(nx, ny, nz) bytes (0 for dims the entry refuses), 16-byte aligned: 4
+ *     bytes per voxel, the plane d with a NaN at an unobserved voxel, written by the first of the two launches.
+ *   MVSN_E_TOOLARGE when voxel_size |(nx-1,ny-1,nz-1)| / step + 2, the most samples a ray holds inside the box, is
+ *   above 2^20.  That count takes T_cam_in_world to be rigid (an orthonormal rotation part, so that depth grows no
+ *   faster than metric length); it also bounds the march, so under a T that shrinks lengths the samples of a ray
+ *   behind that count are not examined.  Nothing outside the planes is read; no atomics: the outputs are bitwise reproducible, and a view's maps
+ *   do not depend on the other views of the call.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_tsdf_raycast_workspace_bytes(int nx, int ny, int nz);
+int mvsn_tsdf_raycast(const float *sdf_sum, const float *weight, const float *color_sum, int nx, int ny, int nz,
+                      float voxel_size, float origin_x, float origin_y, float origin_z, const float *K,
+                      const float *T_cam_in_world, int n_views, int rows, int cols, float min_weight, float min_depth,
+                      float max_depth, float step, void *workspace, size_t workspace_bytes, float *depth,
+                      float *normals, float *colors, float *weight_out, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -1,11 +1,13 @@
-"""A dense TSDF volume on the device: posed depth maps integrated along their viewing rays, and a triangle mesh taken
+"""A dense TSDF volume on the device: posed depth maps integrated along their viewing rays, a triangle mesh taken
 from the volume by Surface Nets (DESIGN.md section 15 states the semantics, every fp32 step and the error bounds; the
-kernels are csrc/mvsn_tsdf.hip).
+kernels are csrc/mvsn_tsdf.hip), and depth, normal, colour and weight maps of its surface ray-cast from any pose (section
+16, csrc/mvsn_tsdf_raycast.hip).
 
 Where ``fusion.fuse_depthmaps`` keeps or drops pixels, the volume averages: every voxel holds the weighted sum of the
 truncated signed distances the views saw at it, so a surface that k views saw is in the result once, free space is
 carved, and the gaps between pixels are filled.  ``TSDFVolume.integrate`` adds views, ``extract_mesh`` gives vertices
-with normals and colours and the triangles between them, and ``fusion.write_ply(..., faces=)`` saves them.
+with normals and colours and the triangles between them, ``fusion.write_ply(..., faces=)`` saves them, and ``raycast``
+renders the surface as a camera sees it.
 
 Conventions are ``fusion``'s: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world``
 (V,4,4) maps camera coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel
@@ -21,6 +23,7 @@ from .fusion import _check_frames, _check_views, _origin_f32, _positive_f32
 
 MAX_VOXELS = 2 ** 31 - 1
 MAX_EXTENT = 2 ** 24                 # voxels along an axis, rows and columns of a map: every index is an exact float32
+MAX_RAY_SAMPLES = 2 ** 20            # samples of one ray inside the volume's box
 
 
 class TSDFMesh(NamedTuple):
@@ -29,6 +32,13 @@ class TSDFMesh(NamedTuple):
     colors: Optional[torch.Tensor]   # (M,3) uint8, or None for a volume without colour
     faces: torch.Tensor              # (F,3) int64 rows of `vertices`, counter-clockwise seen from the outside
     cell: torch.Tensor               # (M,) int64: the cell's linear index (k * Ny + j) * Nx + i, ascending
+
+
+class TSDFRender(NamedTuple):
+    depth: torch.Tensor              # (V,1,H,W) fp32 z-depth of the hit in the rendering camera, 0 without a hit
+    normals: torch.Tensor            # (V,3,H,W) fp32 unit vectors in the world frame, pointing outwards, or (0,0,0)
+    colors: Optional[torch.Tensor]   # (V,3,H,W) fp32 in the range of `images`, or None for a volume without colour
+    weight: torch.Tensor             # (V,1,H,W) fp32 interpolated weight at the hit, 0 without one
 
 
 class TSDFVolume:
@@ -134,11 +144,27 @@ class TSDFVolume:
         synchronisation is the read of the two counts that size the outputs."""
         return extract_mesh(self.sdf_sum, self.weight, self.color_sum, self.voxel_size, self.origin, min_weight)
 
+    def raycast(self, K: torch.Tensor, T_cam_in_world: torch.Tensor, size: Sequence[int], *, min_weight: float = 1.0,
+                min_depth: float = 0.0, max_depth: Optional[float] = None, step: Optional[float] = None) -> TSDFRender:
+        """The surface of the volume as cameras (``K``, ``T_cam_in_world``) (V,4,4) see it, in maps of ``size`` = (H, W):
+        ``depth`` is the z-depth in the rendering camera (what ``integrate`` consumes), ``normals`` the unit gradient of
+        the interpolated values in the world frame (outwards, as the mesh's), ``colors`` the interpolated
+        ``color_sum / weight`` and ``weight`` the interpolated weight; a pixel without a hit holds zeros in all of them.
+        The ray of a pixel is sampled at the depths k * ``step``, k = 1, 2, ..., inside (``min_depth``, ``max_depth``]
+        (``step`` None: min(voxel_size, trunc / 4); ``max_depth`` None: no far limit); a sample is defined where the 8
+        voxels around it have ``weight >= min_weight`` and its value is their trilinear interpolant; the hit is the
+        first change from >= 0 to < 0 between two consecutive defined samples, placed by linear interpolation; a change
+        from < 0 to >= 0 (a surface seen from behind) ends the ray.  Bitwise reproducible, a view's maps do not depend on
+        the other views of the call, no host synchronisation.  DESIGN.md section 16 has every fp32 step."""
+        if step is None:
+            with np.errstate(all="ignore"):
+                step = min(self.voxel_size, self.trunc / np.float32(4))
+        return raycast(self.sdf_sum, self.weight, self.color_sum, self.voxel_size, self.origin, K, T_cam_in_world, size,
+                       min_weight=min_weight, min_depth=min_depth, max_depth=max_depth, step=step)
 
-def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[torch.Tensor], voxel_size: float,
-                 origin: Sequence[float], min_weight: float = 1.0) -> TSDFMesh:
-    """``TSDFVolume.extract_mesh`` on state tensors of any origin: ``sdf_sum`` and ``weight`` (Nz,Ny,Nx) fp32,
-    ``color_sum`` (3,Nz,Ny,Nx) fp32 or None."""
+
+def _check_state(sdf_sum, weight, color_sum):
+    """ValueError unless the three are state tensors of one volume on one device; returns (nx, ny, nz, device)."""
     if not torch.is_tensor(sdf_sum) or sdf_sum.dim() != 3 or sdf_sum.dtype != torch.float32:
         raise ValueError("sdf_sum must be a (Nz,Ny,Nx) float32 tensor")
     nz, ny, nx = (int(x) for x in sdf_sum.shape)
@@ -154,6 +180,14 @@ def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optiona
             raise ValueError(f"color_sum is on {color_sum.device}, sdf_sum on {dev}")
     if nx * ny * nz > MAX_VOXELS or max(nx, ny, nz) > MAX_EXTENT:
         raise ValueError(f"at most 2^31 - 1 voxels and 2^24 along an axis, got {nx} x {ny} x {nz}")
+    return nx, ny, nz, dev
+
+
+def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[torch.Tensor], voxel_size: float,
+                 origin: Sequence[float], min_weight: float = 1.0) -> TSDFMesh:
+    """``TSDFVolume.extract_mesh`` on state tensors of any origin: ``sdf_sum`` and ``weight`` (Nz,Ny,Nx) fp32,
+    ``color_sum`` (3,Nz,Ny,Nx) fp32 or None."""
+    nx, ny, nz, dev = _check_state(sdf_sum, weight, color_sum)
     v = _positive_f32(voxel_size, "voxel_size")[0]
     mw = _positive_f32(min_weight, "min_weight")[0]
     o = _origin_f32(origin)
@@ -189,4 +223,77 @@ def extract_mesh(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optiona
                                             m, quads, _native.ptr(out.vertices), _native.ptr(out.normals),
                                             _native.ptr(out.colors), _native.ptr(out.faces), _native.ptr(out.cell), st),
                       "mvsn_tsdf_extract")
+    return out
+
+
+def raycast(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[torch.Tensor], voxel_size: float,
+            origin: Sequence[float], K: torch.Tensor, T_cam_in_world: torch.Tensor, size: Sequence[int], *,
+            min_weight: float = 1.0, min_depth: float = 0.0, max_depth: Optional[float] = None,
+            step: Optional[float] = None) -> TSDFRender:
+    """``TSDFVolume.raycast`` on state tensors of any origin (``extract_mesh``'s).  ``step`` None: ``voxel_size``."""
+    nx, ny, nz, dev = _check_state(sdf_sum, weight, color_sum)
+    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+        if not torch.is_tensor(m) or m.dim() != 3 or tuple(m.shape[1:]) != (4, 4) or m.shape[0] != K.shape[0]:
+            raise ValueError(f"{name} must be a (V,4,4) tensor" + ("" if m is K else " like K"))
+        if not m.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {m.dtype}")
+        if m.device != dev:
+            raise ValueError(f"{name} is on {m.device}, the volume on {dev}")
+    V = int(K.shape[0])
+    if V < 1:
+        raise ValueError("K must hold at least one view")
+    try:
+        H, W = (int(x) for x in size)
+        if any(x != y or isinstance(y, bool) for x, y in zip((H, W), size)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be two integers (H, W), got {size!r}") from None
+    if H < 1 or W < 1:
+        raise ValueError(f"size must be at least 1 x 1, got {H} x {W}")
+    if V > 65535 or H * W > 2 ** 31 - 1 or max(H, W) > MAX_EXTENT:
+        raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
+    v = _positive_f32(voxel_size, "voxel_size")[0]
+    mw = _positive_f32(min_weight, "min_weight")[0]
+    st = _positive_f32(v if step is None else step, "step")[0]
+    o = _origin_f32(origin)
+    with np.errstate(all="ignore"):
+        try:
+            lo = np.float32(min_depth)
+            hi = np.float32(np.inf if max_depth is None else max_depth)
+        except (TypeError, ValueError):
+            raise ValueError(f"min_depth and max_depth must be numbers, got {min_depth!r} and {max_depth!r}") from None
+    if not np.isfinite(lo):
+        raise ValueError(f"min_depth must be a finite number, got {min_depth!r}")
+    if (max_depth is not None and not np.isfinite(hi)) or not hi > lo:
+        raise ValueError(f"max_depth must be a finite number above min_depth = {lo}, or None, got {max_depth!r}")
+    # no ray holds more samples inside the box: its length in depth is at most its metric length, at most the diagonal
+    samples = float(v) * float(np.sqrt(float((nx - 1) ** 2 + (ny - 1) ** 2 + (nz - 1) ** 2))) / float(st) + 2.0
+    if samples > MAX_RAY_SAMPLES:
+        raise ValueError(f"a ray can hold {samples:.0f} samples inside the volume, at most 2^20: choose a larger step "
+                         f"than {st}")
+
+    def maps(make):
+        return TSDFRender(make((V, 1, H, W), dtype=torch.float32, device=dev),
+                          make((V, 3, H, W), dtype=torch.float32, device=dev),
+                          make((V, 3, H, W), dtype=torch.float32, device=dev) if color_sum is not None else None,
+                          make((V, 1, H, W), dtype=torch.float32, device=dev))
+    if min(nx, ny, nz) < 2:            # no cell, no sample is ever defined, nothing to launch
+        return maps(torch.zeros)
+    if not sdf_sum.is_cuda:
+        raise RuntimeError("raycast runs on HIP devices only: make the volume on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, w = sdf_sum.detach().contiguous(), weight.detach().contiguous()
+    c = color_sum.detach().contiguous() if color_sum is not None else None
+    # (held in names until the launch is queued: a converted copy must not be freed and its block handed out again)
+    K32, T32 = (t.detach().to(torch.float32).contiguous() for t in (K, T_cam_in_world))
+    ws_bytes = lib.mvsn_tsdf_raycast_workspace_bytes(nx, ny, nz)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = maps(torch.empty)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_tsdf_raycast(
+            _native.ptr(s), _native.ptr(w), _native.ptr(c), nx, ny, nz, float(v), float(o[0]), float(o[1]), float(o[2]),
+            _native.ptr(K32), _native.ptr(T32), V, H, W, float(mw), float(lo), float(hi), float(st),
+            _native.ptr(ws), ws_bytes, _native.ptr(out.depth), _native.ptr(out.normals), _native.ptr(out.colors),
+            _native.ptr(out.weight), _native.stream()), "mvsn_tsdf_raycast")
     return out

@@ -27,7 +27,12 @@ device (projection, nearest gather, masked accumulate, a view at a time), the by
 once, written once) over its time as a share of STREAMING_BYTES_PER_S (the 6.3 TB/s a streaming kernel reaches on this
 device) and of DEPTH_NORMALS_BYTES_PER_S (the 2.95 TB/s depth_normals_kernel reached), ms per extract_mesh call with M and F, and the
 mesh vertices scored by metrics.cloud_metrics against the fused cloud of the true depths (points on the analytic
-surfaces; threshold one voxel)."""
+surfaces; threshold one voxel).  --raycast: also renders that volume (with colour) back into the scene's V input views
+(TSDFVolume.raycast at the default step, one voxel) and reports, as "raycast", ms per call, the share of pixels with a
+hit, the ms of a call of one pixel (the preparation pass that every call pays, whatever V is), how far the rendered depth
+is from the input depth, and the same fixed-step march for depth alone composed from torch ops (grid_sample on values(),
+one step of all rays at a time) on the first TORCH_RAYCAST_VIEWS views, with the share of the samples inside the box that
+were not defined."""
 import argparse
 import json
 import os
@@ -284,7 +289,87 @@ def run_tsdf(sc, res, steps, warmup):
     return {"tsdf": out}
 
 
-def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False):
+TORCH_RAYCAST_VIEWS = 4
+
+
+def torch_raycast(vol, K, T, size, step):
+    """The march for depth alone from torch ops: every ray of every view advanced one step at a time through
+    grid_sample on values() (trilinear, a NaN where a corner is unobserved), every intermediate a (V,H,W) tensor in
+    HBM.  Returns (depth (V,H,W), samples inside the box, undefined ones among them)."""
+    import torch.nn.functional as F
+    H, W = size
+    dev = K.device
+    nx, ny, nz = vol.dims
+    vs = float(vol.voxel_size)
+    o = torch.tensor([float(x) for x in vol.origin], dtype=torch.float64, device=dev)
+    A = (T[:, :3, :3].double() @ torch.linalg.inv(K[:, :3, :3].double()) / vs).float()
+    g0 = ((T[:, :3, 3].double() - o) / vs).float()
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32),
+                            torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    dirs = torch.einsum("vij,hwj->vhwi", A, torch.stack([xs, ys, torch.ones_like(xs)], -1))
+    g0 = g0[:, None, None, :]
+    values = vol.values()[None, None]
+    top = torch.tensor([nx - 1, ny - 1, nz - 1], dtype=torch.float32, device=dev)
+    # the depths of the box: between the camera z of its corners
+    corners = torch.tensor([[i, j, k] for i in (0, nx - 1) for j in (0, ny - 1) for k in (0, nz - 1)],
+                           dtype=torch.float64, device=dev) * vs + o
+    z = torch.einsum("vj,cvj->vc", T[:, :3, 2].double(), corners[:, None, :] - T[None, :, :3, 3].double())
+    k0, k1 = max(1, int(z.min() / step) - 1), int(z.max() / step) + 2
+    shape = dirs.shape[:3]
+    f_prev = torch.full(shape, float("nan"), device=dev)
+    alive = torch.ones(shape, dtype=torch.bool, device=dev)
+    depth = torch.zeros(shape, device=dev)
+    inside_n = torch.zeros((), dtype=torch.int64, device=dev)
+    undefined_n = torch.zeros((), dtype=torch.int64, device=dev)
+    t_prev = 0.0
+    for k in range(k0, k1 + 1):
+        t = float(np.float32(k) * np.float32(step))
+        g = t * dirs + g0
+        inside = ((g >= 0) & (g < top)).all(-1)
+        f = F.grid_sample(values, (2 * g / top - 1)[None], mode="bilinear", padding_mode="border", align_corners=True)[0, 0]
+        f = torch.where(inside, f, torch.full_like(f, float("nan")))
+        inside_n += (alive & inside).sum()
+        undefined_n += (alive & inside & torch.isnan(f)).sum()
+        hit = alive & (f_prev >= 0) & (f < 0)
+        depth = torch.where(hit, t_prev + step * f_prev / (f_prev - f), depth)
+        alive &= ~(hit | ((f_prev < 0) & (f >= 0)))
+        f_prev, t_prev = f, t
+    return depth, inside_n, undefined_n
+
+
+def run_raycast(sc, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    V, _, H, W = depth.shape
+    trunc = 4 * TSDF_VOXEL
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, trunc, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    step = float(min(vol.voxel_size, vol.trunc / np.float32(4)))
+    r, times = timed(lambda: vol.raycast(K, T, (H, W)), steps, warmup)
+    _, ptimes = timed(lambda: vol.raycast(K[:1], T[:1], (1, 1)), steps, warmup)
+    hit = r.depth > 0
+    both = hit & (depth > 0)
+    diff = (r.depth - depth).abs()[both]
+    sub = min(V, TORCH_RAYCAST_VIEWS)
+    (tdepth, inside_n, undefined_n), ttimes = timed(lambda: torch_raycast(vol, K[:sub], T[:sub], (H, W), step), 2, 1)
+    thit = tdepth > 0
+    same = thit == hit[:sub, 0]
+    tboth = thit & hit[:sub, 0]
+    return {"raycast": {
+        "dims": list(TSDF_DIMS), "voxel_size": TSDF_VOXEL, "step": step, "views": V, "rays": V * H * W,
+        "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+        "ns_per_ray_at_mean": 1e6 * float(np.mean(times)) / (V * H * W),
+        "one_pixel_call_ms_mean": float(np.mean(ptimes)), "one_pixel_call_ms_min": float(np.min(ptimes)),
+        "preparation_share_of_call": float(np.mean(ptimes)) / float(np.mean(times)),
+        "hit_share": float(hit.float().mean()), "defined_hit_share": float((r.weight > 0).float().mean()),
+        "abs_rendered_minus_input_depth_median": float(diff.median()), "abs_rendered_minus_input_depth_max": float(diff.max()),
+        "torch_views": sub, "torch_ms_per_call_mean": float(np.mean(ttimes)), "torch_ms_per_call_min": float(np.min(ttimes)),
+        "torch_ms_per_call_all_views": float(np.mean(ttimes)) * V / sub,
+        "torch_hit_mask_agreement": float(same.float().mean()),
+        "torch_depth_difference_max": float((tdepth - r.depth[:sub, 0]).abs()[tboth].max()) if bool(tboth.any()) else 0.0,
+        "samples_inside_box_undefined_share": float(undefined_n) / max(int(inside_n), 1)}}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -303,7 +388,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     oriented = run_normals(sc, res, steps, warmup) if normals else {}
     scored = run_cloud(sc, nb, res, steps, warmup) if cloud else {}
     volume = run_tsdf(sc, res, steps, warmup) if tsdf else {}
-    return {**gated, **merged, **oriented, **scored, **volume, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    rendered = run_raycast(sc, steps, warmup) if raycast else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -322,11 +408,13 @@ def main():
                     help="also score a perturbed fusion against the true one (cloud_metrics) and time cloud_nearest")
     ap.add_argument("--tsdf", action="store_true",
                     help="also integrate the views into a 256^3 TSDF volume, extract its mesh and score it")
+    ap.add_argument("--raycast", action="store_true",
+                    help="also render the TSDF volume back into the input views (raycast), and the torch form of the march")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf)), flush=True)
+                             a.tsdf, a.raycast)), flush=True)
 
 
 if __name__ == "__main__":
