@@ -755,6 +755,46 @@ int mvsn_tsdf_raycast(const float *sdf_sum, const float *weight, const float *co
                       float max_depth, float step, void *workspace, size_t workspace_bytes, float *depth,
                       float *normals, float *colors, float *weight_out, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Alignment of depth maps to the TSDF volume: Gauss-Newton on the point-to-TSDF residual (tsdf.TSDFVolume.align; the
+ * semantics, every fp32 step and the error bounds are DESIGN.md section 17).  The state, K, T_cam_in_world and the limits
+ * are mvsn_tsdf_raycast's; depth (V,rows,cols) fp32, valid (V,rows,cols) bytes or NULL, weights (V,rows,cols) fp32 or
+ * NULL; 1 <= stride <= 2^24: the pixels with x % stride == 0 and y % stride == 0 are looked at.
+ * Per view the camera A, g0 of the ray-cast from the current fp64 pose; per pixel with depth D the grid point
+ *   g = fma(D, dir, g0), its cell, fractions, trilinear value f and analytic gradient as in the ray-cast.  The pixel
+ *   takes part iff D is finite and > 0, valid is set, its weight w (1 without weights) is finite and > 0, the cell is in
+ *   range with its 8 corners at weight >= min_weight, |f| <= band and n = gradient / voxel_size is finite.  Then
+ *   r = f / voxel_size, q = g - (N - 1) / 2, J = (n, q x n) in fp32, and in fp64 H = sum w J J^T, b = sum w J r, sum w,
+ *   sum w r^2 and the count, summed in an order the launch geometry fixes (no atomics: bitwise reproducible, and a view's
+ *   results do not depend on the other views).
+ * mvsn_tsdf_align_system evaluates that once at T_cam_in_world:
+ *   H (V,6,6), b (V,6), sums (V,3) = (count, sum w, sum w r^2), all fp64; residual (V,rows,cols) fp32 or NULL: r where
+ *   the pixel takes part, NaN elsewhere, every pixel written once.
+ * mvsn_tsdf_align iterates: iterations (0 to 1000) times, per view: stop with status 1 if count < min_pixels; scale H to
+ *   a unit diagonal and take its Cholesky factor, stop with status 2 at a diagonal entry that is not a positive finite
+ *   number or a pivot < min_pivot (inside (0, 1)); solve H (v, omega) = -b and apply R <- exp([omega]x) R,
+ *   t <- exp([omega]x) (t - cw) + cw + voxel_size v about the volume's centre cw.  A stopped view keeps its pose.
+ *   T_out (V,4,4) fp32: the final poses, each number rounded once from the fp64 pose, T_cam_in_world's bottom rows;
+ *   history (V,iterations+1,3) fp64: (count, sum w, sum w r^2) at the pose before update i, the last row at the final
+ *   pose; status (V) int32: 0, or what stopped the view; information (V,6,6) fp64: H at the final pose.
+ *   The launches: the values pass once, then iterations + 1 times the sums and their reduction per view, which solves
+ *   in all but the last.  Nothing waits on another workgroup and nothing is read on the host.
+ * workspace: mvsn_tsdf_align_workspace_bytes(nx, ny, nz, n_views, rows, cols, stride) bytes (0 for what the entries
+ *   refuse), 16-byte aligned: the plane d, the fp64 poses and a record of 30 doubles per workgroup.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_tsdf_align_workspace_bytes(int nx, int ny, int nz, int n_views, int rows, int cols, int stride);
+int mvsn_tsdf_align_system(const float *sdf_sum, const float *weight, int nx, int ny, int nz, float voxel_size,
+                           float origin_x, float origin_y, float origin_z, const float *depth, const uint8_t *valid,
+                           const float *weights, const float *K, const float *T_cam_in_world, int n_views, int rows,
+                           int cols, int stride, float min_weight, float band, void *workspace, size_t workspace_bytes,
+                           double *H, double *b, double *sums, float *residual, mvsn_stream_t stream);
+int mvsn_tsdf_align(const float *sdf_sum, const float *weight, int nx, int ny, int nz, float voxel_size, float origin_x,
+                    float origin_y, float origin_z, const float *depth, const uint8_t *valid, const float *weights,
+                    const float *K, const float *T_cam_in_world, int n_views, int rows, int cols, int stride,
+                    float min_weight, float band, int iterations, long min_pixels, double min_pivot, void *workspace,
+                    size_t workspace_bytes, float *T_out, double *history, int *status, double *information,
+                    mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -18,18 +18,11 @@
 // Contraction is off for the whole file: every fused multiply-add of section 16 is written as fmaf, every other step
 // is one fp32 operation.
 #pragma clang fp contract(off)
-#include <math.h>
-
-#include "mvsn_common.h"
-#include "mvsn_geom.h"
+#include "mvsn_tsdf_sample.h"
 
 namespace mvsn {
 
-constexpr int TR_THREADS = 256;
 constexpr int TR_TILE = 16;                             // pixels of a workgroup along each axis: 2 x 2 waves of 8 x 8
-constexpr int TR_VOX = 4;                               // voxels per thread of the values pass: one 16-byte access
-constexpr float TR_FLT_MAX = 3.4028234e38f;
-constexpr int TR_MAX_EXTENT = 1 << 24;                  // rows, cols, dims and k up to here: every index is an exact fp32
 constexpr long TR_MAX_SAMPLES = 1L << 20;               // samples of one ray inside the box
 constexpr int TR_SLACK = 8;                             // the clip's widening (2 x 2), its floor and ceil, and room
 
@@ -69,22 +62,6 @@ __device__ inline void raycast_camera(const float *K, const float *T, float voxe
                                 (double)T[a * 4 + 2] * Ki[6 + b]) / vs);
     out[9 + a] = (float)(((double)T[a * 4 + 3] - o[a]) / vs);
   }
-}
-
-// the 8 values of the cell whose lowest corner is at `at`: v[c], c = dx + 2 dy + 4 dz (the compiler fetches each
-// x-adjacent pair with one 8-byte load: four loads per cell)
-__device__ __forceinline__ void cell_load(const float *__restrict__ p, long at, long nx, long nxy, float *v) {
-  v[0] = p[at], v[1] = p[at + 1], v[2] = p[at + nx], v[3] = p[at + nx + 1];
-  v[4] = p[at + nxy], v[5] = p[at + nxy + 1], v[6] = p[at + nxy + nx], v[7] = p[at + nxy + nx + 1];
-}
-
-__device__ __forceinline__ float lerp(float fr, float lo, float hi) { return fmaf(fr, hi - lo, lo); }
-
-// the trilinear interpolant: along x, then y, then z
-__device__ __forceinline__ float trilinear(const float *v, float fx, float fy, float fz) {
-  const float x00 = lerp(fx, v[0], v[1]), x10 = lerp(fx, v[2], v[3]);
-  const float x01 = lerp(fx, v[4], v[5]), x11 = lerp(fx, v[6], v[7]);
-  return lerp(fz, lerp(fy, x00, x10), lerp(fy, x01, x11));
 }
 
 template <bool COLOR>
@@ -181,11 +158,8 @@ __global__ __launch_bounds__(TR_THREADS) void tsdf_raycast_kernel(
       cell_load(sdf_sum, at, lnx, nxy, v);
 #pragma unroll
       for (int c = 0; c < 8; ++c) v[c] = v[c] / w[c];
-      // the gradient of the trilinear interpolant: per axis the bilinear interpolant of the four differences along it
-      const float grad[3] = {
-          lerp(fz, lerp(fy, v[1] - v[0], v[3] - v[2]), lerp(fy, v[5] - v[4], v[7] - v[6])),
-          lerp(fz, lerp(fx, v[2] - v[0], v[3] - v[1]), lerp(fx, v[6] - v[4], v[7] - v[5])),
-          lerp(fy, lerp(fx, v[4] - v[0], v[5] - v[1]), lerp(fx, v[6] - v[2], v[7] - v[3]))};
+      float grad[3];
+      trilinear_gradient(v, fx, fy, fz, grad);
       const float len = sqrtf(fmaf(grad[0], grad[0], fmaf(grad[1], grad[1], grad[2] * grad[2])));
       const bool unit = len > 0.0f && len <= TR_FLT_MAX;
 #pragma unroll
@@ -213,13 +187,6 @@ __global__ __launch_bounds__(TR_THREADS) void tsdf_raycast_kernel(
     if (COLOR) colors[((size_t)view * 3 + m) * P + pix] = out_c[m];
   }
 }
-
-inline bool raycast_dims_ok(int nx, int ny, int nz) {
-  return nx > 0 && ny > 0 && nz > 0 && nx <= TR_MAX_EXTENT && ny <= TR_MAX_EXTENT && nz <= TR_MAX_EXTENT &&
-         (long)nx * ny <= 0x7fffffffL && (long)nx * ny * nz <= 0x7fffffffL;
-}
-
-inline bool raycast_positive(float x) { return x > 0.0f && x <= TR_FLT_MAX; }
 
 // no ray holds more samples inside the box than this: its length in depth is at most its metric length (the camera
 // ray's z component is 1), which is at most the box's diagonal

@@ -6,8 +6,9 @@ kernels are csrc/mvsn_tsdf.hip), and depth, normal, colour and weight maps of it
 Where ``fusion.fuse_depthmaps`` keeps or drops pixels, the volume averages: every voxel holds the weighted sum of the
 truncated signed distances the views saw at it, so a surface that k views saw is in the result once, free space is
 carved, and the gaps between pixels are filled.  ``TSDFVolume.integrate`` adds views, ``extract_mesh`` gives vertices
-with normals and colours and the triangles between them, ``fusion.write_ply(..., faces=)`` saves them, and ``raycast``
-renders the surface as a camera sees it.
+with normals and colours and the triangles between them, ``fusion.write_ply(..., faces=)`` saves them, ``raycast``
+renders the surface as a camera sees it, and ``align`` refines the poses of depth maps against it (section 17,
+csrc/mvsn_tsdf_align.hip).
 
 Conventions are ``fusion``'s: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world``
 (V,4,4) maps camera coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel
@@ -39,6 +40,13 @@ class TSDFRender(NamedTuple):
     normals: torch.Tensor            # (V,3,H,W) fp32 unit vectors in the world frame, pointing outwards, or (0,0,0)
     colors: Optional[torch.Tensor]   # (V,3,H,W) fp32 in the range of `images`, or None for a volume without colour
     weight: torch.Tensor             # (V,1,H,W) fp32 interpolated weight at the hit, 0 without one
+
+
+class TSDFAlignment(NamedTuple):
+    T_cam_in_world: torch.Tensor     # (V,4,4) fp32, the refined poses (each number rounded once from the fp64 pose)
+    history: torch.Tensor            # (V, iterations+1, 3) fp64: count, sum_w, sum_w_r2 at the pose BEFORE update i; the last row at the final pose
+    status: torch.Tensor             # (V,) int32: 0 ran all iterations, 1 stopped: fewer than min_pixels take part, 2 stopped: normal matrix not positive definite
+    information: torch.Tensor        # (V,6,6) fp64: the normal matrix at the final pose (its inverse is the pose covariance up to the noise scale)
 
 
 class TSDFVolume:
@@ -161,6 +169,32 @@ class TSDFVolume:
                 step = min(self.voxel_size, self.trunc / np.float32(4))
         return raycast(self.sdf_sum, self.weight, self.color_sum, self.voxel_size, self.origin, K, T_cam_in_world, size,
                        min_weight=min_weight, min_depth=min_depth, max_depth=max_depth, step=step)
+
+    def align(self, depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, *,
+              valid: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, min_weight: float = 1.0,
+              band: Optional[float] = None, iterations: int = 10, stride: int = 1, min_pixels: int = 6,
+              min_pivot: float = 1e-9) -> TSDFAlignment:
+        """Refine the poses ``T_cam_in_world`` (V,4,4) of the depth maps ``depth`` (V,1,H,W) fp32 against the volume:
+        Gauss-Newton on the point-to-TSDF residual, no data association and no render.  A pixel with depth D is the
+        point ``ray * D`` of its view; it takes part when it lies on the ``stride`` lattice (x % stride == 0 and
+        y % stride == 0), D is finite and > 0, ``valid`` is set, its weight w (``weights`` (V,1,H,W) fp32; 1 without) is
+        finite and > 0, the 8 voxels around the point have ``weight >= min_weight`` (``raycast``'s "defined"), the
+        trilinear value f there has |f| <= ``band`` and its gradient is finite.  The residual is r = f / voxel_size;
+        every iteration solves the 6 x 6 normal equations of sum w r^2 for a rigid update about the volume's centre and
+        applies it to the pose, which is carried in fp64.  A view stops, and keeps its pose, when fewer than
+        ``min_pixels`` pixels take part (status 1) or when the normal matrix, scaled to a unit diagonal, has a Cholesky
+        pivot below ``min_pivot`` (status 2: the scene does not constrain all six degrees of freedom); the remaining
+        rows of its ``history`` repeat.  ``band`` None is ``trunc / 2``: a default, not a measured constant -- values at
+        +-trunc are clamped and carry no gradient, so the band must stay inside the truncation.  ``iterations`` is an
+        integer in [0, 1000]; with 0 the result holds the float32 values of the input poses and one history row.  Every
+        view is aligned on its own; bitwise reproducible; everything is validated here, before any launch; no host
+        synchronisation whatever ``iterations`` is.  DESIGN.md section 17 has every step."""
+        if band is None:
+            with np.errstate(all="ignore"):
+                band = self.trunc / np.float32(2)
+        return align(self.sdf_sum, self.weight, self.voxel_size, self.origin, depth, K, T_cam_in_world, band=band,
+                     valid=valid, weights=weights, min_weight=min_weight, iterations=iterations, stride=stride,
+                     min_pixels=min_pixels, min_pivot=min_pivot)
 
 
 def _check_state(sdf_sum, weight, color_sum):
@@ -296,4 +330,124 @@ def raycast(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[tor
             _native.ptr(K32), _native.ptr(T32), V, H, W, float(mw), float(lo), float(hi), float(st),
             _native.ptr(ws), ws_bytes, _native.ptr(out.depth), _native.ptr(out.normals), _native.ptr(out.colors),
             _native.ptr(out.weight), _native.stream()), "mvsn_tsdf_raycast")
+    return out
+
+
+def _integer(value, name, lo, hi=None):
+    """``value`` as an int; ValueError unless it is an integer (not a bool) in [lo, hi]."""
+    try:
+        i = int(value)
+        if i != value or isinstance(value, bool):
+            raise TypeError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name} must be an integer, got {value!r}") from None
+    if i < lo or (hi is not None and i > hi):
+        raise ValueError(f"{name} must be an integer " + (f"in [{lo}, {hi}]" if hi is not None else f">= {lo}") + f", got {value!r}")
+    return i
+
+
+def _check_align(sdf_sum, weight, voxel_size, origin, depth, K, T_cam_in_world, valid, weights, min_weight, band, stride):
+    """The validation ``align`` and ``align_system`` share; returns the checked scalars and sizes."""
+    nx, ny, nz, dev = _check_state(sdf_sum, weight, None)
+
+    def limits(V, H, W, d):
+        if V > 65535 or H * W > 2 ** 31 - 1 or max(H, W) > MAX_EXTENT:
+            raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
+        if d != dev:
+            raise ValueError(f"depth is on {d}, the volume on {dev}")
+    V, H, W, _ = _check_views(depth, K, T_cam_in_world, limits=limits, floating=True)
+    if valid is not None:
+        _check_frames("valid", valid, V, H, W, 1, (torch.bool, torch.uint8), dev)
+    if weights is not None:
+        _check_frames("weights", weights, V, H, W, 1, (torch.float32,), dev)
+    v = _positive_f32(voxel_size, "voxel_size")[0]
+    mw = _positive_f32(min_weight, "min_weight")[0]
+    bd = _positive_f32(band, "band")[0]
+    o = _origin_f32(origin)
+    st = min(_integer(stride, "stride", 1), max(H, W))     # (a longer stride leaves pixel (0, 0), as max(H, W) does)
+    return nx, ny, nz, dev, V, H, W, v, mw, bd, o, st
+
+
+def _align_inputs(sdf_sum, weight, depth, K, T_cam_in_world, valid, weights):
+    # (held in names until the launches are queued: a converted copy must not be freed and its block handed out again)
+    return (sdf_sum.detach().contiguous(), weight.detach().contiguous(), depth.detach().contiguous(),
+            valid.detach().contiguous().view(torch.uint8) if valid is not None else None,
+            weights.detach().contiguous() if weights is not None else None,
+            K.detach().to(torch.float32).contiguous(), T_cam_in_world.detach().to(torch.float32).contiguous())
+
+
+def align_system(sdf_sum: torch.Tensor, weight: torch.Tensor, voxel_size: float, origin: Sequence[float],
+                 depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, *, band: float,
+                 valid: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, min_weight: float = 1.0,
+                 stride: int = 1, with_residual: bool = False):
+    """One evaluation of ``align``'s Gauss-Newton system at the float32 values of ``T_cam_in_world``, on state tensors
+    of any origin: ``(H (V,6,6) fp64, b (V,6) fp64, count (V,) int64, sum_w (V,) fp64, sum_w_r2 (V,) fp64, residual)``
+    with H = sum w J J^T, b = sum w J r over the pixels that take part, J = (n, q x n) the derivative of r with respect
+    to the update (v, omega) about the volume's centre, in voxel units.  ``residual`` (V,1,H,W) fp32, with
+    ``with_residual``, is r per pixel and NaN where the pixel does not take part; None without.  ``band`` is required
+    (the state has no ``trunc``).  What ``align`` iterates; the covariance of a pose is H^-1 times the noise scale."""
+    nx, ny, nz, dev, V, H, W, v, mw, bd, o, st = _check_align(sdf_sum, weight, voxel_size, origin, depth, K, T_cam_in_world,
+                                                               valid, weights, min_weight, band, stride)
+    f64 = dict(dtype=torch.float64, device=dev)
+    if min(nx, ny, nz) < 2:            # no cell, no point is ever defined, nothing to launch
+        res = torch.full((V, 1, H, W), float("nan"), dtype=torch.float32, device=dev) if with_residual else None
+        return (torch.zeros((V, 6, 6), **f64), torch.zeros((V, 6), **f64), torch.zeros((V,), dtype=torch.int64, device=dev),
+                torch.zeros((V,), **f64), torch.zeros((V,), **f64), res)
+    if not depth.is_cuda:
+        raise RuntimeError("align_system runs on HIP devices only: make the volume and the depth maps on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, w, d, vd, wt, K32, T32 = _align_inputs(sdf_sum, weight, depth, K, T_cam_in_world, valid, weights)
+    ws_bytes = lib.mvsn_tsdf_align_workspace_bytes(nx, ny, nz, V, H, W, st)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    Hm, b, sums = torch.empty((V, 6, 6), **f64), torch.empty((V, 6), **f64), torch.empty((V, 3), **f64)
+    res = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev) if with_residual else None
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_tsdf_align_system(
+            _native.ptr(s), _native.ptr(w), nx, ny, nz, float(v), float(o[0]), float(o[1]), float(o[2]), _native.ptr(d),
+            _native.ptr(vd), _native.ptr(wt), _native.ptr(K32), _native.ptr(T32), V, H, W, st, float(mw), float(bd),
+            _native.ptr(ws), ws_bytes, _native.ptr(Hm), _native.ptr(b), _native.ptr(sums), _native.ptr(res),
+            _native.stream()), "mvsn_tsdf_align_system")
+    dense = lambda t: t.clone(memory_format=torch.contiguous_format)   # noqa: E731  (unit strides for V = 1 too)
+    return Hm, b, dense(sums[:, 0]).to(torch.int64), dense(sums[:, 1]), dense(sums[:, 2]), res
+
+
+def align(sdf_sum: torch.Tensor, weight: torch.Tensor, voxel_size: float, origin: Sequence[float], depth: torch.Tensor,
+          K: torch.Tensor, T_cam_in_world: torch.Tensor, *, band: float, valid: Optional[torch.Tensor] = None,
+          weights: Optional[torch.Tensor] = None, min_weight: float = 1.0, iterations: int = 10, stride: int = 1,
+          min_pixels: int = 6, min_pivot: float = 1e-9) -> TSDFAlignment:
+    """``TSDFVolume.align`` on state tensors of any origin (``extract_mesh``'s).  ``band`` is required: the state has
+    no ``trunc``; keep it inside the truncation the state was integrated with."""
+    nx, ny, nz, dev, V, H, W, v, mw, bd, o, st = _check_align(sdf_sum, weight, voxel_size, origin, depth, K, T_cam_in_world,
+                                                               valid, weights, min_weight, band, stride)
+    it = _integer(iterations, "iterations", 0, 1000)
+    mp = _integer(min_pixels, "min_pixels", 1, 2 ** 62)
+    try:
+        pv = float(min_pivot)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_pivot must be a number inside (0, 1), got {min_pivot!r}") from None
+    if not 0.0 < pv < 1.0:
+        raise ValueError(f"min_pivot must be a number inside (0, 1), got {min_pivot!r}")
+    if min(nx, ny, nz) < 2:            # no cell, no point is ever defined, nothing to launch: every view stops at once
+        return TSDFAlignment(T_cam_in_world.detach().to(torch.float32).clone(),
+                             torch.zeros((V, it + 1, 3), dtype=torch.float64, device=dev),
+                             torch.ones((V,), dtype=torch.int32, device=dev),
+                             torch.zeros((V, 6, 6), dtype=torch.float64, device=dev))
+    if not depth.is_cuda:
+        raise RuntimeError("align runs on HIP devices only: make the volume and the depth maps on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, w, d, vd, wt, K32, T32 = _align_inputs(sdf_sum, weight, depth, K, T_cam_in_world, valid, weights)
+    ws_bytes = lib.mvsn_tsdf_align_workspace_bytes(nx, ny, nz, V, H, W, st)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = TSDFAlignment(torch.empty((V, 4, 4), dtype=torch.float32, device=dev),
+                        torch.empty((V, it + 1, 3), dtype=torch.float64, device=dev),
+                        torch.empty((V,), dtype=torch.int32, device=dev),
+                        torch.empty((V, 6, 6), dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_tsdf_align(
+            _native.ptr(s), _native.ptr(w), nx, ny, nz, float(v), float(o[0]), float(o[1]), float(o[2]), _native.ptr(d),
+            _native.ptr(vd), _native.ptr(wt), _native.ptr(K32), _native.ptr(T32), V, H, W, st, float(mw), float(bd), it, mp,
+            pv, _native.ptr(ws), ws_bytes, _native.ptr(out.T_cam_in_world), _native.ptr(out.history),
+            _native.ptr(out.status), _native.ptr(out.information), _native.stream()), "mvsn_tsdf_align")
     return out

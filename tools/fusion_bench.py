@@ -32,7 +32,11 @@ surfaces; threshold one voxel).  --raycast: also renders that volume (with colou
 hit, the ms of a call of one pixel (the preparation pass that every call pays, whatever V is), how far the rendered depth
 is from the input depth, and the same fixed-step march for depth alone composed from torch ops (grid_sample on values(),
 one step of all rays at a time) on the first TORCH_RAYCAST_VIEWS views, with the share of the samples inside the box that
-were not defined."""
+were not defined.  --align: also perturbs the scene's poses by a fixed seeded twist (ALIGN_SHIFT, ALIGN_ANGLE), aligns
+all V views against that volume (TSDFVolume.align, ALIGN_ITERATIONS iterations, the default band trunc / 2) and reports,
+as "align", ms per call and per iteration, the ms of a call with no iteration (the preparation pass and one evaluation),
+the pose errors before and after, the status counts, and one iteration (the evaluation of the 6 x 6 system and its solve)
+composed from torch ops on the first TORCH_ALIGN_VIEWS views."""
 import argparse
 import json
 import os
@@ -369,7 +373,123 @@ def run_raycast(sc, steps, warmup):
         "samples_inside_box_undefined_share": float(undefined_n) / max(int(inside_n), 1)}}
 
 
-def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False):
+TORCH_ALIGN_VIEWS = 4
+ALIGN_ITERATIONS = 10
+ALIGN_SHIFT = 0.02            # one voxel
+ALIGN_ANGLE = 0.004           # radians: 0.23 degrees
+
+
+def align_twists(V, device):
+    """T_cam_in_world <- [exp([w]x) R, t + s]: w of length ALIGN_ANGLE and s of length ALIGN_SHIFT in seeded directions."""
+    gen = torch.Generator().manual_seed(17)
+    w = torch.nn.functional.normalize(torch.randn(V, 3, generator=gen, dtype=torch.float64), dim=1) * ALIGN_ANGLE
+    s = torch.nn.functional.normalize(torch.randn(V, 3, generator=gen, dtype=torch.float64), dim=1) * ALIGN_SHIFT
+    Wx = torch.zeros(V, 3, 3, dtype=torch.float64)
+    Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0] = -w[:, 2], w[:, 1], w[:, 2]
+    Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 0], -w[:, 1], w[:, 0]
+    return torch.linalg.matrix_exp(Wx).to(device), s.to(device)
+
+
+def pose_errors(T, T_true):
+    """(translation distances, rotation angles) (V,) between poses, fp64."""
+    T, T_true = T.double(), T_true.double()
+    dR = T[:, :3, :3] @ T_true[:, :3, :3].transpose(1, 2)
+    cos = ((dR.diagonal(dim1=1, dim2=2).sum(1) - 1) / 2).clamp(-1, 1)
+    return (T[:, :3, 3] - T_true[:, :3, 3]).norm(dim=1), torch.acos(cos)
+
+
+def torch_align_iteration(vol, depth, K, T, band):
+    """One iteration from torch ops: the points, the 8 corners of their cells gathered from values(), the trilinear value
+    and gradient, J, the sums as einsums in fp64, a Cholesky solve and the update; every intermediate a (V,H,W) tensor
+    in HBM.  Returns (new poses (V,4,4) fp64, count (V,), sum w r^2 (V,))."""
+    dev = K.device
+    V, _, H, W = depth.shape
+    nx, ny, nz = vol.dims
+    vs = float(vol.voxel_size)
+    o = torch.tensor([float(x) for x in vol.origin], dtype=torch.float64, device=dev)
+    A = (T[:, :3, :3].double() @ torch.linalg.inv(K[:, :3, :3].double()) / vs).float()
+    g0 = ((T[:, :3, 3].double() - o) / vs).float()
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32),
+                            torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    dirs = torch.einsum("vij,hwj->vhwi", A, torch.stack([xs, ys, torch.ones_like(xs)], -1))
+    g = depth[:, 0, :, :, None] * dirs + g0[:, None, None, :]
+    c = torch.floor(g)
+    top = torch.tensor([nx - 2, ny - 2, nz - 2], dtype=torch.float32, device=dev)
+    ok = ((c >= 0) & (c <= top)).all(-1) & torch.isfinite(depth[:, 0]) & (depth[:, 0] > 0)
+    ci = torch.where(ok[..., None], c, torch.zeros_like(c)).long()
+    fr = g - c
+    d = vol.values().reshape(-1)
+    at = (ci[..., 2] * ny + ci[..., 1]) * nx + ci[..., 0]
+    v = [d[at + (k & 1) + ((k >> 1) & 1) * nx + (k >> 2) * nx * ny] for k in range(8)]
+    lerp = lambda f, a, b: a + f * (b - a)   # noqa: E731
+    fx, fy, fz = fr[..., 0], fr[..., 1], fr[..., 2]
+    f = lerp(fz, lerp(fy, lerp(fx, v[0], v[1]), lerp(fx, v[2], v[3])), lerp(fy, lerp(fx, v[4], v[5]), lerp(fx, v[6], v[7])))
+    n = torch.stack([lerp(fz, lerp(fy, v[1] - v[0], v[3] - v[2]), lerp(fy, v[5] - v[4], v[7] - v[6])),
+                     lerp(fz, lerp(fx, v[2] - v[0], v[3] - v[1]), lerp(fx, v[6] - v[4], v[7] - v[5])),
+                     lerp(fy, lerp(fx, v[4] - v[0], v[5] - v[1]), lerp(fx, v[6] - v[2], v[7] - v[3]))], -1) / vs
+    ok = ok & (f.abs() <= band) & torch.isfinite(n).all(-1)
+    c0 = torch.tensor([(nx - 1) / 2, (ny - 1) / 2, (nz - 1) / 2], dtype=torch.float32, device=dev)
+    J = torch.cat([n, torch.cross(g - c0, n, dim=-1)], -1)
+    J = torch.where(ok[..., None], J, torch.zeros_like(J)).double().reshape(V, -1, 6)
+    r = torch.where(ok, f / vs, torch.zeros_like(f)).double().reshape(V, -1)
+    Hm = torch.einsum("vpi,vpj->vij", J, J)
+    b = torch.einsum("vpi,vp->vi", J, r)
+    s = Hm.diagonal(dim1=1, dim2=2).rsqrt()
+    L = torch.linalg.cholesky_ex(Hm * s[:, :, None] * s[:, None, :]).L      # (no host read: a failed factor gives NaNs)
+    delta = torch.cholesky_solve(-(b * s)[..., None], L)[..., 0] * s
+    w = delta[:, 3:]
+    Wx = torch.zeros(V, 3, 3, dtype=torch.float64, device=dev)
+    Wx[:, 0, 1], Wx[:, 0, 2], Wx[:, 1, 0] = -w[:, 2], w[:, 1], w[:, 2]
+    Wx[:, 1, 2], Wx[:, 2, 0], Wx[:, 2, 1] = -w[:, 0], -w[:, 1], w[:, 0]
+    Rd = torch.linalg.matrix_exp(Wx)
+    cw = o + vs * c0.double()
+    out = T.double().clone()
+    out[:, :3, :3] = Rd @ out[:, :3, :3]
+    out[:, :3, 3] = torch.einsum("vij,vj->vi", Rd, T[:, :3, 3].double() - cw) + cw + vs * delta[:, :3]
+    return out, ok.reshape(V, -1).sum(1), (r * r).sum(1)
+
+
+def run_align(sc, steps, warmup):
+    depth, K, T = sc["depth"], sc["K"], sc["T_cam_in_world"]
+    V, _, H, W = depth.shape
+    trunc = 4 * TSDF_VOXEL
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, trunc, device=depth.device)
+    vol.integrate(depth, K, T)
+    Rd, shift = align_twists(V, depth.device)
+    off = T.double().clone()
+    off[:, :3, :3] = Rd @ off[:, :3, :3]
+    off[:, :3, 3] += shift
+    off = off.float()
+    r, times = timed(lambda: vol.align(depth, K, off, iterations=ALIGN_ITERATIONS), steps, warmup)
+    _, ztimes = timed(lambda: vol.align(depth, K, off, iterations=0), steps, warmup)
+    before, after = pose_errors(off, T), pose_errors(r.T_cam_in_world, T)
+    sub = min(V, TORCH_ALIGN_VIEWS)
+    band = float(vol.trunc / np.float32(2))
+    (tT, tcount, tcost), ttimes = timed(lambda: torch_align_iteration(vol, depth[:sub], K[:sub], off[:sub], band), 2, 1)
+    one = vol.align(depth[:sub], K[:sub], off[:sub], iterations=1)
+    per_iteration = (float(np.mean(times)) - float(np.mean(ztimes))) / ALIGN_ITERATIONS
+    hist = r.history
+    return {"align": {
+        "dims": list(TSDF_DIMS), "voxel_size": TSDF_VOXEL, "band": band, "views": V, "pixels": V * H * W,
+        "iterations": ALIGN_ITERATIONS, "shift": ALIGN_SHIFT, "angle": ALIGN_ANGLE,
+        "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+        "zero_iteration_call_ms_mean": float(np.mean(ztimes)), "ms_per_iteration": per_iteration,
+        "ns_per_pixel_and_iteration": 1e6 * per_iteration / (V * H * W),
+        "translation_error_before_mean": float(before[0].mean()), "translation_error_after_mean": float(after[0].mean()),
+        "translation_error_after_max": float(after[0].max()),
+        "rotation_error_before_mean": float(before[1].mean()), "rotation_error_after_mean": float(after[1].mean()),
+        "rotation_error_after_max": float(after[1].max()),
+        "status_counts": [int((r.status == k).sum()) for k in range(3)],
+        "share_of_pixels_taking_part_first_last": [float(hist[:, 0, 0].sum()) / (V * H * W), float(hist[:, -1, 0].sum()) / (V * H * W)],
+        "sum_w_r2_first_last": [float(hist[:, 0, 2].sum()), float(hist[:, -1, 2].sum())],
+        "torch_views": sub, "torch_ms_per_iteration_mean": float(np.mean(ttimes)), "torch_ms_per_iteration_min": float(np.min(ttimes)),
+        "torch_ms_per_iteration_all_views": float(np.mean(ttimes)) * V / sub,
+        "torch_count_equal": bool((tcount == one.history[:, 0, 0].long()).all()),
+        "torch_pose_difference_max": float((tT - one.T_cam_in_world.double()).abs().max())}}
+
+
+def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
+        align=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -389,7 +509,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     scored = run_cloud(sc, nb, res, steps, warmup) if cloud else {}
     volume = run_tsdf(sc, res, steps, warmup) if tsdf else {}
     rendered = run_raycast(sc, steps, warmup) if raycast else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    aligned = run_align(sc, steps, warmup) if align else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -410,11 +531,13 @@ def main():
                     help="also integrate the views into a 256^3 TSDF volume, extract its mesh and score it")
     ap.add_argument("--raycast", action="store_true",
                     help="also render the TSDF volume back into the input views (raycast), and the torch form of the march")
+    ap.add_argument("--align", action="store_true",
+                    help="also align the views from perturbed poses to the TSDF volume, and the torch form of one iteration")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast)), flush=True)
+                             a.tsdf, a.raycast, a.align)), flush=True)
 
 
 if __name__ == "__main__":
