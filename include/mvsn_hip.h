@@ -795,6 +795,54 @@ int mvsn_tsdf_align(const float *sdf_sum, const float *weight, int nx, int ny, i
                     size_t workspace_bytes, float *T_out, double *history, int *status, double *information,
                     mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected components of a triangle mesh, and the mesh of the components one keeps (multi_view_stereonet_amd/mesh.py:
+ * mesh_components, filter_mesh; the semantics, the termination and the visibility argument are DESIGN.md section 18).
+ * The graph has the n_vertices rows as nodes and the sides of the faces as edges; a face with an index outside
+ * [0, n_vertices) takes no part (label -1; the index is never used as an address); a vertex no face uses is a component
+ * of its own.  Component ids are dense and ordered by the component's lowest vertex row.
+ *   faces (n_faces,3) int64 (NULL with n_faces = 0)   1 <= n_vertices <= 2^31 - 1   0 <= n_faces <= 2^31 - 1
+ *   workspace: mvsn_mesh_workspace_bytes(n_vertices, n_faces) bytes (0 for sizes the entries refuse), 16-byte aligned:
+ *     a head of 16 bytes, 8 bytes per vertex (parent, and the root -> id map that mvsn_mesh_select reuses as the vertex
+ *     row map), 12 bytes per 256 vertices and per 256 faces.
+ * mvsn_mesh_components_label (init, hook, flatten, the scan and a 16-byte device copy): a lock-free union-find over
+ *   int32 `parent` in the workspace, one thread per face; a root is hooked under a lower root by a compare-and-swap, so
+ *   every walk descends and every loop is bounded by n_vertices, whatever the schedule.
+ *   -> result (2 int64): [0] the number of components C, [1] status bits (MVSN_MESH_STATUS_*; 0 = fine).  Reading the
+ *      two words back is the one host synchronisation of a labelling.
+ * mvsn_mesh_components_emit (three launches), on the workspace handed on unchanged, n_components = C as read back
+ *   (outside [1, n_vertices] it cannot be this workspace's: MVSN_E_BADARG):
+ *   -> vertex_label (n_vertices) int64   face_label (n_faces) int64: the label of the face's first index, or -1
+ *      vertex_count, face_count, first (C) int64: the sizes of every component and its lowest vertex row
+ * mvsn_mesh_select (count, the scan, rank, an 8-byte device copy): keep (C) bytes, non-zero = the component stays; the
+ *   labels as emitted (a label outside [0, C) is dropped).  Needs no labelling in the workspace, and overwrites its map.
+ *   -> result (2 int64): [0] the kept vertices M', [1] M' + the kept faces F'; the workspace holds the vertex row map
+ *      (int32, -1 for a dropped vertex).
+ * mvsn_mesh_compact (two launches; n_vertices_out = 0: none), on select's workspace, with M' and F' as read back:
+ *   vertices, normals (n_vertices,3) fp32, copied as bits; colors (n_vertices,3) u8 with out_colors, or both NULL;
+ *   cell (n_vertices) int64
+ *   -> the rows of the kept vertices and faces in their input order, out_faces renumbered through the row map;
+ *      vertex_rows (M'), face_rows (F') int64: the input row of every output row.
+ * Integer atomics only (a compare-and-swap on a root, relaxed loads and stores of parent, sums), no float arithmetic:
+ * every output is a deterministic function of the inputs, whatever order the faces come in.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_MESH_STATUS_WORKSPACE 1   /* a walk over `parent` ran out of its bound or met a parent above its vertex:
+                                          the workspace was overwritten during the call (cannot happen otherwise) */
+size_t mvsn_mesh_workspace_bytes(long n_vertices, long n_faces);
+int mvsn_mesh_components_label(const int64_t *faces, long n_vertices, long n_faces, int64_t *result, void *workspace,
+                               size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_components_emit(const int64_t *faces, long n_vertices, long n_faces, void *workspace,
+                              size_t workspace_bytes, long n_components, int64_t *vertex_label, int64_t *face_label,
+                              int64_t *vertex_count, int64_t *face_count, int64_t *first, mvsn_stream_t stream);
+int mvsn_mesh_select(const int64_t *vertex_label, const int64_t *face_label, const uint8_t *keep, long n_vertices,
+                     long n_faces, long n_components, int64_t *result, void *workspace, size_t workspace_bytes,
+                     mvsn_stream_t stream);
+int mvsn_mesh_compact(const float *vertices, const float *normals, const uint8_t *colors, const int64_t *cell,
+                      const int64_t *faces, const int64_t *face_label, const uint8_t *keep, long n_vertices, long n_faces,
+                      long n_components, const void *workspace, size_t workspace_bytes, long n_vertices_out,
+                      long n_faces_out, float *out_vertices, float *out_normals, uint8_t *out_colors, int64_t *out_cell,
+                      int64_t *out_faces, int64_t *vertex_rows, int64_t *face_rows, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

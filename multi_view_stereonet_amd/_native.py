@@ -143,6 +143,12 @@ SIGNATURES = {
                                [ctypes.c_float] * 2 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
     "mvsn_tsdf_align": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_float] * 4 + [c_void_p] * 5 + [c_int] * 4 +
                         [ctypes.c_float] * 2 + [c_int, c_long, ctypes.c_double, c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
+    "mvsn_mesh_workspace_bytes": (c_size_t, [c_long] * 2),
+    "mvsn_mesh_components_label": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_components_emit": (c_int, [c_void_p, c_long, c_long, c_void_p, c_size_t, c_long] + [c_void_p] * 5 + [c_void_p]),
+    "mvsn_mesh_select": (c_int, [c_void_p] * 3 + [c_long] * 3 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_compact": (c_int, [c_void_p] * 7 + [c_long] * 3 + [c_void_p, c_size_t, c_long, c_long] + [c_void_p] * 7 +
+                          [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

@@ -36,7 +36,11 @@ were not defined.  --align: also perturbs the scene's poses by a fixed seeded tw
 all V views against that volume (TSDFVolume.align, ALIGN_ITERATIONS iterations, the default band trunc / 2) and reports,
 as "align", ms per call and per iteration, the ms of a call with no iteration (the preparation pass and one evaluation),
 the pose errors before and after, the status counts, and one iteration (the evaluation of the 6 x 6 system and its solve)
-composed from torch ops on the first TORCH_ALIGN_VIEWS views."""
+composed from torch ops on the first TORCH_ALIGN_VIEWS views.  --mesh: also extracts the mesh of that volume (with colour)
+and reports, as "mesh", M, F, the number of components C and the largest one's share, ms per mesh_components call and per
+filter_mesh(min_faces=MESH_MIN_FACES) call (labelling included, and with the components handed in), and the labelling
+composed from torch ops -- scatter_reduce(amin) over the sides of the faces plus a pointer jump, repeated to a fixed point
+with a host read per round -- with its rounds and whether it finds the same partition."""
 import argparse
 import json
 import os
@@ -51,6 +55,7 @@ import torch  # noqa: E402
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, depth_normals,  # noqa: E402
                                              fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
+from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
@@ -488,8 +493,54 @@ def run_align(sc, steps, warmup):
         "torch_pose_difference_max": float((tT - one.T_cam_in_world.double()).abs().max())}}
 
 
+MESH_MIN_FACES = 200
+
+
+def torch_mesh_components(faces, m):
+    """The labelling from torch ops: every vertex takes the lowest label across the sides of its faces
+    (scatter_reduce amin), then one pointer jump, repeated to a fixed point with a host read per round (what a caller had
+    to write without mesh_components).  Returns (the lowest row of every vertex's component (m,), rounds)."""
+    u = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2]])
+    v = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0]])
+    label = torch.arange(m, dtype=torch.int64, device=faces.device)
+    rounds = 0
+    while True:
+        rounds += 1
+        new = label.scatter_reduce(0, u, label[v], "amin").scatter_reduce(0, v, label[u], "amin")
+        new = new[new]
+        if bool((new == label).all()):                      # the host read of the round
+            return label, rounds
+        label = new
+
+
+def run_mesh(sc, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, 4 * TSDF_VOXEL, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    mesh = vol.extract_mesh()
+    m, f = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    comp, times = timed(lambda: mesh_components(mesh.faces, m), steps, warmup)
+    clean, ftimes = timed(lambda: filter_mesh(mesh, min_faces=MESH_MIN_FACES), steps, warmup)
+    _, stimes = timed(lambda: filter_mesh(mesh, min_faces=MESH_MIN_FACES, components=comp), steps, warmup)
+    (tlabel, rounds), ttimes = timed(lambda: torch_mesh_components(mesh.faces, m), min(steps, 3), 1)
+    c = int(comp.first.shape[0])
+    return {"mesh": {
+        "dims": list(TSDF_DIMS), "voxel_size": TSDF_VOXEL, "M": m, "F": f, "C": c,
+        "largest_component_share_of_faces": float(comp.face_count.max()) / max(f, 1),
+        "largest_component_share_of_vertices": float(comp.vertex_count.max()) / max(m, 1),
+        "workspace_bytes": int(_native.load().mvsn_mesh_workspace_bytes(m, f)),
+        "components_ms_per_call_mean": float(np.mean(times)), "components_ms_per_call_min": float(np.min(times)),
+        "min_faces": MESH_MIN_FACES, "filter_ms_per_call_mean": float(np.mean(ftimes)),
+        "filter_ms_per_call_min": float(np.min(ftimes)),
+        "filter_with_components_handed_in_ms_mean": float(np.mean(stimes)),
+        "kept_components": int((comp.face_count >= MESH_MIN_FACES).sum()),
+        "kept_vertices": int(clean.mesh.vertices.shape[0]), "kept_faces": int(clean.mesh.faces.shape[0]),
+        "torch_ms_per_call_mean": float(np.mean(ttimes)), "torch_ms_per_call_min": float(np.min(ttimes)),
+        "torch_rounds": rounds, "torch_partition_equal": bool(torch.equal(tlabel, comp.first[comp.vertex_label]))}}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False):
+        align=False, mesh=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -510,7 +561,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     volume = run_tsdf(sc, res, steps, warmup) if tsdf else {}
     rendered = run_raycast(sc, steps, warmup) if raycast else {}
     aligned = run_align(sc, steps, warmup) if align else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    cleaned = run_mesh(sc, steps, warmup) if mesh else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -533,11 +585,13 @@ def main():
                     help="also render the TSDF volume back into the input views (raycast), and the torch form of the march")
     ap.add_argument("--align", action="store_true",
                     help="also align the views from perturbed poses to the TSDF volume, and the torch form of one iteration")
+    ap.add_argument("--mesh", action="store_true",
+                    help="also label the components of the volume's mesh and drop the small ones, and the torch form")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh)), flush=True)
 
 
 if __name__ == "__main__":
