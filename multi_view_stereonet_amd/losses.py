@@ -70,7 +70,9 @@ def get_occlusion_mask(K, T_right_in_left, left_idepthmap, left_invalid_mask, ri
 
 def left_right_idepthmap_consistency_losses(T_right_in_left, T_left_in_right, K_pyr, left_idepthmap_pyr: List[Optional[torch.Tensor]],
                                             left_occlusion_mask_pyr, right_idepthmap_pyr, right_occlusion_mask_pyr):
-    """Left/right geometric consistency between idepth pyramids: 0-dim tensor on the inputs' device."""
+    """Left/right geometric consistency between idepth pyramids: 0-dim tensor on the inputs' device.  With every level
+    None there is no input to name a device: a 0-dim zero on the CPU, for the float 0.0 the reference returns
+    (losses.py:116, 160)."""
     lib = _native.load()
     loss = None
     for lvl in range(len(left_idepthmap_pyr)):

@@ -3088,23 +3088,7 @@ def test_two_view_bidirectional_golden():
     assert loss.is_cuda and loss.dim() == 0    # (NaN when every pixel is occluded, as in the reference)
 
 
-def _project_f64(K, T_right_in_left, idepth):
-    """x' ~ K (R K^-1 [x y 1]^T / idepth + t), (R, t) = inverse(T_right_in_left), in float64 from first principles, with the
-    guards of the operation under test (depth = 1 / (idepth + 1e-6), idepth' = 1 / (z' + 1e-6), a divisor of z' + 1e-7;
-    stereo/image_predictor.py:538-576): normalised right-image coordinate (B,rows,cols,2), idepth' (B,1,rows,cols), and the
-    out-of-image mask |n| > 1."""
-    K, T, idp = K.cpu().double(), T_right_in_left.cpu().double(), idepth.cpu().double()
-    B, _, rows, cols = idp.shape
-    Tl, Ki = torch.linalg.inv(T), torch.linalg.inv(K[:, :3, :3])
-    ys, xs = torch.meshgrid(torch.arange(rows, dtype=torch.float64), torch.arange(cols, dtype=torch.float64), indexing="ij")
-    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(rows * cols, dtype=torch.float64)], 0)
-    X = (Ki @ pix) / (idp.reshape(B, 1, -1) + 1e-6)
-    Xr = Tl[:, :3, :3] @ X + Tl[:, :3, 3:4]
-    id_prime = (1.0 / (Xr[:, 2] + 1e-6)).view(B, 1, rows, cols)
-    cam = K[:, :3, :3] @ Xr
-    u, v = cam[:, 0] / (cam[:, 2] + 1e-7), cam[:, 1] / (cam[:, 2] + 1e-7)
-    uv = torch.stack([(u + 0.5) * 2.0 / cols - 1.0, (v + 0.5) * 2.0 / rows - 1.0], -1).view(B, rows, cols, 2)
-    return uv, id_prime, ((uv[..., 0].abs() > 1.0) | (uv[..., 1].abs() > 1.0)).unsqueeze(1)
+from consistency_reference import project as _project_f64   # noqa: E402  (the float64 projection: one place for both files)
 
 
 @pytest.mark.parametrize("rows,cols", [(131, 277), (96, 200)])
