@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MVSN_ABI_VERSION 6
+#define MVSN_ABI_VERSION 7
 
 #define MVSN_E_BADARG (-1)      /* null pointer, non-positive size, unsupported channel count */
 #define MVSN_E_TOOLARGE (-2)    /* shape exceeds what the kernel's LDS/global plan supports */
@@ -298,8 +298,8 @@ int mvsn_conv_forward(const mvsn_conv_desc *desc, const float *in, const float *
 int mvsn_conv_forward_blocks(const mvsn_conv_desc *desc, const float *const *in_blocks, const int *block_channels,
                              int num_blocks, const float *weight_packed, const float *bias, float *out,
                              float *out_partials, mvsn_stream_t stream);
-/* A normalise / activate / add pass handed over as a job: the arguments of mvsn_groupnorm_lrelu_apply (r_stats NULL,
- * residual optional) or of mvsn_groupnorm_lrelu_add2 (r_stats / r_gamma / r_beta set: the residual is a raw conv output). */
+/* A normalise / activate / add pass handed over as a job: the arguments of mvsn_groupnorm_lrelu_apply with finalised
+ * statistics (stat_tiles = 0). */
 typedef struct mvsn_apply_job {
   const float *x, *stats, *gamma, *beta;
   const float *residual, *r_stats, *r_gamma, *r_beta;
@@ -334,24 +334,18 @@ int mvsn_groupnorm_finalize(const float *partials, int n, int tiles, float *stat
 size_t mvsn_groupnorm_finalize_split_workspace_bytes(int n, int tiles);
 int mvsn_groupnorm_finalize_split(const float *partials, int n, int tiles, float *stats, void *workspace,
                                   size_t workspace_bytes, mvsn_stream_t stream);
-/* out = [residual +] LeakyReLU_0.2(GroupNorm(x)) on (N,32,spatial); residual may be NULL; out may alias x */
-int mvsn_groupnorm_lrelu_apply(const float *x, const float *stats, const float *gamma, const float *beta,
-                               const float *residual, int n, long spatial, float *out, mvsn_stream_t stream);
-/* out = LeakyReLU(GroupNorm(x)) + LeakyReLU(GroupNorm_r(r)): the first residual block of a refiner
- * (:472-474) when the head's activation x0 = LReLU(GN(conv0)) is never materialised -- conv0's raw output r
- * feeds block 1's convolution through mvsn_conv_forward's in_stats transform and this call as the residual. */
-int mvsn_groupnorm_lrelu_add2(const float *x, const float *stats, const float *gamma, const float *beta,
-                              const float *r, const float *r_stats, const float *r_gamma, const float *r_beta, int n,
-                              long spatial, float *out, mvsn_stream_t stream);
-/* mvsn_groupnorm_lrelu_apply / _add2 handed the producing convolution's RECORDS (N, tiles, 4, 3) instead of finalised
- * statistics: every workgroup of the pass forms x's (mean, rstd) itself with mvsn_groupnorm_finalize's own code (same
- * bits), so the dependent finalize launch in front of the pass disappears -- small batches, where that launch (7 us)
- * costs more than re-reading a few hundred records per workgroup.  r_stats NULL: plain pass (residual optional);
- * r_stats set (finalised, (N,4,2)): the _add2 form with the raw residual `residual`. */
-int mvsn_groupnorm_lrelu_apply_records(const float *x, const float *records, int tiles, const float *gamma,
-                                       const float *beta, const float *residual, const float *r_stats,
-                                       const float *r_gamma, const float *r_beta, int n, long spatial, float *out,
-                                       mvsn_stream_t stream);
+/* out = [residual +] LeakyReLU_0.2(GroupNorm(x)) on (N,32,spatial); out may alias x.
+ * stats: (N,4,2) finalised when stat_tiles == 0, else the producer's records (N,stat_tiles,4,3), finalised by every
+ * workgroup of the pass with mvsn_groupnorm_finalize's own code (same bits): the dependent finalize launch in front of
+ * the pass disappears -- small batches, where that launch (7 us) costs more than re-reading a few hundred records per
+ * workgroup.  mvsn_conv_to1_block takes its in_stats / stat_tiles the same way.
+ * residual optional; r_stats set: the residual is itself a raw convolution output (r_gamma, r_beta required), always
+ * finalised, out = LeakyReLU(GroupNorm(x)) + LeakyReLU(GroupNorm_r(residual)) -- the first residual block of a refiner
+ * (:472-474) when the head's activation x0 = LReLU(GN(conv0)) is never materialised: conv0's raw output feeds block 1's
+ * convolution through mvsn_conv_forward's in_stats transform and this call as the residual. */
+int mvsn_groupnorm_lrelu_apply(const float *x, const float *stats, int stat_tiles, const float *gamma, const float *beta,
+                               const float *residual, const float *r_stats, const float *r_gamma, const float *r_beta,
+                               int n, long spatial, float *out, mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 32 -> 1 channel 3x3 (kd = 1) or 3x3x3 (kd = 3) convolution, 'same' padding, dilation 1: the last
@@ -376,16 +370,11 @@ int mvsn_conv_to1_volume_norm(const float *in_raw, const float *in_stats, const 
 /* The same 2-D layer with the tower's LAST residual block folded into its load: the input
  * in_residual + LeakyReLU(GroupNorm(in_raw)) (SimpleBasicBlock, multi_view_stereonet.py:21-38) is formed in
  * registers from the raw output of the block's convolution and the block's input, never written.
- *   in_raw, in_residual (N,32,H,W)  in_stats (N,4,2)  in_gamma, in_beta (32)  in_residual may be NULL */
-int mvsn_conv_to1_block(const float *in_raw, const float *in_stats, const float *in_gamma, const float *in_beta,
-                        const float *in_residual, const float *weight, const float *bias, const float *prior,
-                        const float *fx, int n, int rows, int cols, float *out, mvsn_stream_t stream);
-/* The same with in_raw's statistics formed inside the launch from its records (N, tiles, 4, 3), see
- * mvsn_groupnorm_lrelu_apply_records. */
-int mvsn_conv_to1_block_records(const float *in_raw, const float *in_records, int tiles, const float *in_gamma,
-                                const float *in_beta, const float *in_residual, const float *weight, const float *bias,
-                                const float *prior, const float *fx, int n, int rows, int cols, float *out,
-                                mvsn_stream_t stream);
+ *   in_raw, in_residual (N,32,H,W)  in_stats, stat_tiles: as mvsn_groupnorm_lrelu_apply's stats  in_gamma, in_beta (32)
+ *   in_residual may be NULL */
+int mvsn_conv_to1_block(const float *in_raw, const float *in_stats, int stat_tiles, const float *in_gamma,
+                        const float *in_beta, const float *in_residual, const float *weight, const float *bias,
+                        const float *prior, const float *fx, int n, int rows, int cols, float *out, mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Soft-argmin over the hypothesis axis: out = sum_d softmax(-cost)_d * idepth_d.

@@ -38,7 +38,7 @@ class TowerDesc(Structure):
 
 CONV_FP32, CONV_BF16X3, CONV_FP32_WINO, CONV_BF16 = 0, 1, 2, 3
 CHAIN_AUTO, CHAIN_DIRECT, CHAIN_WINOGRAD, CHAIN_STEPWISE, CHAIN_BANDED = 0, 1, 2, 3, 4
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 # name -> (restype, argtypes); mirrors include/mvsn_hip.h one to one
@@ -78,16 +78,13 @@ SIGNATURES = {
     "mvsn_groupnorm_finalize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mvsn_groupnorm_finalize_split_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mvsn_groupnorm_finalize_split": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mvsn_groupnorm_lrelu_apply": (c_int, [c_void_p] * 5 + [c_int, c_long, c_void_p, c_void_p]),
-    "mvsn_groupnorm_lrelu_add2": (c_int, [c_void_p] * 8 + [c_int, c_long, c_void_p, c_void_p]),
-    "mvsn_conv_to1_block": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "mvsn_groupnorm_lrelu_apply": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 6 + [c_int, c_long, c_void_p, c_void_p]),
+    "mvsn_conv_to1_block": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p]),
     "mvsn_debug_set_band_flags": (c_int, [c_int]),
     "mvsn_debug_set_wino_rowphase": (c_int, [c_int]),
     "mvsn_debug_wino_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int * 8)]),
     "mvsn_debug_conv_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int * 8)]),
     "mvsn_copy_many": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "mvsn_conv_to1_block_records": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "mvsn_groupnorm_lrelu_apply_records": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 6 + [c_int, c_long, c_void_p, c_void_p]),
     "mvsn_conv_to1_supported": (c_int, [c_int, c_int]),
     "mvsn_conv_to1_volume_norm": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
     "mvsn_conv_to1": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_void_p]),

@@ -134,7 +134,7 @@ int chain_steps_launch(const ChainArgs &a, int n_chains, void *workspace, size_t
     if (int rc = mvsn_groupnorm_finalize(part0, N, records, st0, stream)) return rc;
     if (int rc = wino_launch(g1, r0, U1, bias1, st0, gn0w, gn0b, r1, part1, stream)) return rc;
     if (int rc = mvsn_groupnorm_finalize(part1, N, records, st1, stream)) return rc;
-    if (int rc = mvsn_groupnorm_lrelu_add2(r1, st1, gn1w, gn1b, r0, st0, gn0w, gn0b, N, P, r1, stream)) return rc;
+    if (int rc = mvsn_groupnorm_lrelu_apply(r1, st1, 0, gn1w, gn1b, r0, st0, gn0w, gn0b, N, P, r1, stream)) return rc;
     if (int rc = wino_launch(g1, r1, U2, bias2, nullptr, nullptr, nullptr, dl, nullptr, stream)) return rc;
     if (int rc = tail(d, moved, dl, cur)) return rc;
     prev = cur;

@@ -178,6 +178,11 @@ class _Records:
         self.partials, self.tiles = partials, int(partials.shape[1])
 
 
+def _stats_arg(st):
+    """(pointer, stat_tiles) as the consumers' entries take them: finalised (N,4,2) statistics (0) or _Records."""
+    return (_native.ptr(st.partials), st.tiles) if isinstance(st, _Records) else (_native.ptr(st), 0)
+
+
 class _Job:
     """mvsn_apply_job + the tensors it points at: out = LReLU(GN(r)) [+ residual | + LReLU(GN_0(residual))], in place."""
 
@@ -788,13 +793,7 @@ class PlaneSweepEngine:
     def gn_lrelu_add2(self, r, st, norm: _Norm, r0, st0, norm0: _Norm, out=None):
         n, spatial = r.shape[0], r[0, 0].numel()
         out = self.empty(r.shape, r.dtype, r.device) if out is None else out
-        if isinstance(st, _Records):
-            self._call("mvsn_groupnorm_lrelu_add2", self.lib.mvsn_groupnorm_lrelu_apply_records, _native.ptr(r),
-                       _native.ptr(st.partials), st.tiles, _native.ptr(norm.gamma), _native.ptr(norm.beta),
-                       _native.ptr(r0), _native.ptr(st0), _native.ptr(norm0.gamma), _native.ptr(norm0.beta), n, spatial,
-                       _native.ptr(out), _native.stream(), nbytes=4.0 * r.numel() * 3)
-            return out
-        self._call("mvsn_groupnorm_lrelu_add2", self.lib.mvsn_groupnorm_lrelu_add2, _native.ptr(r), _native.ptr(st),
+        self._call("mvsn_groupnorm_lrelu_add2", self.lib.mvsn_groupnorm_lrelu_apply, _native.ptr(r), *_stats_arg(st),
                    _native.ptr(norm.gamma), _native.ptr(norm.beta), _native.ptr(r0), _native.ptr(st0),
                    _native.ptr(norm0.gamma), _native.ptr(norm0.beta), n, spatial, _native.ptr(out), _native.stream(),
                    nbytes=4.0 * r.numel() * 3)
@@ -806,14 +805,7 @@ class PlaneSweepEngine:
         if out is None:
             out = self.empty((n, 1, rows, cols), dtype=torch.float32, device=r.device)
         assert tuple(out.shape) == (n, 1, rows, cols) and out.is_contiguous()
-        if isinstance(st, _Records):
-            self._call("mvsn_conv_to1_block" + self._lvl(), self.lib.mvsn_conv_to1_block_records, _native.ptr(r),
-                       _native.ptr(st.partials), st.tiles, _native.ptr(norm.gamma), _native.ptr(norm.beta),
-                       _native.ptr(x), _native.ptr(c.weight), _native.ptr(c.bias), _native.ptr(prior), _native.ptr(fx),
-                       n, rows, cols, _native.ptr(out), _native.stream(), flops=2.0 * 32 * 9 * out.numel(),
-                       nbytes=4.0 * (2 * r.numel() + out.numel()))
-            return out
-        self._call("mvsn_conv_to1_block" + self._lvl(), self.lib.mvsn_conv_to1_block, _native.ptr(r), _native.ptr(st),
+        self._call("mvsn_conv_to1_block" + self._lvl(), self.lib.mvsn_conv_to1_block, _native.ptr(r), *_stats_arg(st),
                    _native.ptr(norm.gamma), _native.ptr(norm.beta), _native.ptr(x), _native.ptr(c.weight),
                    _native.ptr(c.bias), _native.ptr(prior), _native.ptr(fx), n, rows, cols, _native.ptr(out),
                    _native.stream(), flops=2.0 * 32 * 9 * out.numel(), nbytes=4.0 * (2 * r.numel() + out.numel()))
@@ -850,15 +842,9 @@ class PlaneSweepEngine:
         n = r.shape[0]
         spatial = r[0, 0].numel()
         out = self.empty(r.shape, r.dtype, r.device) if out is None else out
-        if isinstance(stats, _Records):
-            self._call("mvsn_groupnorm_lrelu_apply" + self._lvl(), self.lib.mvsn_groupnorm_lrelu_apply_records, _native.ptr(r),
-                       _native.ptr(stats.partials), stats.tiles, _native.ptr(norm.gamma), _native.ptr(norm.beta),
-                       _native.ptr(residual), None, None, None, n, spatial, _native.ptr(out), _native.stream(),
-                       nbytes=4.0 * r.numel() * (3 if residual is not None else 2))
-            return out
         self._call("mvsn_groupnorm_lrelu_apply" + self._lvl(), self.lib.mvsn_groupnorm_lrelu_apply, _native.ptr(r),
-                   _native.ptr(stats), _native.ptr(norm.gamma), _native.ptr(norm.beta), _native.ptr(residual), n,
-                   spatial, _native.ptr(out), _native.stream(),
+                   *_stats_arg(stats), _native.ptr(norm.gamma), _native.ptr(norm.beta), _native.ptr(residual), None, None,
+                   None, n, spatial, _native.ptr(out), _native.stream(),
                    nbytes=4.0 * r.numel() * (3 if residual is not None else 2))
         return out
 

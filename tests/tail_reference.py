@@ -1,5 +1,5 @@
-"""Plain restatements of the small kernels either side of the cost-volume regulariser (csrc/mvsn_misc.hip above the
-32 -> 1 layers, mvsn_image_pyramid of csrc/mvsn_prepare.hip): soft-argmin, bilinear resize of idepth maps and masks,
+"""Plain restatements of the small kernels either side of the cost-volume regulariser (csrc/mvsn_misc.hip,
+mvsn_image_pyramid of csrc/mvsn_prepare.hip): soft-argmin, bilinear resize of idepth maps and masks,
 the area pyramid, multi-source fusion.
 
 Written from the operations, not from the kernels, in float64 arithmetic -- except where float32 IS the operation:

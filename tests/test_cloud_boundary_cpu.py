@@ -117,7 +117,7 @@ def test_native_carries_the_cloud_signatures():
                                                      c_void_p])
     assert sig["mvsn_cloud_nearest"] == (c_int, [c_void_p, c_long, c_float, c_float, c_void_p, c_size_t, c_long,
                                                  c_void_p, c_void_p, c_void_p, c_void_p])
-    assert _native.ABI_VERSION == 6                                     # additions only
+    assert _native.ABI_VERSION == 7
     assert "mvsn_cloud.hip" in build.SOURCES and "mvsn_voxel.hip" in build.SOURCES
     assert "mvsn_voxel.h" in build.HEADERS                              # the shared cell / key / hash: part of the digest
 
@@ -131,7 +131,7 @@ def test_header_declares_and_library_exports_the_cloud_entries():
         assert hasattr(lib, name), f"{name} is not exported"
     assert re.search(r"#define\s+MVSN_CLOUD_STATUS_RANGE\s+1\b", header)
     assert re.search(r"#define\s+MVSN_CLOUD_STATUS_TABLE\s+2\b", header)
-    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+6\b", header)
+    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+7\b", header)
 
 
 def test_workspace_size_and_argument_checks():

@@ -31,7 +31,7 @@ def test_new_entries_validate_before_any_device_work():
     _fails(lib.mvsn_fusion_gather(ONE, ONE, None, 1, 16, 4, ONE, None), lib, b"null")
     for V, HW, M in ((0, 16, 4), (1, 0, 4), (1, 16, 0), (1, 1 << 31, 4)):
         _fails(lib.mvsn_fusion_gather(ONE, ONE, ONE, V, HW, M, ONE, None), lib, b"bad sizes")
-    assert lib.mvsn_abi_version() == 6            # additions only
+    assert lib.mvsn_abi_version() == 7
 
 
 def test_confidence_is_an_engine_option_off_by_default():

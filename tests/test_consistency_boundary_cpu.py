@@ -28,7 +28,7 @@ def test_reproject_validates_before_any_device_work():
         args = list(good)
         args[5:8] = [batch, rows, cols]
         _fails(lib.mvsn_idepth_reproject(*args), lib, b"bad sizes")
-    assert lib.mvsn_abi_version() == 6
+    assert lib.mvsn_abi_version() == 7
 
 
 def test_occlusion_mask_validates_before_any_device_work():

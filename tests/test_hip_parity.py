@@ -755,8 +755,8 @@ def test_refiner_tower_end_trimming_is_equivalent():
 
 def test_statistics_formed_by_the_consumer_are_bit_identical():
     """Small batches: the normalise/activate passes and the folded 32 -> 1 tail are handed the producing convolution's
-    GroupNorm RECORDS and finalise them inside their own launch (mvsn_groupnorm_lrelu_apply_records,
-    mvsn_conv_to1_block_records) -- the same bits as with the stand-alone mvsn_groupnorm_finalize launch, fewer
+    GroupNorm RECORDS and finalise them inside their own launch (mvsn_groupnorm_lrelu_apply, mvsn_conv_to1_block with
+    stat_tiles > 0) -- the same bits as with the stand-alone mvsn_groupnorm_finalize launch, fewer
     launches; the regulariser's in-place passes likewise."""
     eng = net_for("gta_sfm_150epochs").engine()
     g = torch.Generator().manual_seed(21)

@@ -117,7 +117,7 @@ def test_entries_in_header_binding_and_binary():
     with open(os.path.join(ROOT, "include", "mvsn_hip.h")) as f:
         header = f.read()
     assert build.SOURCES.count("mvsn_mesh.hip") == 1
-    assert _native.ABI_VERSION == 6 and "#define MVSN_ABI_VERSION 6" in header.replace("  ", " ")
+    assert _native.ABI_VERSION == 7 and "#define MVSN_ABI_VERSION 7" in header.replace("  ", " ")
     for name in ENTRIES:
         assert re.search(r"\b%s\(" % name, header), name
         assert name in _native.SIGNATURES
@@ -125,7 +125,7 @@ def test_entries_in_header_binding_and_binary():
     for name in ENTRIES:
         assert hasattr(lib, name), name
     lib.mvsn_abi_version.restype = ctypes.c_int
-    assert lib.mvsn_abi_version() == 6
+    assert lib.mvsn_abi_version() == 7
     size = lib.mvsn_mesh_workspace_bytes
     size.restype, size.argtypes = ctypes.c_size_t, [ctypes.c_long] * 2
     assert size(0, 4) == 0 and size(-1, 4) == 0 and size(4, -1) == 0

@@ -25,7 +25,7 @@ def test_native_carries_the_normals_signatures():
     assert sig["mvsn_depth_normals"] == (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float, c_void_p, c_void_p])
     assert sig["mvsn_normals_gather"] == (c_int, [c_void_p] * 3 + [c_int, c_long, c_long, c_void_p, c_void_p])
     assert sig["mvsn_voxel_normals"] == (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p])
-    assert _native.ABI_VERSION == 6                                     # additions only
+    assert _native.ABI_VERSION == 7
     assert "mvsn_normals.hip" in build.SOURCES
 
 
@@ -36,8 +36,8 @@ def test_header_declares_and_library_exports_the_normals_entries():
     for name in ENTRIES:
         assert name in declared, f"{name} is not declared in include/mvsn_hip.h"
         assert hasattr(lib, name), f"{name} is not exported"
-    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+6\b", header)
-    assert _native.load().mvsn_abi_version() == 6
+    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+7\b", header)
+    assert _native.load().mvsn_abi_version() == 7
     source = open(os.path.join(ROOT, "multi_view_stereonet_amd", "csrc", "mvsn_normals.hip")).read()
     assert re.search(r"^#pragma clang fp contract\(off\)", source, flags=re.M)
 

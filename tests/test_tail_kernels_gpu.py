@@ -1,4 +1,4 @@
-"""The small kernels either side of the cost-volume regulariser (csrc/mvsn_misc.hip above the 32 -> 1 layers,
+"""The small kernels either side of the cost-volume regulariser (csrc/mvsn_misc.hip,
 mvsn_image_pyramid of csrc/mvsn_prepare.hip) against the restatements of tests/tail_reference.py, at the shapes where
 such kernels go wrong: ragged widths, D % 16 != 0, pixel counts off the block size, partial tiles, S = 3, unaligned
 copies.  Every tolerance is a bound of tail_reference.py, which tests/test_tail_reference_cpu.py shows ATen's own float32

@@ -162,7 +162,7 @@ def test_entries_in_header_binding_and_binary():
     with open(os.path.join(ROOT, "include", "mvsn_hip.h")) as f:
         header = f.read()
     assert build.SOURCES.count("mvsn_tsdf_align.hip") == 1 and build.HEADERS.count("mvsn_tsdf_sample.h") == 1
-    assert _native.ABI_VERSION == 6 and "#define MVSN_ABI_VERSION 6" in header.replace("  ", " ")
+    assert _native.ABI_VERSION == 7 and "#define MVSN_ABI_VERSION 7" in header.replace("  ", " ")
     for name in ENTRIES:
         assert re.search(r"\b%s\(" % name, header), name
         assert name in _native.SIGNATURES

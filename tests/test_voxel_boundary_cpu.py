@@ -102,7 +102,7 @@ def test_native_carries_the_voxel_signatures():
                                                                                     c_void_p])
     assert sig["mvsn_voxel_merge"] == (c_int, [c_void_p, c_void_p, c_long] + [c_float] * 5 +
                                        [c_void_p, c_size_t, c_long] + [c_void_p] * 6 + [c_void_p])
-    assert _native.ABI_VERSION == 6                                     # additions only
+    assert _native.ABI_VERSION == 7
     assert "mvsn_voxel.hip" in build.SOURCES
 
 
@@ -115,7 +115,7 @@ def test_header_declares_and_library_exports_the_voxel_entries():
         assert hasattr(lib, name), f"{name} is not exported"
     assert re.search(r"#define\s+MVSN_VOXEL_STATUS_RANGE\s+1\b", header)
     assert re.search(r"#define\s+MVSN_VOXEL_STATUS_TABLE\s+2\b", header)
-    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+6\b", header)
+    assert re.search(r"#define\s+MVSN_ABI_VERSION\s+7\b", header)
 
 
 def test_workspace_size_and_argument_checks():

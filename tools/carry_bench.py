@@ -46,13 +46,9 @@ for bi, mode1, add2 in ((0, False, False), (1, False, False), (2, False, False),
                                             P(o), P(p), _native.stream()), "conv")
 
     def run_apply(o=jout):
-        if add2:
-            _native.check(lib.mvsn_groupnorm_lrelu_add2(P(jr), P(stats), P(norm.gamma), P(norm.beta), P(jr0), P(stats0),
-                                                        P(norm0.gamma), P(norm0.beta), n, rows * cols, P(o),
-                                                        _native.stream()), "add2")
-        else:
-            _native.check(lib.mvsn_groupnorm_lrelu_apply(P(jr), P(stats), P(norm.gamma), P(norm.beta), P(jres), n,
-                                                         rows * cols, P(o), _native.stream()), "apply")
+        raw = (P(jr0), P(stats0), P(norm0.gamma), P(norm0.beta)) if add2 else (P(jres), None, None, None)
+        _native.check(lib.mvsn_groupnorm_lrelu_apply(P(jr), P(stats), 0, P(norm.gamma), P(norm.beta), *raw, n, rows * cols,
+                                                     P(o), _native.stream()), "add2" if add2 else "apply")
 
     job = _native.ApplyJob(P(jr), P(stats), P(norm.gamma), P(norm.beta), P(jr0) if add2 else P(jres),
                            P(stats0) if add2 else None, P(norm0.gamma) if add2 else None,

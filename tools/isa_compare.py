@@ -13,7 +13,12 @@ after normalising what moves without the code moving: the function index in basi
 
 lines = instruction lines, mfma = v_mfma among them, the rest from the kernel's amdhsa.kernels metadata entry (scratch =
 .private_segment_fixed_size, bytes).  A DIFFERENT symbol prints the figures of both sides.  Exit status 1 if any symbol
-differs or exists on one side only."""
+differs or exists on one side only.
+
+Kernels that changed files: the parent's files, then `--pooled` and the new tree's files; the symbols of each side are
+pooled, compared by name, and a line names both files (`<parent file> -> <new file>`):
+
+    tools/isa_compare.py PARENT_TREE NEW_TREE mvsn_conv.hip mvsn_misc.hip --pooled mvsn_conv.hip mvsn_misc.hip mvsn_groupnorm.hip"""
 import argparse
 import concurrent.futures
 import os
@@ -92,14 +97,33 @@ def main():
     ap.add_argument("new")
     ap.add_argument("files", nargs="+", help=".hip files of multi_view_stereonet_amd/csrc")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--pooled", nargs="+", metavar="FILE", help="kernels may have changed files: `files` are the parent's, "
+                    "these the new tree's; the symbols of each side are pooled and compared by name")
     a = ap.parse_args()
+    files = {"parent": a.files, "new": a.pooled or a.files}
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
         jobs = {(side, f): pool.submit(compile_asm, tree, f, os.path.join(tmp, "%s_%s.s" % (side, f)))
-                for side, tree in (("parent", a.parent), ("new", a.new)) for f in a.files}
+                for side, tree in (("parent", a.parent), ("new", a.new)) for f in files[side]}
         asm = {k: split_symbols(j.result()) for k, j in jobs.items()}
     print("# flags: %s -S --cuda-device-only" % " ".join(HIPCC_FLAGS + os.environ.get("MVSN_HIPCC_FLAGS", "").split()))
     bad = 0
-    for f in a.files:
+    if a.pooled:
+        old, new = ({sym: (f, s) for f in files[side] for sym, s in asm[(side, f)].items()} for side in ("parent", "new"))
+        for side, pool_ in (("parent", old), ("new", new)):
+            twice = sum(len(asm[(side, f)]) for f in files[side]) - len(pool_)
+            bad += twice                                 # (a kernel defined in two files of one side has no one counterpart)
+            print("# %s: %s: %d symbols%s" % (side, " ".join(files[side]), len(pool_), ", %d defined twice" % twice if twice else ""))
+        only_old, only_new = sorted(set(old) - set(new)), sorted(set(new) - set(old))
+        print("# only in parent: %s; only in new: %s" % (", ".join(only_old) or "none", ", ".join(only_new) or "none"))
+        bad += len(only_old) + len(only_new)
+        for sym in sorted(set(old) & set(new)):
+            (fo, so), (fn, sn) = old[sym], new[sym]
+            if so["text"] == sn["text"]:
+                print("identical  %s -> %s  %s  [%s]" % (fo, fn, sym, figures(so)))
+            else:
+                bad += 1
+                print("DIFFERENT  %s -> %s  %s  parent [%s]  new [%s]" % (fo, fn, sym, figures(so), figures(sn)))
+    for f in [] if a.pooled else a.files:
         old, new = asm[("parent", f)], asm[("new", f)]
         only_old, only_new = sorted(set(old) - set(new)), sorted(set(new) - set(old))
         print("# %s: symbols parent %d, new %d; only in parent: %s; only in new: %s" %
