@@ -141,9 +141,9 @@ class EngineOptions:
         # consecutive launches of a sliced tower walk their tiles in opposite directions: each starts on what the one
         # before it wrote / read last (38.55 -> 38.42 ms per step, five interleaved pairs; results identical)
         self.carry_alternate = True
-        # ... the regulariser's three in-place passes the same way: measured +0.1-0.2 ms per 38.6 ms step only (a pass
-        # costs the volume kernel about what it costs alone), so the regulariser stays one batch by default
-        self.carry_volume_passes = False
+        # ... the regulariser's three in-place passes the same way (cost_volume_filter_sliced): a carrying half-batch
+        # launch costs 0.04 ms over the plain one where the pass alone costs 0.16 (profiles/r15_volume_carry)
+        self.carry_volume_passes = True
         # Plane-resident towers on the 16x32 coarse grid (mvsn_tower_16x32): the level-4 refiner and the extractor's
         # residual stack as ONE launch each, one persistent workgroup per sample (15-21 launches otherwise)
         self.towers = True

@@ -19,6 +19,14 @@ source assumes.  This script compiles the file to assembly with the library's fl
      path-insensitive walk also follows combinations the counter excludes.  What the static walk cannot decide, the
      1000-launch bit-identity stress test (tests/test_hip_parity.py::test_carried_dilation1_launches_stress_bit_identical)
      covers dynamically.
+  5. (volume carriers, conv_wino_kernel<.., VOL, RIDE = 1>) the carried job's units are loaded by inline assembly too
+     (`buffer_load_dwordx4 v[a:b], .. offen nt` in a block: a HIDDEN load -- with the compiler's own load the waitcnt pass
+     puts `s_waitcnt vmcnt(0)` in front of its first use, a drain of the DMA pieces it does not know about).  To the
+     compiler v[a:b] are defined the moment the block ends, so on every control-flow path from the load no instruction
+     may name one of them before a hand-placed `s_waitcnt vmcnt` (a copy, a spill or a hoisted use would read them
+     with the load in flight, a write would be overwritten by it).  Every volume carrier has such loads.
+  6. (volume carriers) no `s_waitcnt .. vmcnt` of the compiler's own inside a loop: each is such a drain.
+  Basic blocks are split at labels and at the `; %bb.N:` markers of fall-through blocks.
 
    python tools/check_dma_isa.py            # exit code 0 = all kernels pass; prints one line per kernel
 """
@@ -31,7 +39,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "multi_view_stereonet_amd", "csrc", "mvsn_conv_wino.hip")
 VMEM = re.compile(r"^\s*(global_(load|store|atomic)|buffer_(load|store|atomic)|flat_(load|store|atomic)|scratch_(load|store))")
-KERNEL = re.compile(r"^(_ZN4mvsn16conv_wino_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E(?:Lb[01]E|Li\d+E)?(?:Lb[01]E)?E\S*):")
+KERNEL = re.compile(r"^(_ZN4mvsn16conv_wino_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELb([01])EE\S*):")
 
 
 def assemble() -> str:
@@ -51,7 +59,8 @@ def kernels(text):
     for k, (i, m) in enumerate(starts):
         end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
         mode, ks, nstage, dil, vol, ride = int(m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)), int(m.group(7))
-        yield m.group(1), dict(mode=mode, ks=ks, nstage=nstage, dil=dil, vol=vol, ride=ride), lines[i + 1:end]
+        yield m.group(1), dict(mode=mode, ks=ks, nstage=nstage, dil=dil, vol=vol, ride=ride, tile=int(m.group(8)),
+                               fullw=int(m.group(9))), lines[i + 1:end]
 
 
 def check(name, p, body):
@@ -67,7 +76,7 @@ def check(name, p, body):
         if t.startswith(";;#ASMEND"):
             blk = None
             continue
-        m = re.match(r"^(\.LBB\d+_\d+):", t)
+        m = re.match(r"^(\.LBB\d+_\d+):", t) or re.match(r"^; (%bb\.\d+):", t)   # (a fall-through block has no label)
         if m:
             bbs.append([m.group(1), []])
             continue
@@ -148,7 +157,69 @@ def check(name, p, body):
                         done.add((pb, need))
                         work.append((pb, len(bbs[pb][1]), need))
             mixed += bad is not None
-    return errs, len(dma_blocks), counted, (paths_total, mixed)
+    # 5. hidden loads (volume carriers): a carried job's unit is loaded by an inline-assembly `buffer_load_dwordx4 v[a:b]`
+    # that the waitcnt pass does not see -- to the compiler v[a:b] are defined the moment the block ends.  On every path
+    # from the load, nothing may name one of those registers before a hand-placed `s_waitcnt vmcnt` (a copy, a spill or
+    # a hoisted use there would read the registers with the load in flight; a write would be overwritten by it).
+    succs = {i: set() for i in range(len(bbs))}
+    for b, ps in preds.items():
+        for pb in ps:
+            succs[pb].add(b)
+    hidden = 0
+    for bi, (label, ins) in enumerate(bbs):
+        for k, (t, bk) in enumerate(ins):
+            m = re.match(r"buffer_load_dwordx4 v\[(\d+):(\d+)\],", t)
+            if not (m and bk is not None and not t.endswith(" lds")):
+                continue
+            hidden += 1
+            regs = set(range(int(m.group(1)), int(m.group(2)) + 1))
+            work, done = [(bi, k + 1)], set()
+            while work:
+                b, pos = work.pop()
+                waited = False
+                for tj, bj in bbs[b][1][pos:]:
+                    if bj is not None and tj.startswith("s_waitcnt vmcnt("):
+                        waited = True
+                        break
+                    if vgprs_named(tj) & regs:
+                        errs.append(f"hidden load {t.split(',')[0]}: `{tj}` names its registers before a counted wait (path through {bbs[b][0]})")
+                        waited = True   # (one report per path)
+                        break
+                if waited:
+                    continue
+                for nb in succs[b]:   # (a path that ends the kernel never reads the registers)
+                    if nb not in done:
+                        done.add(nb)
+                        work.append((nb, 0))
+    if p["vol"] and hidden == 0:
+        errs.append("volume carrier without an inline-assembly load of the carried job: the check is stale")
+    # 6. (volume carriers) inside the loops every wait on the vector-memory queue is a hand-placed one: a wait of the
+    # compiler's there is a drain of the DMA ring it does not know about, once per step or tile
+    if p["vol"]:
+        def loops(b):   # can block b reach itself?
+            seen, work = set(), list(succs[b])
+            while work:
+                x = work.pop()
+                if x == b:
+                    return True
+                if x not in seen:
+                    seen.add(x)
+                    work.extend(succs[x])
+            return False
+        for bi, (label, ins) in enumerate(bbs):
+            own = [t for t, bk in ins if bk is None and re.match(r"s_waitcnt\b.*vmcnt", t)]
+            if own and loops(bi):
+                errs.append(f"compiler-placed `{own[0]}` inside a loop ({label})")
+    return errs, len(dma_blocks), counted, (paths_total, mixed, hidden)
+
+
+def vgprs_named(t):
+    """The vector registers an instruction names (single registers and ranges; not the accumulation registers)."""
+    regs = set()
+    for a, b in re.findall(r"(?<![\w.])v\[(\d+):(\d+)\]", t):
+        regs.update(range(int(a), int(b) + 1))
+    regs.update(int(a) for a in re.findall(r"(?<![\w.\[])v(\d+)\b", t))
+    return regs
 
 
 S2_KERNEL = re.compile(r"^(_ZN4mvsn19conv_wino_s2_kernel\S*):")
@@ -259,8 +330,8 @@ def main():
             continue
         errs, ndma, nwait, ndec = check(name, p, body)
         checked += 1
-        tag = "mode=%(mode)d ks=%(ks)d stages=%(nstage)d dil=%(dil)d vol=%(vol)d ride=%(ride)d" % p
-        print(f"conv_wino_kernel<{tag}>: {ndma} DMA sites, {nwait} counted waits ({ndec[0]} pieces-only paths, {ndec[1]} waits with a mixed path): {'OK' if not errs else 'FAIL'}")
+        tag = "mode=%(mode)d ks=%(ks)d stages=%(nstage)d dil=%(dil)d vol=%(vol)d ride=%(ride)d tile=%(tile)d fullw=%(fullw)d" % p
+        print(f"conv_wino_kernel<{tag}>: {ndma} DMA sites, {nwait} counted waits ({ndec[0]} pieces-only paths, {ndec[1]} waits with a mixed path), {ndec[2]} hidden loads: {'OK' if not errs else 'FAIL'}")
         for e in errs[:10]:
             print("   ", e)
         bad += bool(errs)
