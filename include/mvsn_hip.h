@@ -669,6 +669,51 @@ int mvsn_cloud_nearest(const float *query, long nq, float inv_cell, float r2, co
                        mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Registration of one cloud to another: Gauss-Newton (ICP) on the residual between a moved source point and its nearest
+ * target point (multi_view_stereonet_amd/fusion.py: cloud_register, cloud_register_system; the semantics and every fp32
+ * step are DESIGN.md section 20).  The target's index is mvsn_cloud_index_build's (index_workspace, its
+ * mvsn_cloud_workspace_bytes(n_target) bytes, inv_cell and r2 as given to mvsn_cloud_nearest): built once, it serves
+ * any number of sources.  source (n_source,3), weights (n_source) or NULL, target (n_target,3) as given to the build,
+ * target_normals (n_target,3) or NULL, all fp32; 1 <= n_source, n_target <= 2^31 - 1.  T (16 fp32, row-major 4 x 4) maps
+ * source coordinates into the target's frame; centre (3 fp32) is the point the rotation update turns about.  T and
+ * centre are DEVICE pointers.
+ * Per source point, with the pose's twelve numbers rounded once to fp32: p'_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a; its match is
+ *   mvsn_cloud_nearest's of p'; d = p' - target[match]; q = p' - centre.  With target_normals (point-to-plane):
+ *   r = (d.x n.x + d.y n.y) + d.z n.z, J = (n, q x n), each product rounded, then one subtraction.  Without
+ *   (point-to-point): three rows r = d_a, J_a = (e_a, q x e_a), and sum w r^2 adds w d2 of the query.  The point takes
+ *   part iff its row and p' are finite, its weight w (1 without weights) is finite and > 0, a match exists, and in plane
+ *   mode the match's normal is finite.  In fp64: H = sum (w J) J^T, b = sum (w J) r, sum w, sum (w r) r, the count,
+ *   summed in an order that n_source alone fixes (at most 1024 workgroups, each on blocks of 1024 rows 1024 blocks
+ *   apart; no atomics: bitwise reproducible).
+ * mvsn_cloud_register_system evaluates that once at T:
+ *   H (6,6), b (6), sums (3) = (count, sum w, sum w r^2), all fp64; index (n_source) int64 and residual (n_source)
+ *   fp32, both or neither NULL: the matched row and r (plane mode) or d2 (point mode) where the point takes part,
+ *   -1 and NaN elsewhere, every row written once.
+ * mvsn_cloud_register iterates, iterations (0 to 1000) times: stop with status 1 if count < min_points; scale H to a
+ *   unit diagonal and take its Cholesky factor, stop with status 2 at a diagonal entry that is not a positive finite
+ *   number, a pivot < min_pivot (inside (0, 1)) or an update that is not finite; solve H (v, omega) = -b and apply
+ *   R <- exp([omega]x) R, t <- exp([omega]x) (t - centre) + centre + v to the fp64 pose.  A stopped run keeps its pose.
+ *   T_out (16 fp32): the final pose, each number rounded once, T_init's bottom row; history (iterations+1,3) fp64:
+ *   (count, sum w, sum w r^2) at the pose before update i, the last row at the final pose; status (1 int32);
+ *   information (6,6) fp64: H at the final pose.  iterations + 1 pairs of launches; nothing waits on another workgroup
+ *   and nothing is read on the host.
+ * workspace: mvsn_cloud_register_workspace_bytes(n_source) bytes (0 for what the entries refuse), 16-byte aligned: the
+ *   fp64 pose and a record of 30 doubles per workgroup.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_cloud_register_workspace_bytes(long n_source);
+int mvsn_cloud_register_system(const float *source, long n_source, const float *weights, const float *target,
+                               const float *target_normals, long n_target, float inv_cell, float r2,
+                               const void *index_workspace, size_t index_workspace_bytes, const float *T,
+                               const float *centre, void *workspace, size_t workspace_bytes, double *H, double *b,
+                               double *sums, int64_t *index, float *residual, mvsn_stream_t stream);
+int mvsn_cloud_register(const float *source, long n_source, const float *weights, const float *target,
+                        const float *target_normals, long n_target, float inv_cell, float r2,
+                        const void *index_workspace, size_t index_workspace_bytes, const float *T_init,
+                        const float *centre, int iterations, long min_points, double min_pivot, void *workspace,
+                        size_t workspace_bytes, float *T_out, double *history, int *status, double *information,
+                        mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dense TSDF volume: depth maps integrated along the viewing rays, and a mesh taken from the volume by Surface Nets
  * (multi_view_stereonet_amd/tsdf.py; the semantics, every fp32 step and the error bounds are DESIGN.md section 15).
  * The state is planar fp32 in the layout (nz,ny,nx), x fastest: sdf_sum = sum w t, weight = sum w, color_sum

@@ -126,6 +126,12 @@ SIGNATURES = {
     "mvsn_cloud_index_build": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_cloud_nearest": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_size_t, c_long] +
                            [c_void_p] * 3 + [c_void_p]),
+    "mvsn_cloud_register_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_cloud_register_system": (c_int, [c_void_p, c_long] + [c_void_p] * 3 + [c_long] + [ctypes.c_float] * 2 +
+                                   [c_void_p, c_size_t] + [c_void_p] * 2 + [c_void_p, c_size_t] + [c_void_p] * 5 + [c_void_p]),
+    "mvsn_cloud_register": (c_int, [c_void_p, c_long] + [c_void_p] * 3 + [c_long] + [ctypes.c_float] * 2 +
+                            [c_void_p, c_size_t] + [c_void_p] * 2 + [c_int, c_long, ctypes.c_double, c_void_p, c_size_t] +
+                            [c_void_p] * 4 + [c_void_p]),
     "mvsn_tsdf_camera_batch": (c_int, []),
     "mvsn_tsdf_integrate": (c_int, [c_void_p] * 6 + [c_int] * 6 + [ctypes.c_float] * 6 + [c_void_p] * 3 + [c_void_p]),
     "mvsn_tsdf_workspace_bytes": (c_size_t, [c_int] * 3),

@@ -21,6 +21,7 @@
 // step is one operation.
 #pragma clang fp contract(off)
 #include "mvsn_tsdf_sample.h"
+#include "mvsn_pose.h"
 
 namespace mvsn {
 
@@ -163,104 +164,29 @@ __global__ __launch_bounds__(TA_THREADS) void tsdf_align_accumulate_kernel(
   }
 }
 
-// exp([w]x) by Rodrigues, the small-angle series below |w|^2 = 1e-8 (the next terms are below 1e-17 of the kept ones)
-__device__ inline void align_rotation(const double *w, double *Rd) {
-  const double t2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-  double a, b;
-  if (t2 < 1e-8) {
-    a = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0);
-    b = 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0);
-  } else {
-    const double t = sqrt(t2);
-    a = sin(t) / t;
-    b = (1.0 - cos(t)) / t2;
-  }
-  // I + a [w]x + b [w]x^2, [w]x^2 = w w^T - |w|^2 I
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Rd[i * 3 + j] = b * (w[i] * w[j]) + (i == j ? 1.0 - b * t2 : 0.0);
-  Rd[1] -= a * w[2], Rd[2] += a * w[1];
-  Rd[3] += a * w[2], Rd[5] -= a * w[0];
-  Rd[6] -= a * w[1], Rd[7] += a * w[0];
-}
-
 // The update of one view from its sums s (TA_TERMS): 0 and the new pose in P, or the status that stops the view (1: fewer
 // than min_pixels take part; 2: the scaled normal matrix has a pivot below min_pivot, or a diagonal entry that is not a
-// positive finite number) with P untouched.
+// positive finite number) with P untouched.  The solve is mvsn_pose.h's; it hands delta to the update below.
 __device__ inline int align_update(const double *s, double min_pixels, double min_pivot, float voxel_size, float ox,
                                    float oy, float oz, int nx, int ny, int nz, double *P) {
-  if (!(s[29] >= min_pixels)) return 1;
-  double M[6][6], sc[6], y[6];
-  {
-    int m = 0;
+  return pose_solve(s, min_pixels, min_pivot, [&](const double *delta) {
+    // R <- Rd R, t <- Rd (t - cw) + cw + voxel_size v, cw = origin + voxel_size c0
+    double Rd[9], N[TA_POSE];
+    align_rotation(delta + 3, Rd);
+    const double vs = (double)voxel_size;
+    const double cw[3] = {(double)ox + vs * ((double)(nx - 1) * 0.5), (double)oy + vs * ((double)(ny - 1) * 0.5),
+                          (double)oz + vs * ((double)(nz - 1) * 0.5)};
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
+    for (int a = 0; a < 3; ++a) {
 #pragma unroll
-      for (int j = i; j < 6; ++j, ++m) M[i][j] = M[j][i] = s[m];
-  }
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    ok = ok && M[i][i] > 0.0 && M[i][i] <= 1.7976931348623157e308;
-    sc[i] = 1.0 / sqrt(M[i][i]);
-  }
-  if (!ok) return 2;
-  // the Cholesky factor L (in the lower triangle of M) of S H S; the pivot of column j is L_jj^2 before its root
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double p = (M[j][j] * sc[j]) * sc[j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) p = p - M[j][k] * M[j][k];
-    ok = ok && p >= min_pivot;                                      // (a NaN fails)
-    const double l = sqrt(p);
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double e = (M[j][i] * sc[i]) * sc[j];                         // (the upper triangle still holds H)
-#pragma unroll
-      for (int k = 0; k < j; ++k) e = e - M[i][k] * M[j][k];
-      M[i][j] = e / l;
+      for (int b = 0; b < 3; ++b) N[a * 3 + b] = (Rd[a * 3] * P[b] + Rd[a * 3 + 1] * P[3 + b]) + Rd[a * 3 + 2] * P[6 + b];
+      N[9 + a] = (((Rd[a * 3] * (P[9] - cw[0]) + Rd[a * 3 + 1] * (P[10] - cw[1])) + Rd[a * 3 + 2] * (P[11] - cw[2])) + cw[a]) +
+                 vs * delta[a];
     }
-    M[j][j] = l;
-  }
-  if (!ok) return 2;
-  // (S H S) y = -S b: L z = -S b, L^T y = z; delta = S y
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double e = -(s[21 + i] * sc[i]);
-#pragma unroll
-    for (int k = 0; k < i; ++k) e = e - M[i][k] * y[k];
-    y[i] = e / M[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double e = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) e = e - M[k][i] * y[k];
-    y[i] = e / M[i][i];
-  }
-  double delta[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) delta[i] = y[i] * sc[i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) ok = ok && fabs(delta[i]) <= 1.7976931348623157e308;
-  if (!ok) return 2;
-  // R <- Rd R, t <- Rd (t - cw) + cw + voxel_size v, cw = origin + voxel_size c0
-  double Rd[9], N[TA_POSE];
-  align_rotation(delta + 3, Rd);
-  const double vs = (double)voxel_size;
-  const double cw[3] = {(double)ox + vs * ((double)(nx - 1) * 0.5), (double)oy + vs * ((double)(ny - 1) * 0.5),
-                        (double)oz + vs * ((double)(nz - 1) * 0.5)};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) N[a * 3 + b] = (Rd[a * 3] * P[b] + Rd[a * 3 + 1] * P[3 + b]) + Rd[a * 3 + 2] * P[6 + b];
-    N[9 + a] = (((Rd[a * 3] * (P[9] - cw[0]) + Rd[a * 3 + 1] * (P[10] - cw[1])) + Rd[a * 3 + 2] * (P[11] - cw[2])) + cw[a]) +
-               vs * delta[a];
-  }
-#pragma unroll
-  for (int i = 0; i < TA_POSE; ++i) P[i] = N[i];
-  return 0;
+    for (int i = 0; i < TA_POSE; ++i) P[i] = N[i];
+    return 0;
+  });
 }
 
 // One workgroup per view.  `pose_in` null: the pose is the float32 T (before the first update).  `update`: solve and

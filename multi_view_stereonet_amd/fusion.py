@@ -11,7 +11,9 @@ cloud on a voxel grid: a surface that k views saw is in the fused cloud k times,
 camera; ``point_normals`` reads those maps at the points of a fused cloud and ``voxel_normals`` takes them through a merge.
 ``cloud_nearest`` (csrc/mvsn_cloud.hip) finds, for every point of one cloud, the nearest point of
 another within a radius, exactly; ``radius_outlier_mask`` is the same query of a cloud against itself
-(``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).  A dense TSDF volume that integrates the same
+(``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).  ``cloud_register`` (DESIGN.md section 20,
+csrc/mvsn_cloud_register.hip) moves one cloud onto another by ICP on that query, point-to-plane or point-to-point, and
+``cloud_register_system`` is one evaluation of its normal equations.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -475,6 +477,209 @@ def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) ->
                          f"cells of {float(h):g} or more from the origin")
     if bits:
         raise RuntimeError(f"cloud_nearest: the hash grid overflowed (status {bits})")
+    return out
+
+
+class CloudRegistration(NamedTuple):
+    T: torch.Tensor                  # (4,4) fp32: source coordinates -> the target's frame, each number rounded once
+    history: torch.Tensor            # (iterations+1,3) fp64: (count, sum w, sum w r^2) before update i; the last row at T
+    status: torch.Tensor             # () int32: 0, 1 = fewer than min_points took part, 2 = the normal matrix was singular
+    information: torch.Tensor        # (6,6) fp64: H = sum w J J^T at T
+
+
+def _integer_in(value, name, lo, hi):
+    try:
+        i = int(value)
+        if i != value or isinstance(value, bool):
+            raise TypeError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name} must be an integer, got {value!r}") from None
+    if i < lo or i > hi:
+        raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {value!r}")
+    return i
+
+
+def _pose_f32(T, name, dev):
+    """``T`` as a contiguous (4,4) float32 tensor on ``dev``; ValueError unless it is a finite (4,4) floating-point
+    tensor.  Its values are looked at where it lives: pass a host tensor and nothing waits for the device."""
+    if not torch.is_tensor(T) or tuple(T.shape) != (4, 4):
+        raise ValueError(f"{name} must be a (4,4) tensor")
+    if not T.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, got {T.dtype}")
+    if T.device.type == "meta":
+        raise ValueError(f"{name} is on {T.device}")
+    T32 = T.detach().to(torch.float32)
+    if not bool(torch.isfinite(T32).all()):
+        raise ValueError(f"{name} must be finite (as float32)")
+    return T32.to(dev).contiguous()
+
+
+def _check_register(source, target, max_dist, target_normals, weights, centre):
+    """The validation ``cloud_register`` and ``cloud_register_system`` share: (N, M, dev, h, inv, r2, centre) with centre
+    None (the default: the target's mean) or three np.float32."""
+    check_cloud("source", source)
+    check_cloud("target", target)
+    dev = source.device
+    if target.device != dev:
+        raise ValueError(f"target is on {target.device}, source on {dev}")
+    N, M = int(source.shape[0]), int(target.shape[0])
+    if target_normals is not None:
+        if not torch.is_tensor(target_normals) or tuple(target_normals.shape) != (M, 3) or \
+                target_normals.dtype != torch.float32:
+            raise ValueError(f"target_normals must be a ({M},3) float32 tensor")
+        if target_normals.device != dev:
+            raise ValueError(f"target_normals is on {target_normals.device}, source on {dev}")
+    if weights is not None:
+        if not torch.is_tensor(weights) or tuple(weights.shape) != (N,) or weights.dtype != torch.float32:
+            raise ValueError(f"weights must be a ({N},) float32 tensor")
+        if weights.device != dev:
+            raise ValueError(f"weights is on {weights.device}, source on {dev}")
+    h, inv, r2 = cloud_radius_scalars(max_dist)
+    c = None
+    if centre is not None:
+        try:
+            if torch.is_tensor(centre):
+                if centre.device.type == "meta":
+                    raise TypeError
+                centre = centre.detach().cpu().numpy()
+            with np.errstate(all="ignore"):
+                c = np.asarray(centre, dtype=np.float64).astype(np.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"centre must be three finite numbers, got {centre!r}") from None
+        if c.shape != (3,) or not np.isfinite(c).all():
+            raise ValueError(f"centre must be three finite numbers (as float32), got {centre!r}")
+    return N, M, dev, h, inv, r2, c
+
+
+def _register_centre(c, target, dev):
+    """(3,) float32 on ``dev``: the given centre, or the fp64 mean of the finite rows of ``target`` rounded once (formed
+    on the device, nothing read back; (0,0,0) where no row is finite)."""
+    if c is not None:
+        return torch.from_numpy(c).to(dev)
+    t = target.detach()
+    ok = torch.isfinite(t).all(dim=1, keepdim=True)
+    total = torch.where(ok, t, torch.zeros((), dtype=t.dtype, device=dev)).to(torch.float64).sum(dim=0)
+    return (total / ok.sum().clamp(min=1).to(torch.float64)).to(torch.float32).contiguous()
+
+
+def _raise_cloud_status(bits, h, who):
+    if bits & CLOUD_STATUS_RANGE:
+        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
+                         f"cells of {float(h):g} or more from the origin")
+    if bits:
+        raise RuntimeError(f"{who}: the hash grid overflowed (status {bits})")
+
+
+def cloud_register_system(source: torch.Tensor, target: torch.Tensor, max_dist: float, T: torch.Tensor, *,
+                          target_normals: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                          centre=None, with_matches: bool = False):
+    """One evaluation of what ``cloud_register`` iterates, at the float32 values of ``T``:
+    ``(H (6,6) fp64, b (6,) fp64, count () int64, sum_w () fp64, sum_w_r2 () fp64, index, residual)`` with
+    H = sum w J J^T and b = sum w J r over the source points that take part.  With ``with_matches``, ``index`` (N,) int64
+    is the matched target row and ``residual`` (N,) fp32 is r (point-to-plane) or the squared distance (point-to-point);
+    -1 and NaN where the point takes no part; both None without.  The covariance of the pose is H^-1 times the noise
+    scale."""
+    N, M, dev, h, inv, r2, c = _check_register(source, target, max_dist, target_normals, weights, centre)
+    T32 = _pose_f32(T, "T", dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    if N == 0 or M == 0:               # nothing to match, nothing to launch
+        index = torch.full((N,), -1, dtype=torch.int64, device=dev) if with_matches else None
+        res = torch.full((N,), float("nan"), dtype=torch.float32, device=dev) if with_matches else None
+        return (torch.zeros((6, 6), **f64), torch.zeros((6,), **f64), torch.zeros((), dtype=torch.int64, device=dev),
+                torch.zeros((), **f64), torch.zeros((), **f64), index, res)
+    if not source.is_cuda:
+        raise RuntimeError("cloud_register_system runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, t = source.detach().contiguous(), target.detach().contiguous()
+    nm = target_normals.detach().contiguous() if target_normals is not None else None
+    wt = weights.detach().contiguous() if weights is not None else None
+    cen = _register_centre(c, t, dev)
+    idx_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(M), lib.mvsn_cloud_register_workspace_bytes(N)
+    idx_ws = torch.empty(idx_bytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    Hm, b, sums = torch.empty((6, 6), **f64), torch.empty((6,), **f64), torch.empty((3,), **f64)
+    index = torch.empty((N,), dtype=torch.int64, device=dev) if with_matches else None
+    res = torch.empty((N,), dtype=torch.float32, device=dev) if with_matches else None
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(idx_ws), idx_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_register_system(
+            _native.ptr(s), N, _native.ptr(wt), _native.ptr(t), _native.ptr(nm), M, float(inv), float(r2),
+            _native.ptr(idx_ws), idx_bytes, _native.ptr(T32), _native.ptr(cen), _native.ptr(ws), ws_bytes, _native.ptr(Hm),
+            _native.ptr(b), _native.ptr(sums), _native.ptr(index), _native.ptr(res), st), "mvsn_cloud_register_system")
+        bits = int(status.item())      # the one host synchronisation
+    _raise_cloud_status(bits, h, "cloud_register_system")
+    return Hm, b, sums[0].to(torch.int64), sums[1].clone(), sums[2].clone(), index, res
+
+
+def cloud_register(source: torch.Tensor, target: torch.Tensor, max_dist: float, *,
+                   target_normals: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                   T_init: Optional[torch.Tensor] = None, centre=None, iterations: int = 20, min_points: int = 6,
+                   min_pivot: float = 1e-9) -> CloudRegistration:
+    """Register ``source`` (N,3) fp32 to ``target`` (M,3) fp32 (ICP; DESIGN.md section 20, csrc/mvsn_cloud_register.hip):
+    the rigid ``T`` with p' = R p + t that brings the source points onto their nearest target points within
+    ``max_dist``, by ``iterations`` Gauss-Newton steps from ``T_init`` (the identity by default).
+
+    With ``target_normals`` (M,3) fp32 the residual is point-to-plane, r = (p' - target_j) . n_j; without, point-to-point,
+    the three differences.  The match j of a source point is exactly ``cloud_nearest(p', target, max_dist)``; a point
+    takes part iff its row and p' are finite, its weight (``weights`` (N,) fp32, 1 without) is finite and > 0, it has a
+    match and, in plane mode, the match's normal is finite.  ``centre`` (three numbers or a (3,) tensor) is the point the
+    rotation update turns about; the default is the mean of the target's finite rows, formed on the device.
+
+    Every iteration forms H = sum w J J^T and b = sum w J r in fp64 in a fixed order (bitwise reproducible), solves
+    H (v, omega) = -b through a Jacobi-scaled Cholesky factor and applies R <- exp([omega]x) R,
+    t <- exp([omega]x) (t - c) + c + v to the fp64 pose.  The run stops, keeping its pose, with status 1 when fewer
+    than ``min_points`` points take part and with status 2 when H has a diagonal entry that is not positive and finite
+    or a scaled pivot below ``min_pivot``; ``history`` rows then repeat.  ``cloud_register_system(..., T=result.T)``
+    reproduces the last history row and ``information`` bit for bit.  Point-to-plane converges in a few iterations from
+    a start within ``max_dist``; point-to-point lowers the distances every step but slides along surfaces slowly.
+
+    Everything is validated here, before any launch; ``T_init`` and ``centre`` are checked where they live (pass host
+    tensors and nothing waits for the device).  The one host synchronisation is the read of the index build's status
+    word, after the whole loop is enqueued."""
+    N, M, dev, h, inv, r2, c = _check_register(source, target, max_dist, target_normals, weights, centre)
+    it = _integer_in(iterations, "iterations", 0, 1000)
+    mp = _integer_in(min_points, "min_points", 1, 2 ** 62)
+    try:
+        pv = float(min_pivot)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_pivot must be a number inside (0, 1), got {min_pivot!r}") from None
+    if not 0.0 < pv < 1.0:
+        raise ValueError(f"min_pivot must be a number inside (0, 1), got {min_pivot!r}")
+    T32 = _pose_f32(torch.eye(4, dtype=torch.float32) if T_init is None else T_init, "T_init", dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    if N == 0 or M == 0:               # nothing to match, nothing to launch: the run stops at once
+        return CloudRegistration(T32.clone(), torch.zeros((it + 1, 3), **f64),
+                                 torch.ones((), dtype=torch.int32, device=dev), torch.zeros((6, 6), **f64))
+    if not source.is_cuda:
+        raise RuntimeError("cloud_register runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, t = source.detach().contiguous(), target.detach().contiguous()
+    nm = target_normals.detach().contiguous() if target_normals is not None else None
+    wt = weights.detach().contiguous() if weights is not None else None
+    cen = _register_centre(c, t, dev)
+    idx_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(M), lib.mvsn_cloud_register_workspace_bytes(N)
+    idx_ws = torch.empty(idx_bytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    run = torch.empty(1, dtype=torch.int32, device=dev)
+    out = CloudRegistration(torch.empty((4, 4), dtype=torch.float32, device=dev), torch.empty((it + 1, 3), **f64),
+                            run[0], torch.empty((6, 6), **f64))
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(idx_ws), idx_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_register(
+            _native.ptr(s), N, _native.ptr(wt), _native.ptr(t), _native.ptr(nm), M, float(inv), float(r2),
+            _native.ptr(idx_ws), idx_bytes, _native.ptr(T32), _native.ptr(cen), it, mp, pv, _native.ptr(ws), ws_bytes,
+            _native.ptr(out.T), _native.ptr(out.history), _native.ptr(run), _native.ptr(out.information), st),
+            "mvsn_cloud_register")
+        bits = int(status.item())      # the one host synchronisation, after the whole loop is enqueued
+    _raise_cloud_status(bits, h, "cloud_register")
     return out
 
 

@@ -40,7 +40,14 @@ composed from torch ops on the first TORCH_ALIGN_VIEWS views.  --mesh: also extr
 and reports, as "mesh", M, F, the number of components C and the largest one's share, ms per mesh_components call and per
 filter_mesh(min_faces=MESH_MIN_FACES) call (labelling included, and with the components handed in), and the labelling
 composed from torch ops -- scatter_reduce(amin) over the sides of the faces plus a pointer jump, repeated to a fixed point
-with a host read per round -- with its rounds and whether it finds the same partition."""
+with a host read per round -- with its rounds and whether it finds the same partition.  --register: also registers each scene's fused cloud, moved
+by a fixed seeded twist (REGISTER_ANGLE, REGISTER_SHIFT about the cloud's mean), back onto itself
+(fusion.cloud_register against the fused cloud with its point_normals, REGISTER_ITERATIONS iterations, max_dist
+REGISTER_MAX_DIST) point-to-plane and point-to-point and reports, as "register", ms per call and per iteration (call
+minus the call with no iteration, over the iterations), ms of one cloud_nearest query at the same max_dist, the pose
+errors before and after, the status and the history's first and last rows, and one iteration composed from torch ops
+(torch.cdist over chunks of the target, gathers, J, the sums as einsums in fp64, a Cholesky solve) on the first
+TORCH_QUERIES source points, with its extrapolation to all of them."""
 import argparse
 import json
 import os
@@ -53,8 +60,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, depth_normals,  # noqa: E402
-                                             fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
+from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, cloud_register,  # noqa: E402
+                                             depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
@@ -493,6 +500,94 @@ def run_align(sc, steps, warmup):
         "torch_pose_difference_max": float((tT - one.T_cam_in_world.double()).abs().max())}}
 
 
+REGISTER_ANGLE, REGISTER_SHIFT, REGISTER_ITERATIONS, REGISTER_MAX_DIST = 0.004, 0.02, 10, 0.04
+
+
+def torch_register_iteration(source, target, normals, T, centre, max_dist):
+    """One iteration from torch ops: the moved points, their nearest targets through torch_cloud_nearest (N x M
+    distances in chunks), the gathers, J, the sums as einsums in fp64, a Cholesky solve and the update.  `normals` None:
+    point-to-point.  Returns (new pose (4,4) fp64, count, sum r^2)."""
+    dev = source.device
+    p = source @ T[:3, :3].T + T[:3, 3]
+    _, index, _ = torch_cloud_nearest(p, target, max_dist)
+    ok = index >= 0
+    j = index.clamp(min=0)
+    d, q = p - target[j], p - centre
+    if normals is not None:
+        n = normals[j]
+        J = torch.cat([n, torch.cross(q, n, dim=-1)], -1)[:, None, :]
+        r = (d * n).sum(-1)[:, None]
+    else:
+        eye = torch.eye(3, device=dev).expand(p.shape[0], 3, 3)
+        J = torch.cat([eye, torch.cross(q[:, None, :].expand(-1, 3, -1), eye, dim=-1)], -1)
+        r = d
+    J = torch.where(ok[:, None, None], J, torch.zeros_like(J)).double().reshape(-1, 6)
+    r = torch.where(ok[:, None], r, torch.zeros_like(r)).double().reshape(-1)
+    Hm, b = J.T @ J, J.T @ r
+    s = Hm.diagonal().rsqrt()
+    L = torch.linalg.cholesky_ex(Hm * s[:, None] * s[None, :]).L           # (no host read: a failed factor gives NaNs)
+    delta = torch.cholesky_solve(-(b * s)[:, None], L)[:, 0] * s
+    w = delta[3:]
+    Wx = torch.zeros(3, 3, dtype=torch.float64, device=dev)
+    Wx[0, 1], Wx[0, 2], Wx[1, 0], Wx[1, 2], Wx[2, 0], Wx[2, 1] = -w[2], w[1], w[2], -w[0], -w[1], w[0]
+    Rd = torch.linalg.matrix_exp(Wx)
+    c = centre.double()
+    out = T.double().clone()
+    out[:3, :3] = Rd @ out[:3, :3]
+    out[:3, 3] = Rd @ (T[:3, 3].double() - c) + c + delta[:3]
+    return out, ok.sum(), (r * r).sum()
+
+
+def run_register(sc, res, steps, warmup):
+    steps, warmup = min(steps, 2), min(warmup, 1)           # (the calls are long: a second or more)
+    depth, K, T = sc["depth"], sc["K"], sc["T_cam_in_world"]
+    dev = depth.device
+    target = res.points
+    normals = point_normals(res, depth_normals(depth, K, T_cam_in_world=T))
+    centre = target.double().mean(dim=0)
+    gen = torch.Generator().manual_seed(23)
+    w = torch.nn.functional.normalize(torch.randn(3, generator=gen, dtype=torch.float64), dim=0) * REGISTER_ANGLE
+    shift = (torch.nn.functional.normalize(torch.randn(3, generator=gen, dtype=torch.float64), dim=0) * REGISTER_SHIFT).to(dev)
+    Wx = torch.zeros(3, 3, dtype=torch.float64)
+    Wx[0, 1], Wx[0, 2], Wx[1, 0], Wx[1, 2], Wx[2, 0], Wx[2, 1] = -w[2], w[1], w[2], -w[0], -w[1], w[0]
+    Rd = torch.linalg.matrix_exp(Wx).to(dev)
+    source = ((target.double() - centre) @ Rd.T + centre + shift).float()
+    T_true = torch.eye(4, dtype=torch.float64, device=dev)          # the pose that undoes the twist
+    T_true[:3, :3], T_true[:3, 3] = Rd.T, centre - Rd.T @ (centre + shift)
+    start = torch.eye(4, dtype=torch.float32)
+    N, M = int(source.shape[0]), int(target.shape[0])
+    _, qtimes = timed(lambda: cloud_nearest(source, target, REGISTER_MAX_DIST), steps, warmup)
+    out = {"n_source": N, "n_target": M, "max_dist": REGISTER_MAX_DIST, "iterations": REGISTER_ITERATIONS,
+           "angle": REGISTER_ANGLE, "shift": REGISTER_SHIFT, "cloud_nearest_ms_mean": float(np.mean(qtimes)),
+           "torch_points": min(N, TORCH_QUERIES)}
+    before = pose_errors(start[None].to(dev), T_true[None])
+    sub = source[:TORCH_QUERIES].contiguous()
+    cen32 = centre.float()
+    for mode, nm in (("plane", normals), ("point", None)):
+        kw = dict(target_normals=nm, centre=cen32.cpu(), T_init=start)
+        r, times = timed(lambda: cloud_register(source, target, REGISTER_MAX_DIST, iterations=REGISTER_ITERATIONS, **kw),
+                         steps, warmup)
+        _, ztimes = timed(lambda: cloud_register(source, target, REGISTER_MAX_DIST, iterations=0, **kw), steps, warmup)
+        after = pose_errors(r.T[None], T_true[None])
+        per_iteration = (float(np.mean(times)) - float(np.mean(ztimes))) / REGISTER_ITERATIONS
+        (tT, tcount, tcost), ttimes = timed(
+            lambda: torch_register_iteration(sub, target, nm, start.to(dev), cen32, REGISTER_MAX_DIST), 2, 1)
+        one = cloud_register(sub, target, REGISTER_MAX_DIST, iterations=1, **kw)
+        out[mode] = {
+            "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+            "zero_iteration_call_ms_mean": float(np.mean(ztimes)), "ms_per_iteration": per_iteration,
+            "ns_per_point_and_iteration": 1e6 * per_iteration / N,
+            "translation_error_before": float(before[0][0]), "translation_error_after": float(after[0][0]),
+            "rotation_error_before": float(before[1][0]), "rotation_error_after": float(after[1][0]),
+            "status": int(r.status), "history_first": r.history[0].tolist(), "history_last": r.history[-1].tolist(),
+            "information_diagonal": r.information.diagonal().tolist(),
+            "torch_ms_per_iteration_mean": float(np.mean(ttimes)),
+            "torch_ms_per_iteration_extrapolated_to_all_points": float(np.mean(ttimes)) * N / float(sub.shape[0]),
+            "torch_count_equal": bool(int(tcount) == int(one.history[0, 0])),
+            "torch_pose_difference_max": float((tT - one.T.double()).abs().max())}
+    return {"register": out}
+
+
 MESH_MIN_FACES = 200
 
 
@@ -540,7 +635,7 @@ def run_mesh(sc, steps, warmup):
 
 
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False):
+        align=False, mesh=False, register=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -562,7 +657,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     rendered = run_raycast(sc, steps, warmup) if raycast else {}
     aligned = run_align(sc, steps, warmup) if align else {}
     cleaned = run_mesh(sc, steps, warmup) if mesh else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    registered = run_register(sc, res, steps, warmup) if register else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -587,11 +683,13 @@ def main():
                     help="also align the views from perturbed poses to the TSDF volume, and the torch form of one iteration")
     ap.add_argument("--mesh", action="store_true",
                     help="also label the components of the volume's mesh and drop the small ones, and the torch form")
+    ap.add_argument("--register", action="store_true",
+                    help="also register the fused cloud, moved by a small twist, back onto itself, and the torch form")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align, a.mesh)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh, a.register)), flush=True)
 
 
 if __name__ == "__main__":
