@@ -1,6 +1,6 @@
 // What the kernels that query a cloud's hash grid share (mvsn_cloud.hip builds the grid and answers the nearest-neighbour
-// query, mvsn_cloud_register.hip matches a moved cloud against it): the workspace layout of an index, the cells a query
-// visits, and the walk of one query over them.  DESIGN.md section 14 has the semantics and the proof that the cells
+// query, mvsn_cloud_register.hip matches a moved cloud against it, mvsn_cloud_normals.hip takes every point's
+// neighbourhood from it): the workspace layout of an index, the cells a query visits, and the walk of one query over them.  DESIGN.md section 14 has the semantics and the proof that the cells
 // visited are enough.
 #pragma once
 #include "mvsn_common.h"
@@ -96,6 +96,52 @@ __device__ __forceinline__ void cloud_walk(float qx, float qy, float qz, float i
                   ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(r[3]);
               best = k < best ? k : best;
             }
+          }
+        }
+  }
+}
+
+// The visitor form of cloud_walk: the same range, probe, clamp and record loop, and the same fp32 differences and
+// d2 <= r2; every accepted record is handed to visit(dx, dy, dz, d2, record) in walk order (which depends on the order in
+// which the scatter's atomics arrived: a visitor must not let its result depend on it).  cloud_walk's own text stays as
+// it is, so that its two users compile to what they compiled to before this form existed.
+template <class Visit>
+__device__ __forceinline__ void cloud_visit(float qx, float qy, float qz, float inv, float r2,
+                                            const unsigned long long *__restrict__ keys, const int *__restrict__ pop,
+                                            const int *__restrict__ start, const floatx4 *__restrict__ records,
+                                            size_t slots, long n, Visit &&visit) {
+#pragma clang fp contract(off)
+  const float tx = qx * inv, ty = qy * inv, tz = qz * inv;
+  if (isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(tx) && isfinite(ty) && isfinite(tz)) {
+    const float reach = r2 < 0x1p-100f ? 2.0f : 1.0f;
+    int lo[3], hi[3];
+    cloud_cell_range(tx, reach, lo + 0, hi + 0);
+    cloud_cell_range(ty, reach, lo + 1, hi + 1);
+    cloud_cell_range(tz, reach, lo + 2, hi + 2);
+    const size_t mask = slots - 1;
+    int c[3];
+    for (c[0] = lo[0]; c[0] <= hi[0]; ++c[0])
+      for (c[1] = lo[1]; c[1] <= hi[1]; ++c[1])
+        for (c[2] = lo[2]; c[2] <= hi[2]; ++c[2]) {
+          const unsigned long long key = voxel_key(c);
+          size_t h = (size_t)voxel_hash(key) & mask;
+          long from = 0, to = 0;
+          for (size_t probe = 0; probe < slots; ++probe) {  // bounded: every slot at most once
+            const unsigned long long seen = keys[h];
+            if (seen == key) {
+              from = (long)start[h];
+              to = from + (long)pop[h];
+              break;
+            }
+            if (seen == VX_EMPTY) break;
+            h = (h + 1) & mask;
+          }
+          from = max(from, 0L), to = min(to, n);
+          for (long j = from; j < to; ++j) {
+            const floatx4 r = records[j];
+            const float dx = qx - r[0], dy = qy - r[1], dz = qz - r[2];
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 <= r2) visit(dx, dy, dz, d2, r);
           }
         }
   }

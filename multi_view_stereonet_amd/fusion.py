@@ -13,7 +13,9 @@ camera; ``point_normals`` reads those maps at the points of a fused cloud and ``
 another within a radius, exactly; ``radius_outlier_mask`` is the same query of a cloud against itself
 (``metrics.cloud_metrics`` builds accuracy / completeness / F-score on it).  ``cloud_register`` (DESIGN.md section 20,
 csrc/mvsn_cloud_register.hip) moves one cloud onto another by ICP on that query, point-to-plane or point-to-point, and
-``cloud_register_system`` is one evaluation of its normal equations.  A dense TSDF volume that integrates the same
+``cloud_register_system`` is one evaluation of its normal equations; ``cloud_normals`` (DESIGN.md section 21,
+csrc/mvsn_cloud_normals.hip) gives a bare cloud the normals that the point-to-plane mode needs, from the covariance of
+every point's neighbours within a radius.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -477,6 +479,115 @@ def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) ->
                          f"cells of {float(h):g} or more from the origin")
     if bits:
         raise RuntimeError(f"cloud_nearest: the hash grid overflowed (status {bits})")
+    return out
+
+
+class CloudNormals(NamedTuple):
+    normals: torch.Tensor            # (N,3) fp32: unit normal, (0,0,0) where the direction is not defined
+    eigenvalues: torch.Tensor        # (N,3) fp32: of the neighbourhood's covariance, ascending, squared world units
+    count: torch.Tensor              # (N,) int32: support points within the radius (cloud_nearest's `within`)
+
+
+def _check_viewpoint(viewpoint, N, dev):
+    """None, or the viewpoint as a (1,3) or (N,3) float32 tensor (three numbers stay where they are until the launch);
+    ValueError for anything that is neither three numbers nor an (N,3) float32 tensor on the points' device."""
+    if viewpoint is None:
+        return None
+    if torch.is_tensor(viewpoint) and viewpoint.dim() == 2:
+        if tuple(viewpoint.shape) != (N, 3) or viewpoint.dtype != torch.float32:
+            raise ValueError(f"viewpoint must be three numbers or a ({N},3) float32 tensor")
+        if viewpoint.device != dev:
+            raise ValueError(f"viewpoint is on {viewpoint.device}, points on {dev}")
+        return viewpoint.detach().contiguous()
+    if torch.is_tensor(viewpoint):     # a (3,) tensor stays where it is until the launch: nothing waits for the device
+        if tuple(viewpoint.shape) != (3,) or viewpoint.dtype == torch.bool or viewpoint.is_complex() or \
+                viewpoint.device.type == "meta":
+            raise ValueError(f"viewpoint must be three numbers or a ({N},3) float32 tensor")
+        return viewpoint.detach().to(torch.float32).reshape(1, 3)
+    try:
+        with np.errstate(all="ignore"):
+            v = np.asarray(viewpoint, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"viewpoint must be three numbers or a ({N},3) float32 tensor, got {viewpoint!r}") from None
+    if v.shape != (3,):
+        raise ValueError(f"viewpoint must be three numbers or a ({N},3) float32 tensor, got {viewpoint!r}")
+    return torch.from_numpy(v.reshape(1, 3))
+
+
+def cloud_normals(points: torch.Tensor, radius: float, *, support: Optional[torch.Tensor] = None, viewpoint=None,
+                  min_neighbours: int = 3, min_gap: float = 2.0 ** -20) -> CloudNormals:
+    """A normal for every row of ``points`` (N,3) fp32 from the covariance of the rows of ``support`` (M,3) fp32 within
+    ``radius`` of it (PCA; DESIGN.md section 21, csrc/mvsn_cloud_normals.hip).  ``support`` defaults to ``points``
+    itself: a point is then its own neighbour, as in ``radius_outlier_mask``.  Neither cloud needs depth maps, a
+    volume or any order: this is where ``cloud_register``'s ``target_normals`` come from for a bare cloud.
+
+    ``count`` is exactly ``cloud_nearest(points, support, radius).within``.  ``eigenvalues`` are those of the
+    neighbourhood's covariance, ascending, in squared world units.  ``normals`` is the unit eigenvector of the smallest,
+    and (0,0,0) where ``count < min_neighbours`` (an integer >= 3), where the point is not finite, and where
+    ``lambda_1 - lambda_0 <= min_gap * lambda_2`` (``min_gap`` in [0, 1)): collinear or coincident neighbours or an
+    isotropic blob, which define no direction.
+
+    The sign: with ``viewpoint`` (three numbers, a (3,) tensor, or an (N,3) fp32 tensor such as
+    ``T_cam_in_world[res.view, :3, 3]``) every normal is flipped so that ``n . (viewpoint - p) >= 0``.  Without one,
+    where that product is 0 and where a viewpoint row is not finite the sign is canonical: the component of largest
+    magnitude is positive, ties going to the lowest axis.  Point-to-plane registration does not care about the sign.
+
+    The differences of the neighbours are quantised to 2^-20 of the radius and summed as exact integers; the
+    covariance, six cyclic Jacobi sweeps and the sign rule run in fp64, and every output number is rounded to fp32
+    once.  Every output is a bitwise-reproducible function of the inputs and does not depend on the order of
+    ``support``'s rows.  A point with more than 2^20 support points within ``radius`` gets the zero normal and zero
+    eigenvalues (the sums could overflow; its count is still exact).  As for ``cloud_nearest``, the time grows with
+    (support points per cell) x (cells visited, 27 almost always): a ``radius`` far above the sampling distance is
+    quadratic within a neighbourhood, and a finite support point more than 2^20 cells of ``radius`` from the origin
+    raises ValueError.  Everything is validated here, before any launch; the one host synchronisation is the read of
+    the index build's status word, after everything is enqueued."""
+    check_cloud("points", points)
+    own = support is None
+    if own:
+        support = points
+    check_cloud("support", support)
+    dev = points.device
+    if support.device != dev:
+        raise ValueError(f"support is on {support.device}, points on {dev}")
+    h, inv, r2 = cloud_radius_scalars(radius, "radius")
+    N, M = int(points.shape[0]), int(support.shape[0])
+    k = _integer_in(min_neighbours, "min_neighbours", 3, 2 ** 62)
+    try:
+        gap = float(min_gap)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_gap must be a number in [0, 1), got {min_gap!r}") from None
+    if not 0.0 <= gap < 1.0:
+        raise ValueError(f"min_gap must be a number in [0, 1), got {min_gap!r}")
+    view = _check_viewpoint(viewpoint, N, dev)
+    if N == 0 or M == 0:               # no neighbourhood, nothing to launch
+        return CloudNormals(torch.zeros((N, 3), dtype=torch.float32, device=dev),
+                            torch.zeros((N, 3), dtype=torch.float32, device=dev),
+                            torch.zeros((N,), dtype=torch.int32, device=dev))
+    if not points.is_cuda:
+        raise RuntimeError("cloud_normals runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    q = points.detach().contiguous()
+    t = q if own else support.detach().contiguous()
+    if view is not None:
+        view = view.to(dev).contiguous()
+    rows = 0 if view is None else int(view.shape[0])
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(M)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    out = CloudNormals(torch.empty((N, 3), dtype=torch.float32, device=dev),
+                       torch.empty((N, 3), dtype=torch.float32, device=dev),
+                       torch.empty((N,), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_normals(_native.ptr(q), N, _native.ptr(view), rows, float(h), float(inv), float(r2),
+                                             k, gap, _native.ptr(ws), ws_bytes, M, _native.ptr(out.normals),
+                                             _native.ptr(out.eigenvalues), _native.ptr(out.count), st),
+                      "mvsn_cloud_normals")
+        bits = int(status.item())      # the one host synchronisation, after everything is enqueued
+    _raise_cloud_status(bits, h, "cloud_normals")   # (cloud_nearest's errors: the support is the index's target, radius its max_dist)
     return out
 
 

@@ -47,7 +47,13 @@ REGISTER_MAX_DIST) point-to-plane and point-to-point and reports, as "register",
 minus the call with no iteration, over the iterations), ms of one cloud_nearest query at the same max_dist, the pose
 errors before and after, the status and the history's first and last rows, and one iteration composed from torch ops
 (torch.cdist over chunks of the target, gathers, J, the sums as einsums in fp64, a Cholesky solve) on the first
-TORCH_QUERIES source points, with its extrapolation to all of them."""
+TORCH_QUERIES source points, with its extrapolation to all of them.  --cloud-normals: also estimates the normals of each
+scene's fused cloud from the bare points (fusion.cloud_normals at radius NORMALS_RADIUS, facing every point's own camera)
+and reports, as "cloud_normals", ms per call, the share of points that got a normal, the angle to point_normals of the same
+cloud (mean and p99), ms of one cloud_nearest query of the cloud against itself at the same radius (the walk is the same:
+the difference is the cost of the moments and the eigen-solve), and the composition from torch ops (torch.cdist over
+chunks of the cloud, the moments as fp64 matrix products, torch.linalg.eigh) on the first TORCH_QUERIES points, with its
+extrapolation to all of them."""
 import argparse
 import json
 import os
@@ -60,7 +66,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_radius_scalars, cloud_register,  # noqa: E402
+from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_normals, cloud_radius_scalars, cloud_register,  # noqa: E402
                                              depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
@@ -588,6 +594,68 @@ def run_register(sc, res, steps, warmup):
     return {"register": out}
 
 
+NORMALS_RADIUS = REGISTER_MAX_DIST                      # the radius the registration above matches within
+TORCH_NORMALS_CHUNK = 1 << 17
+
+
+def torch_cloud_normals(query, cloud, radius):
+    """The normals from torch ops (what a caller had to write without cloud_normals): the neighbours through torch.cdist
+    over chunks of the cloud, the count and the first and second moments as fp64 matrix products with the 0/1 mask, the
+    covariance, torch.linalg.eigh.  Returns (unit eigenvector of the smallest eigenvalue (Q,3) fp64, count (Q,))."""
+    Q = query.shape[0]
+    cnt = torch.zeros(Q, dtype=torch.float64, device=query.device)
+    S = torch.zeros(Q, 3, dtype=torch.float64, device=query.device)
+    SS = torch.zeros(Q, 9, dtype=torch.float64, device=query.device)
+    for a in range(0, cloud.shape[0], TORCH_NORMALS_CHUNK):
+        part = cloud[a:a + TORCH_NORMALS_CHUNK]
+        w = (torch.cdist(query, part) <= radius).double()
+        p = part.double()
+        cnt += w.sum(dim=1)
+        S += w @ p
+        SS += w @ (p[:, :, None] * p[:, None, :]).reshape(-1, 9)
+    n = cnt.clamp(min=1.0)[:, None]
+    m = S / n
+    C = (SS / n).reshape(Q, 3, 3) - m[:, :, None] * m[:, None, :]
+    _, E = torch.linalg.eigh(C)
+    return E[:, :, 0], cnt
+
+
+def _angles(a, b, line=False):
+    a, b = a.double(), b.double()
+    ang = torch.atan2(torch.linalg.cross(a, b).norm(dim=1), (a * b).sum(dim=1))
+    return torch.minimum(ang, np.pi - ang) if line else ang
+
+
+def run_cloud_normals(sc, res, steps, warmup):
+    steps, warmup = min(steps, 3), min(warmup, 1)           # (the calls are long: a tenth of a second or more)
+    depth, K, T = sc["depth"], sc["K"], sc["T_cam_in_world"]
+    points = res.points
+    N = int(points.shape[0])
+    centres = T[res.view.long(), :3, 3].float().contiguous()
+    got, times = timed(lambda: cloud_normals(points, NORMALS_RADIUS, viewpoint=centres), steps, warmup)
+    nn, qtimes = timed(lambda: cloud_nearest(points, points, NORMALS_RADIUS), steps, warmup)
+    assert torch.equal(nn.within, got.count)
+    truth = point_normals(res, depth_normals(depth, K, T_cam_in_world=T))
+    has = (got.normals != 0).any(dim=1)
+    both = has & (truth != 0).any(dim=1)
+    ang = _angles(got.normals[both], truth[both]).sort().values
+    sub = points[:TORCH_QUERIES].contiguous()
+    (tn, tcount), ttimes = timed(lambda: torch_cloud_normals(sub, points, NORMALS_RADIUS), 2, 1)
+    sub_has = has[:TORCH_QUERIES]
+    scale = N / float(sub.shape[0])
+    return {"cloud_normals": {
+        "n_points": N, "radius": NORMALS_RADIUS, "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+        "ns_per_point": 1e6 * float(np.mean(times)) / N, "cloud_nearest_ms_mean": float(np.mean(qtimes)),
+        "neighbours_mean": float(got.count.float().mean()), "neighbours_max": int(got.count.max()),
+        "share_with_normal": float(has.float().mean()), "compared_with_point_normals": int(both.sum()),
+        "angle_to_point_normals_mean": float(ang.mean()), "angle_to_point_normals_p99": float(ang[int(0.99 * (len(ang) - 1))]),
+        "torch_points": int(sub.shape[0]), "torch_ms_mean": float(np.mean(ttimes)),
+        "torch_ms_extrapolated_to_all_points": float(np.mean(ttimes)) * scale,
+        "torch_count_differs": int((tcount.long() != got.count[:TORCH_QUERIES].long()).sum()),
+        "torch_line_angle_max": float(_angles(tn[sub_has], got.normals[:TORCH_QUERIES][sub_has], line=True).max())
+        if bool(sub_has.any()) else 0.0}}
+
+
 MESH_MIN_FACES = 200
 
 
@@ -635,7 +703,7 @@ def run_mesh(sc, steps, warmup):
 
 
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -658,7 +726,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     aligned = run_align(sc, steps, warmup) if align else {}
     cleaned = run_mesh(sc, steps, warmup) if mesh else {}
     registered = run_register(sc, res, steps, warmup) if register else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    estimated = run_cloud_normals(sc, res, steps, warmup) if cloud_normals_too else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -685,11 +754,13 @@ def main():
                     help="also label the components of the volume's mesh and drop the small ones, and the torch form")
     ap.add_argument("--register", action="store_true",
                     help="also register the fused cloud, moved by a small twist, back onto itself, and the torch form")
+    ap.add_argument("--cloud-normals", action="store_true",
+                    help="also estimate the fused cloud's normals from its bare points (cloud_normals), and the torch form")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align, a.mesh, a.register)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals)), flush=True)
 
 
 if __name__ == "__main__":
