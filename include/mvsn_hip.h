@@ -741,6 +741,38 @@ int mvsn_cloud_normals(const float *query, long nq, const float *viewpoint, long
                        mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The k nearest neighbours between two clouds within a radius, and the statistics of the statistical outlier filter
+ * (multi_view_stereonet_amd/fusion.py: cloud_knn, statistical_outlier_mask; the semantics are DESIGN.md section 22).
+ * The target's index is mvsn_cloud_index_build's (index_workspace, its mvsn_cloud_workspace_bytes(n_target) bytes; cell,
+ * inv_cell and r2 as given to the build and to mvsn_cloud_nearest): built once, it serves any number of query sets.
+ * mvsn_cloud_knn: one thread per query point.
+ *   query (nq,3) fp32, 1 <= nq <= 2^31 - 1; 1 <= k <= 64; exclude_self 0 or not 0
+ *   A target is a candidate exactly when mvsn_cloud_nearest counts it (its fp32 d2 <= r2; a NaN never is) and, with
+ *   exclude_self, its row is not the query's row.  The key of a candidate is (uint64(bits of d2) << 32) | row; the result
+ *   is the k least keys in ascending order: that of the brute force over every target and a stable sort on (d2, row),
+ *   whatever the order of the target's rows in the index.
+ *   -> dist2 (nq,k) fp32 and index (nq,k) int64, row-major: slot j the j-th nearest, +inf and -1 from the number of
+ *      candidates on   within (nq) int32: the number of candidates   mean (nq) fp64 or NULL:
+ *      (sum_j sqrt((double)dist2[j])) / k, summed for j = 0 .. k-1 in that order from 0, one fp64 operation per step; NaN
+ *      with fewer than k candidates.  Every element written once.
+ *   A query with a non-finite coordinate gets all +inf / -1, within 0 and mean NaN; a non-finite target is nobody's
+ *   neighbour; a query may lie anywhere.  mvsn_cloud_knn at k = 1 is mvsn_cloud_nearest bit for bit.
+ * mvsn_cloud_mean_stats: mean (n) fp64, 1 <= n <= 2^31 - 1 -> stats (3) fp64 = (count, mu, sigma) over the entries that
+ *   are not NaN: mu = (sum m) / count (NaN for count 0), sigma = sqrt((sum (m - mu)^2) / (count - 1)) (0 for count < 2),
+ *   two passes.  Both sums in fp64 in an order that n alone fixes (at most 1024 workgroups, each on blocks of 1024 rows
+ *   1024 blocks apart, then one workgroup over their records).
+ *   workspace: mvsn_cloud_mean_stats_workspace_bytes(n) bytes (0 for what the entry refuses), 16-byte aligned.
+ * No atomics, nothing waits on another workgroup, nothing is read on the host: every output is a bitwise-reproducible
+ * function of the inputs.
+ * ------------------------------------------------------------------------------------------- */
+int mvsn_cloud_knn(const float *query, long nq, int k, int exclude_self, float cell, float inv_cell, float r2,
+                   const void *index_workspace, size_t index_workspace_bytes, long n_target, float *dist2,
+                   int64_t *index, int *within, double *mean, mvsn_stream_t stream);
+size_t mvsn_cloud_mean_stats_workspace_bytes(long n);
+int mvsn_cloud_mean_stats(const double *mean, long n, void *workspace, size_t workspace_bytes, double *stats,
+                          mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dense TSDF volume: depth maps integrated along the viewing rays, and a mesh taken from the volume by Surface Nets
  * (multi_view_stereonet_amd/tsdf.py; the semantics, every fp32 step and the error bounds are DESIGN.md section 15).
  * The state is planar fp32 in the layout (nz,ny,nx), x fastest: sdf_sum = sum w t, weight = sum w, color_sum

@@ -134,6 +134,10 @@ SIGNATURES = {
                             [c_void_p] * 4 + [c_void_p]),
     "mvsn_cloud_normals": (c_int, [c_void_p, c_long, c_void_p, c_long] + [ctypes.c_float] * 3 + [c_long, ctypes.c_double] +
                            [c_void_p, c_size_t, c_long] + [c_void_p] * 3 + [c_void_p]),
+    "mvsn_cloud_knn": (c_int, [c_void_p, c_long, c_int, c_int] + [ctypes.c_float] * 3 + [c_void_p, c_size_t, c_long] +
+                       [c_void_p] * 4 + [c_void_p]),
+    "mvsn_cloud_mean_stats_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_cloud_mean_stats": (c_int, [c_void_p, c_long, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mvsn_tsdf_camera_batch": (c_int, []),
     "mvsn_tsdf_integrate": (c_int, [c_void_p] * 6 + [c_int] * 6 + [ctypes.c_float] * 6 + [c_void_p] * 3 + [c_void_p]),
     "mvsn_tsdf_workspace_bytes": (c_size_t, [c_int] * 3),

@@ -15,7 +15,9 @@ another within a radius, exactly; ``radius_outlier_mask`` is the same query of a
 csrc/mvsn_cloud_register.hip) moves one cloud onto another by ICP on that query, point-to-plane or point-to-point, and
 ``cloud_register_system`` is one evaluation of its normal equations; ``cloud_normals`` (DESIGN.md section 21,
 csrc/mvsn_cloud_normals.hip) gives a bare cloud the normals that the point-to-plane mode needs, from the covariance of
-every point's neighbours within a radius.  A dense TSDF volume that integrates the same
+every point's neighbours within a radius.  ``cloud_knn`` (csrc/mvsn_cloud_knn.hip) returns the k
+nearest neighbours within a radius themselves, and ``statistical_outlier_mask`` is the statistical outlier filter on it,
+whose threshold follows the cloud's own spacing.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -810,6 +812,134 @@ def radius_outlier_mask(points: torch.Tensor, radius: float, min_neighbours: int
         return torch.zeros((0,), dtype=torch.bool, device=points.device)
     nn = cloud_nearest(points, points, radius)
     return (nn.within - 1 >= k) & torch.isfinite(points).all(dim=1)
+
+
+class CloudKNN(NamedTuple):
+    dist2: torch.Tensor              # (N,k) fp32: squared distances to the k nearest target points, ascending; +inf past the last
+    index: torch.Tensor              # (N,k) int64: their rows, -1 past the last
+    within: torch.Tensor             # (N,) int32: number of candidates (target points within max_dist, less the point itself with exclude_self)
+
+
+class CloudOutliers(NamedTuple):
+    keep: torch.Tensor               # (N,) bool: mean_dist <= mean + std_ratio * std
+    mean_dist: torch.Tensor          # (N,) fp64: mean distance to the k nearest other points, NaN with fewer than k within max_dist
+    mean: torch.Tensor               # () fp64, on the device: mean of mean_dist over the points that have one
+    std: torch.Tensor                # () fp64, on the device: their sample standard deviation
+
+
+CLOUD_KNN_MAX = 64
+
+
+def _check_knn(query, target, k, max_dist, exclude_self, names=("query", "target")):
+    """The validation of ``cloud_knn``: (N, T, dev, k, h, inv, r2)."""
+    check_cloud(names[0], query)
+    check_cloud(names[1], target)
+    if query.device != target.device:
+        raise ValueError(f"{names[0]} is on {query.device}, {names[1]} on {target.device}")
+    h, inv, r2 = cloud_radius_scalars(max_dist)
+    kk = _integer_in(k, "k", 1, CLOUD_KNN_MAX)
+    N, T = int(query.shape[0]), int(target.shape[0])
+    if exclude_self and N != T:
+        raise ValueError(f"exclude_self needs query and target to be the same cloud: {N} query rows, {T} target rows")
+    return N, T, query.device, kk, h, inv, r2
+
+
+def _cloud_knn(who, query, target, N, T, dev, k, h, inv, r2, exclude_self, with_mean):
+    """(CloudKNN, mean (N,) fp64 or None): the launches of ``cloud_knn`` after its validation."""
+    if N == 0 or T == 0:               # nothing to find, nothing to launch
+        out = CloudKNN(torch.full((N, k), float("inf"), dtype=torch.float32, device=dev),
+                       torch.full((N, k), -1, dtype=torch.int64, device=dev),
+                       torch.zeros((N,), dtype=torch.int32, device=dev))
+        return out, (torch.full((N,), float("nan"), dtype=torch.float64, device=dev) if with_mean else None)
+    if not query.is_cuda:
+        raise RuntimeError(f"{who} runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    q = query.detach().contiguous()
+    t = q if target is query else target.detach().contiguous()
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(T)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    out = CloudKNN(torch.empty((N, k), dtype=torch.float32, device=dev),
+                   torch.empty((N, k), dtype=torch.int64, device=dev),
+                   torch.empty((N,), dtype=torch.int32, device=dev))
+    mean = torch.empty((N,), dtype=torch.float64, device=dev) if with_mean else None
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), T, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_knn(_native.ptr(q), N, k, 1 if exclude_self else 0, float(h), float(inv), float(r2),
+                                         _native.ptr(ws), ws_bytes, T, _native.ptr(out.dist2), _native.ptr(out.index),
+                                         _native.ptr(out.within), _native.ptr(mean), st), "mvsn_cloud_knn")
+        bits = int(status.item())      # the one host synchronisation, after the query is enqueued
+    _raise_cloud_status(bits, h, who)
+    return out, mean
+
+
+def cloud_knn(query: torch.Tensor, target: torch.Tensor, k: int, max_dist: float = None, *,
+              exclude_self: bool = False) -> CloudKNN:
+    """For every row of ``query`` (N,3) fp32 the ``k`` (1 to 64) nearest rows of ``target`` (T,3) fp32 within
+    ``max_dist`` (PCL's and Open3D's hybrid search; DESIGN.md section 22, csrc/mvsn_cloud_knn.hip): their squared
+    distances in ascending order, their rows, and how many candidates there were.  Neither cloud needs any order.
+
+    A target is a candidate exactly when ``cloud_nearest`` counts it: ``(dx*dx + dy*dy) + dz*dz <= h*h`` of the fp32
+    differences with h = float32(max_dist).  With ``exclude_self`` (``query`` and ``target`` must then have the same
+    number of rows: the same cloud) the target row equal to the query's row is no candidate; its exact duplicates are.
+    Ties in the distance go to the lowest target row.  The result is exactly that of the brute force over every target
+    point and a stable sort on (distance, row): it is a bitwise-reproducible function of the inputs, and permuting the
+    target's rows changes nothing but the rows reported.  Slots from the number of candidates on hold (+inf, -1).
+    ``cloud_knn(q, t, 1, h)`` is ``cloud_nearest(q, t, h)`` bit for bit.  A target with a non-finite coordinate is
+    nobody's neighbour, a query with one gets all (+inf, -1) and 0, and a query may lie anywhere.
+
+    As for ``cloud_nearest``, the time grows with (targets per cell) x (cells visited, 27 almost always): a ``max_dist``
+    far above the sampling distance is quadratic within a neighbourhood, and a finite target more than 2^20 cells of
+    ``max_dist`` from the origin raises ValueError.  ``max_dist`` is required: leaving it out is a ValueError like any
+    other bad radius.  Everything is validated here, before any launch; the one host synchronisation is the read of the
+    index build's status word, after the query is enqueued."""
+    N, T, dev, kk, h, inv, r2 = _check_knn(query, target, k, max_dist, exclude_self)
+    return _cloud_knn("cloud_knn", query, target, N, T, dev, kk, h, inv, r2, bool(exclude_self), False)[0]
+
+
+def statistical_outlier_mask(points: torch.Tensor, k: int, std_ratio: float, max_dist: float = None) -> CloudOutliers:
+    """The statistical outlier filter of PCL (``StatisticalOutlierRemoval``) and Open3D (``remove_statistical_outlier``)
+    on ``points`` (N,3) fp32: ``mean_dist`` is every point's mean distance to its ``k`` (1 to 64) nearest OTHER points
+    (``cloud_knn(points, points, k, max_dist, exclude_self=True)``: exact duplicates count, at distance 0, as in
+    ``radius_outlier_mask``), ``mean`` and ``std`` are the mean and the sample standard deviation of ``mean_dist`` over
+    the cloud, and ``keep = mean_dist <= mean + std_ratio * std`` (``std_ratio`` a finite number >= 0).  Unlike
+    ``radius_outlier_mask`` the threshold follows the cloud's own spacing.
+
+    A point with fewer than ``k`` other points within ``max_dist``, or with a non-finite coordinate, has ``mean_dist``
+    NaN: it gets ``keep`` False and enters neither ``mean`` nor ``std``.  ``max_dist`` bounds the search (and its cost,
+    as for ``cloud_nearest``); choose it several times the spacing of the sparsest part that should be kept.
+
+    ``mean_dist`` is the fp64 sum of the k fp64 square roots in order of distance, over k; ``mean`` and ``std`` are
+    two-pass fp64 sums in an order that N alone fixes; the comparison runs on the device in fp64.  Nothing is read on
+    the host but the index build's status word: every output is a bitwise-reproducible function of the inputs.
+    Everything is validated here, before any launch."""
+    N, _, dev, kk, h, inv, r2 = _check_knn(points, points, k, max_dist, True, names=("points", "points"))
+    try:
+        ratio = float(std_ratio)
+        if isinstance(std_ratio, (bool, str)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"std_ratio must be a finite number >= 0, got {std_ratio!r}") from None
+    if not (np.isfinite(ratio) and ratio >= 0.0):
+        raise ValueError(f"std_ratio must be a finite number >= 0, got {std_ratio!r}")
+    if N == 0:
+        return CloudOutliers(torch.zeros((0,), dtype=torch.bool, device=dev),
+                             torch.zeros((0,), dtype=torch.float64, device=dev),
+                             torch.full((), float("nan"), dtype=torch.float64, device=dev),
+                             torch.zeros((), dtype=torch.float64, device=dev))
+    _, mean_dist = _cloud_knn("statistical_outlier_mask", points, points, N, N, dev, kk, h, inv, r2, True, True)
+    lib = _native.load()
+    ws_bytes = lib.mvsn_cloud_mean_stats_workspace_bytes(N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    stats = torch.empty((3,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_cloud_mean_stats(_native.ptr(mean_dist), N, _native.ptr(ws), ws_bytes, _native.ptr(stats),
+                                                _native.stream()), "mvsn_cloud_mean_stats")
+    keep = mean_dist <= stats[1] + ratio * stats[2]          # (a NaN compares false)
+    return CloudOutliers(keep, mean_dist, stats[1], stats[2])
 
 
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:

@@ -53,7 +53,13 @@ and reports, as "cloud_normals", ms per call, the share of points that got a nor
 cloud (mean and p99), ms of one cloud_nearest query of the cloud against itself at the same radius (the walk is the same:
 the difference is the cost of the moments and the eigen-solve), and the composition from torch ops (torch.cdist over
 chunks of the cloud, the moments as fp64 matrix products, torch.linalg.eigh) on the first TORCH_QUERIES points, with its
-extrapolation to all of them."""
+extrapolation to all of them.  --knn: also searches each scene's fused cloud for every point's k nearest other points
+(fusion.cloud_knn of the cloud against itself, exclude_self, within KNN_RADIUS) at k = 8 and 32 and filters it
+(fusion.statistical_outlier_mask, k = 8, std_ratio 2) and reports, as "knn", ms per call, ms of one cloud_nearest query of
+the cloud against itself at the same radius (the same walk: the floor), the share of points with fewer than k neighbours,
+ms per statistical_outlier_mask call and the share kept, and the search composed from torch ops (torch.cdist over chunks of
+the cloud, topk per chunk, topk over the chunks' winners) on the first TORCH_QUERIES points, with its extrapolation to
+all of them."""
 import argparse
 import json
 import os
@@ -66,8 +72,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (cloud_nearest, cloud_normals, cloud_radius_scalars, cloud_register,  # noqa: E402
-                                             depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
+from multi_view_stereonet_amd.fusion import (cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
+                                             cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
@@ -656,6 +662,64 @@ def run_cloud_normals(sc, res, steps, warmup):
         if bool(sub_has.any()) else 0.0}}
 
 
+KNN_RADIUS = NORMALS_RADIUS
+KNN_K = (8, 32)
+KNN_STD_RATIO = 2.0
+
+
+def torch_cloud_knn(query, cloud, k, radius):
+    """The k nearest other points from torch ops (what a caller had to write without cloud_knn): torch.cdist over chunks of
+    the cloud, the point itself masked, topk per chunk, topk over the chunks' winners.  cdist's own arithmetic: at these sizes
+    it takes the matrix-product form, whose error in d^2 (about 1e-7 of the coordinates' squares) is of the size of a nearest
+    neighbour's d^2 itself, so its distances and with them its neighbours differ from the exact ones (the result reports by
+    how much); its other form refuses a launch of this size.  The first rows of `cloud` are `query`.  Returns (dist (Q,k), index (Q,k))."""
+    Q = query.shape[0]
+    own = torch.arange(Q, device=query.device)
+    best_d = torch.full((Q, k), float("inf"), device=query.device)
+    best_i = torch.full((Q, k), -1, dtype=torch.int64, device=query.device)
+    for a in range(0, cloud.shape[0], TORCH_NORMALS_CHUNK):
+        d = torch.cdist(query, cloud[a:a + TORCH_NORMALS_CHUNK])
+        if a < Q:
+            rows = own[a:a + d.shape[1]]
+            d[rows, rows - a] = float("inf")
+        d = torch.where(d <= radius, d, torch.full((), float("inf"), device=d.device))
+        cd, ci = torch.topk(d, min(k, d.shape[1]), dim=1, largest=False)
+        md, mi = torch.cat([best_d, cd], dim=1), torch.cat([best_i, ci + a], dim=1)
+        best_d, pick = torch.topk(md, k, dim=1, largest=False)
+        best_i = torch.gather(mi, 1, pick)
+    return best_d, torch.where(torch.isinf(best_d), torch.full_like(best_i, -1), best_i)
+
+
+def run_knn(res, steps, warmup):
+    steps, warmup = min(steps, 3), min(warmup, 1)           # (the calls are long: a tenth of a second or more)
+    points = res.points
+    N = int(points.shape[0])
+    nn, qtimes = timed(lambda: cloud_nearest(points, points, KNN_RADIUS), steps, warmup)
+    out = {"n_points": N, "radius": KNN_RADIUS, "cloud_nearest_ms_mean": float(np.mean(qtimes)),
+           "neighbours_mean": float(nn.within.float().mean()) - 1.0, "neighbours_max": int(nn.within.max()) - 1}
+    sub = points[:TORCH_QUERIES].contiguous()
+    scale = N / float(sub.shape[0])
+    for k in KNN_K:
+        got, times = timed(lambda: cloud_knn(points, points, k, KNN_RADIUS, exclude_self=True), steps, warmup)
+        assert torch.equal(got.within, nn.within - torch.isfinite(points).all(dim=1).int())
+        (td, ti), ttimes = timed(lambda: torch_cloud_knn(sub, points, k, KNN_RADIUS), 2, 1)
+        mine = got.dist2[:TORCH_QUERIES].sqrt()
+        both = torch.isfinite(mine) & torch.isfinite(td)
+        out["k%d" % k] = {
+            "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+            "ns_per_point": 1e6 * float(np.mean(times)) / N, "share_with_fewer_than_k": float((got.within < k).float().mean()),
+            "torch_points": int(sub.shape[0]), "torch_ms_mean": float(np.mean(ttimes)),
+            "torch_ms_extrapolated_to_all_points": float(np.mean(ttimes)) * scale,
+            "torch_distance_differs_max": float((mine[both] - td[both]).abs().max()) if bool(both.any()) else 0.0,
+            "torch_index_differs": int((ti != got.index[:TORCH_QUERIES]).sum())}
+    sor, stimes = timed(lambda: statistical_outlier_mask(points, KNN_K[0], KNN_STD_RATIO, KNN_RADIUS), steps, warmup)
+    out["statistical_outlier_mask"] = {
+        "k": KNN_K[0], "std_ratio": KNN_STD_RATIO, "ms_per_call_mean": float(np.mean(stimes)), "ms_per_call_min": float(np.min(stimes)),
+        "share_kept": float(sor.keep.float().mean()), "share_without_k_neighbours": float(torch.isnan(sor.mean_dist).float().mean()),
+        "mean": float(sor.mean), "std": float(sor.std)}
+    return {"knn": out}
+
+
 MESH_MIN_FACES = 200
 
 
@@ -703,7 +767,7 @@ def run_mesh(sc, steps, warmup):
 
 
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -727,7 +791,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     cleaned = run_mesh(sc, steps, warmup) if mesh else {}
     registered = run_register(sc, res, steps, warmup) if register else {}
     estimated = run_cloud_normals(sc, res, steps, warmup) if cloud_normals_too else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    searched = run_knn(res, steps, warmup) if knn else {}
+    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -756,11 +821,14 @@ def main():
                     help="also register the fused cloud, moved by a small twist, back onto itself, and the torch form")
     ap.add_argument("--cloud-normals", action="store_true",
                     help="also estimate the fused cloud's normals from its bare points (cloud_normals), and the torch form")
+    ap.add_argument("--knn", action="store_true",
+                    help="also search the fused cloud for every point's k nearest others (cloud_knn) and filter it "
+                         "(statistical_outlier_mask), and the torch form of the search")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn)), flush=True)
 
 
 if __name__ == "__main__":
