@@ -773,6 +773,64 @@ int mvsn_cloud_mean_stats(const double *mean, long n, void *workspace, size_t wo
                           mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Global registration of two clouds: FPFH descriptors, nearest neighbours in descriptor space, RANSAC over the
+ * correspondences (multi_view_stereonet_amd/fusion.py: cloud_fpfh, feature_nearest, cloud_ransac, cloud_register_global;
+ * the semantics and the exact arithmetic of every step are DESIGN.md section 23).
+ * mvsn_cloud_fpfh: points and normals (n,3) fp32, 1 <= n <= 2^31 - 1; the index is mvsn_cloud_index_build's of the points
+ *   themselves (index_workspace, its mvsn_cloud_workspace_bytes(n) bytes; cell = radius, inv_cell and r2 as given to the
+ *   build); min_neighbours >= 1.  Two launches, one thread per point.
+ *   A pair (i, j) counts when mvsn_cloud_nearest counts j for i (fp32 d2 <= r2), j != i, d2 != 0 and both normals are
+ *   finite and not (0,0,0).  Its Darboux triple, every step one fp32 operation: e = p_j - p_i, a_i = n_i . e, a_j = n_j . e
+ *   ((x + y) + z); the source s is i where |a_i| > |a_j|, j where |a_j| > |a_i|, the lower row at a tie; u = n_s,
+ *   l = (p_t - p_s) / sqrt(d2) per component, f2 = u . l, v = u x l, w = u x v, f1 = v . n_t, and f3 the angle of
+ *   (u . n_t, w . n_t).  Bins: floor(((f + 1) 11) / 2) clamped to 0 .. 10 for f1 and f2; for f3 the sector of
+ *   [-pi, pi] / 11 found by the signs of b_k x (c, s) against the ten inner boundary directions b_k (fp32 literals).
+ *   -> spfh (n,33) int32: the counts, f1's 11 bins, then f2's, then f3's   pairs (n) int32: K_i, the number of pairs
+ *   -> features (n,33) fp32: with A[b] = sum over the pairs (i, j) with K_j > 0 (n' of them) of
+ *      rint(((w 2^20) spfh_j[b]) / K_j), w = r2 / max(d2, r2 2^-20), every step one fp64 operation and the sum an exact
+ *      64-bit integer, F[b] = spfh_i[b] / K_i + (A[b] 2^-20) / n' (the second term 0 where n' = 0) in fp64, and each
+ *      11-bin block scaled to (F[b] 100) / (sum of the block, from its first bin upwards), rounded to fp32 once.  A row
+ *      with K_i < min_neighbours or n' > 2^20 is all zero.  Every element written once.
+ * mvsn_cloud_feature_nearest: query (nq,dim) and target (nt,dim) fp32, dim = 33 (anything else: MVSN_E_BADARG),
+ *   1 <= nq, nt <= 2^31 - 1.  A row of either side takes part iff its 33 values are finite and not all zero.
+ *   d2 = sum_b (q_b - t_b)^2 from b = 0 upwards, one fp32 operation per step; the key of a target is
+ *   (uint64(bits of d2) << 32) | row.  -> index (nq) int64 and dist2 (nq) fp32: the least key's row and d2 (ties to the
+ *   lowest row), -1 and +inf where the query takes no part or no target does; second_dist2 (nq) fp32: the second least
+ *   key's d2, +inf where there is none.  One launch; eight waves share 64 query rows and merge their least keys.
+ * mvsn_cloud_feature_mutual: index (nq) int64 into nt rows, back (nt) int64 into nq rows
+ *   -> mutual (nq) bytes: 1 where 0 <= index[i] < nt and back[index[i]] == i, else 0.
+ * mvsn_cloud_ransac: source (ns,3), target (nt,3) fp32; correspondences (c,2) int64 of (source row, target row), 1 <= ns,
+ *   nt, c <= 2^31 - 1; r2 > 0 the squared inlier distance; edge_similarity inside (0, 1]; 1 <= hypotheses <= 2^24 (below:
+ *   MVSN_E_BADARG, above: MVSN_E_TOOLARGE); workspace: mvsn_cloud_ransac_workspace_bytes() bytes, 16-byte aligned, cleared
+ *   by a memset on the stream.  A correspondence with a row outside its cloud takes no part and is never dereferenced.
+ *   Hypothesis h draws j = 0, 1, 2: z = seed + (3 h + j + 1) 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) 0x94D049BB133111EB; z = z ^ z >> 31 (all mod 2^64); the draw is ((z >> 32) c) >> 32.  It is
+ *   rejected when two draws coincide, a drawn row lies outside its cloud, a drawn point is not finite, for a pair of
+ *   draws min(|ds|^2, |dt|^2) < edge_similarity^2 max(|ds|^2, |dt|^2), a triangle has |a x b|^2 <= 2^-40 |a|^2 |b|^2
+ *   (a = p1 - p0, b = p2 - p0), or the pose is not finite.  In fp64, one operation per step: e1 = a / sqrt(|a|^2),
+ *   e3 = (e1 x b) / |e1 x b|, e2 = e3 x e1 for both triangles, R_ij = (e1t_i e1s_j + e2t_i e2s_j) + e3t_i e3s_j,
+ *   c = ((p0 + p1) + p2) / 3, t = c_t - R c_s.  Its count: the correspondences with |(R s + t) - t_j|^2 <= (double)r2.
+ *   The winner has the most inliers, ties to the lowest h.
+ *   -> T (16 fp32) and T64 (16 fp64): the winner's pose, row-major 4x4   best (3 int64) = (hypothesis, inliers, status)
+ *      inlier (c) bytes: 1 for the winner's inliers.  status 0; 1: fewer than 3 correspondences with both rows inside
+ *      and finite; 2: every hypothesis rejected.  With status 1 or 2: T the identity, best = (-1, 0, status), inlier 0.
+ *   Two launches and nothing read on the host; the only atomic is a 64-bit integer maximum: every output is a
+ *   bitwise-reproducible function of the inputs.
+ * ------------------------------------------------------------------------------------------- */
+int mvsn_cloud_fpfh(const float *points, const float *normals, long n, float cell, float inv_cell, float r2,
+                    long min_neighbours, const void *index_workspace, size_t index_workspace_bytes, int *spfh,
+                    int *pairs, float *features, mvsn_stream_t stream);
+int mvsn_cloud_feature_nearest(const float *query, long nq, const float *target, long nt, int dim, int64_t *index,
+                               float *dist2, float *second_dist2, mvsn_stream_t stream);
+int mvsn_cloud_feature_mutual(const int64_t *index, long nq, const int64_t *back, long nt, unsigned char *mutual,
+                              mvsn_stream_t stream);
+size_t mvsn_cloud_ransac_workspace_bytes(void);
+int mvsn_cloud_ransac(const float *source, long ns, const float *target, long nt, const int64_t *correspondences, long c,
+                      float r2, double edge_similarity, long hypotheses, unsigned long long seed, void *workspace,
+                      size_t workspace_bytes, float *T, double *T64, int64_t *best, unsigned char *inlier,
+                      mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dense TSDF volume: depth maps integrated along the viewing rays, and a mesh taken from the volume by Surface Nets
  * (multi_view_stereonet_amd/tsdf.py; the semantics, every fp32 step and the error bounds are DESIGN.md section 15).
  * The state is planar fp32 in the layout (nz,ny,nx), x fastest: sdf_sum = sum w t, weight = sum w, color_sum

@@ -138,6 +138,13 @@ SIGNATURES = {
                        [c_void_p] * 4 + [c_void_p]),
     "mvsn_cloud_mean_stats_workspace_bytes": (c_size_t, [c_long]),
     "mvsn_cloud_mean_stats": (c_int, [c_void_p, c_long, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mvsn_cloud_fpfh": (c_int, [c_void_p, c_void_p, c_long] + [ctypes.c_float] * 3 + [c_long, c_void_p, c_size_t] +
+                        [c_void_p] * 3 + [c_void_p]),
+    "mvsn_cloud_feature_nearest": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int] + [c_void_p] * 3 + [c_void_p]),
+    "mvsn_cloud_feature_mutual": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p]),
+    "mvsn_cloud_ransac_workspace_bytes": (c_size_t, []),
+    "mvsn_cloud_ransac": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, ctypes.c_float, ctypes.c_double,
+                                  c_long, ctypes.c_uint64, c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
     "mvsn_tsdf_camera_batch": (c_int, []),
     "mvsn_tsdf_integrate": (c_int, [c_void_p] * 6 + [c_int] * 6 + [ctypes.c_float] * 6 + [c_void_p] * 3 + [c_void_p]),
     "mvsn_tsdf_workspace_bytes": (c_size_t, [c_int] * 3),

@@ -17,7 +17,10 @@ csrc/mvsn_cloud_register.hip) moves one cloud onto another by ICP on that query,
 csrc/mvsn_cloud_normals.hip) gives a bare cloud the normals that the point-to-plane mode needs, from the covariance of
 every point's neighbours within a radius.  ``cloud_knn`` (csrc/mvsn_cloud_knn.hip) returns the k
 nearest neighbours within a radius themselves, and ``statistical_outlier_mask`` is the statistical outlier filter on it,
-whose threshold follows the cloud's own spacing.  A dense TSDF volume that integrates the same
+whose threshold follows the cloud's own spacing.  ``cloud_register_global`` registers two clouds
+from unrelated frames, the start that ``cloud_register`` needs: ``cloud_fpfh`` (csrc/mvsn_cloud_fpfh.hip) describes every
+point by its FPFH histogram, ``feature_nearest`` (csrc/mvsn_cloud_match.hip) matches the descriptors, and ``cloud_ransac``
+(csrc/mvsn_cloud_ransac.hip) finds the pose that most correspondences agree on.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -940,6 +943,281 @@ def statistical_outlier_mask(points: torch.Tensor, k: int, std_ratio: float, max
                                                 _native.stream()), "mvsn_cloud_mean_stats")
     keep = mean_dist <= stats[1] + ratio * stats[2]          # (a NaN compares false)
     return CloudOutliers(keep, mean_dist, stats[1], stats[2])
+
+
+class CloudFeatures(NamedTuple):
+    features: torch.Tensor           # (N,33) fp32: the FPFH descriptor, each 11-bin block summing to 100; zero where undefined
+    spfh: torch.Tensor               # (N,33) int32: the point's own pair histogram (f1's 11 bins, f2's, f3's)
+    pairs: torch.Tensor              # (N,) int32: K_i, the number of pairs counted (the sum of each block of spfh)
+
+
+class FeatureMatches(NamedTuple):
+    index: torch.Tensor              # (Q,) int64: the nearest target row in descriptor space, -1 where none
+    dist2: torch.Tensor              # (Q,) fp32: its squared descriptor distance, +inf where none
+    second_dist2: torch.Tensor       # (Q,) fp32: the runner-up's, +inf where there is none (for a ratio test)
+    mutual: Optional[torch.Tensor]   # (Q,) bool: the match's own nearest query row is this row; None unless asked
+
+
+class CloudRansac(NamedTuple):
+    T: torch.Tensor                  # (4,4) fp32: source coordinates -> the target's frame; the identity unless status is 0
+    hypothesis: torch.Tensor         # () int64: the winning hypothesis, -1 where none
+    inliers: torch.Tensor            # () int64: its number of inlier correspondences
+    status: torch.Tensor             # () int64: 0, 1 = fewer than 3 usable correspondences, 2 = every hypothesis rejected
+    inlier: torch.Tensor             # (C,) bool: the winner's inliers
+
+
+class GlobalRegistration(NamedTuple):
+    T: torch.Tensor                  # (4,4) fp32: the refined pose with refine, else the coarse one
+    coarse: CloudRansac              # the RANSAC result
+    correspondences: torch.Tensor    # (C,2) int64: (source row, target row) handed to RANSAC
+    refined: Optional[CloudRegistration]   # cloud_register's result from coarse.T; None without refine
+
+
+FEATURE_DIM = 33
+RANSAC_MAX_HYPOTHESES = 2 ** 24
+
+
+def _check_normals(normals, name, N, dev, what="points"):
+    if not torch.is_tensor(normals) or tuple(normals.shape) != (N, 3) or normals.dtype != torch.float32:
+        raise ValueError(f"{name} must be a ({N},3) float32 tensor")
+    if normals.device != dev:
+        raise ValueError(f"{name} is on {normals.device}, {what} on {dev}")
+
+
+def _check_fpfh(points, normals, radius, min_neighbours, names=("points", "normals")):
+    check_cloud(names[0], points)
+    N, dev = int(points.shape[0]), points.device
+    _check_normals(normals, names[1], N, dev, names[0])
+    h, inv, r2 = cloud_radius_scalars(radius, "radius")
+    return N, dev, h, inv, r2, _integer_in(min_neighbours, "min_neighbours", 1, 2 ** 62)
+
+
+def cloud_fpfh(points: torch.Tensor, normals: torch.Tensor, radius: float, *, min_neighbours: int = 3) -> CloudFeatures:
+    """The Fast Point Feature Histogram (Rusu et al., ICRA 2009; PCL's ``FPFHEstimation``, Open3D's
+    ``compute_fpfh_feature``) of every row of ``points`` (N,3) fp32 with ``normals`` (N,3) fp32 from its neighbours
+    within ``radius``: 33 bins, three blocks of 11 (csrc/mvsn_cloud_fpfh.hip).
+
+    A neighbour j of i is one that ``cloud_nearest(points, points, radius)`` counts, other than i itself and not at
+    distance 0, with both normals finite and not (0,0,0) (what ``cloud_normals`` writes where it is undefined).  ``spfh``
+    holds the counts of the pair's three Darboux-frame features, each in 11 equal bins, and ``pairs`` their number K_i.
+    ``features`` adds to the point's own histogram the mean of its neighbours' histograms, weighted by
+    ``radius^2 / max(d^2, radius^2 2^-20)`` (scale-free, unlike the paper's 1/distance), and scales each block to sum 100;
+    a point with ``K_i < min_neighbours`` (an integer >= 1), or with more than 2^20 neighbours, gets an all-zero row.
+
+    Every step up to the bins is a single fp32 operation (no atan2: the angle's bin comes from sign tests), the counts
+    and the weighted sums are exact integers, the rest is fp64 rounded to fp32 once: every output is a
+    bitwise-reproducible function of the inputs, and permuting the rows permutes the outputs (a tie between the two
+    angles of a pair, which goes to the lower row, aside).  As for ``cloud_nearest``, the time grows with (points per
+    cell) x 27 cells, and a finite point more than 2^20 cells of ``radius`` from the origin raises ValueError.
+    Everything is validated here, before any launch; the one host synchronisation is the read of the index build's
+    status word, after everything is enqueued."""
+    N, dev, h, inv, r2, k = _check_fpfh(points, normals, radius, min_neighbours)
+    if N == 0:                         # no neighbourhood, nothing to launch
+        return CloudFeatures(torch.zeros((0, FEATURE_DIM), dtype=torch.float32, device=dev),
+                             torch.zeros((0, FEATURE_DIM), dtype=torch.int32, device=dev),
+                             torch.zeros((0,), dtype=torch.int32, device=dev))
+    if not points.is_cuda:
+        raise RuntimeError("cloud_fpfh runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    p, nm = points.detach().contiguous(), normals.detach().contiguous()
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    out = CloudFeatures(torch.empty((N, FEATURE_DIM), dtype=torch.float32, device=dev),
+                        torch.empty((N, FEATURE_DIM), dtype=torch.int32, device=dev),
+                        torch.empty((N,), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(p), N, float(h), float(inv), _native.ptr(status),
+                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_fpfh(_native.ptr(p), _native.ptr(nm), N, float(h), float(inv), float(r2), k,
+                                          _native.ptr(ws), ws_bytes, _native.ptr(out.spfh), _native.ptr(out.pairs),
+                                          _native.ptr(out.features), st), "mvsn_cloud_fpfh")
+        bits = int(status.item())      # the one host synchronisation, after everything is enqueued
+    _raise_cloud_status(bits, h, "cloud_fpfh")
+    return out
+
+
+def _check_features(name, t):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != FEATURE_DIM:
+        raise ValueError(f"{name} must be an (N,{FEATURE_DIM}) tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if int(t.shape[0]) > 2 ** 31 - 1:
+        raise ValueError(f"at most 2^31 - 1 {name} rows, got {int(t.shape[0])}")
+
+
+def feature_nearest(query_features: torch.Tensor, target_features: torch.Tensor, *, mutual: bool = False) -> FeatureMatches:
+    """For every row of ``query_features`` (Q,33) fp32 the nearest row of ``target_features`` (T,33) fp32 in descriptor
+    space, by brute force (csrc/mvsn_cloud_match.hip): its row, its squared distance, and the
+    squared distance of the runner-up (for a ratio test).
+
+    The distance is ``sum_b (q_b - t_b)^2`` from b = 0 upwards, each step one fp32 operation; ties go to the lowest
+    target row.  A row of either side takes part iff its 33 values are finite and not all zero (``cloud_fpfh`` writes
+    zeros where the descriptor is undefined); a query row that takes no part, or finds no target, gets (-1, +inf, +inf).
+    With ``mutual`` the same search runs with the roles swapped and ``mutual[i]`` says whether the match's own nearest
+    query row is i.  Every output is a bitwise-reproducible function of the inputs; nothing is read on the host.  The
+    time is Q x T x 33: meant for clouds merged to 10^4 - 10^5 points (``voxel_merge``)."""
+    _check_features("query_features", query_features)
+    _check_features("target_features", target_features)
+    dev = query_features.device
+    if target_features.device != dev:
+        raise ValueError(f"query_features is on {dev}, target_features on {target_features.device}")
+    Q, T = int(query_features.shape[0]), int(target_features.shape[0])
+    want = bool(mutual)
+    if Q == 0 or T == 0:               # nothing to find, nothing to launch
+        return FeatureMatches(torch.full((Q,), -1, dtype=torch.int64, device=dev),
+                              torch.full((Q,), float("inf"), dtype=torch.float32, device=dev),
+                              torch.full((Q,), float("inf"), dtype=torch.float32, device=dev),
+                              torch.zeros((Q,), dtype=torch.bool, device=dev) if want else None)
+    if not query_features.is_cuda:
+        raise RuntimeError("feature_nearest runs on HIP devices only: move the descriptors to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    q, t = query_features.detach().contiguous(), target_features.detach().contiguous()
+
+    def search(a, na, b, nb):
+        index = torch.empty((na,), dtype=torch.int64, device=dev)
+        d2, second = torch.empty((na,), dtype=torch.float32, device=dev), torch.empty((na,), dtype=torch.float32, device=dev)
+        _native.check(lib.mvsn_cloud_feature_nearest(_native.ptr(a), na, _native.ptr(b), nb, FEATURE_DIM, _native.ptr(index),
+                                                     _native.ptr(d2), _native.ptr(second), _native.stream()),
+                      "mvsn_cloud_feature_nearest")
+        return index, d2, second
+
+    with torch.cuda.device(dev):
+        index, d2, second = search(q, Q, t, T)
+        both = None
+        if want:
+            back, _, _ = search(t, T, q, Q)
+            both = torch.empty((Q,), dtype=torch.bool, device=dev)
+            _native.check(lib.mvsn_cloud_feature_mutual(_native.ptr(index), Q, _native.ptr(back), T, _native.ptr(both),
+                                                        _native.stream()), "mvsn_cloud_feature_mutual")
+    return FeatureMatches(index, d2, second, both)
+
+
+def _check_ransac(source, target, max_dist, hypotheses, seed, edge_similarity):
+    """The validation ``cloud_ransac`` and ``cloud_register_global`` share: (N, M, dev, r2, hypotheses, seed, es)."""
+    check_cloud("source", source)
+    check_cloud("target", target)
+    dev = source.device
+    if target.device != dev:
+        raise ValueError(f"target is on {target.device}, source on {dev}")
+    _, _, r2 = cloud_radius_scalars(max_dist)
+    hyp = _integer_in(hypotheses, "hypotheses", 1, RANSAC_MAX_HYPOTHESES)
+    sd = _integer_in(seed, "seed", 0, 2 ** 64 - 1)
+    try:
+        es = float(edge_similarity)
+        if isinstance(edge_similarity, (bool, str)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"edge_similarity must be a number inside (0, 1], got {edge_similarity!r}") from None
+    if not 0.0 < es <= 1.0:
+        raise ValueError(f"edge_similarity must be a number inside (0, 1], got {edge_similarity!r}")
+    return int(source.shape[0]), int(target.shape[0]), dev, r2, hyp, sd, es
+
+
+def _no_pose(C, status, dev):
+    return CloudRansac(torch.eye(4, dtype=torch.float32, device=dev), torch.full((), -1, dtype=torch.int64, device=dev),
+                       torch.zeros((), dtype=torch.int64, device=dev), torch.full((), status, dtype=torch.int64, device=dev),
+                       torch.zeros((C,), dtype=torch.bool, device=dev))
+
+
+def _cloud_ransac(source, target, corr, N, M, dev, r2, hyp, sd, es):
+    C = int(corr.shape[0])
+    if N == 0 or M == 0 or C == 0:     # fewer than 3 usable correspondences, nothing to launch
+        return _no_pose(C, 1, dev)
+    if not source.is_cuda:
+        raise RuntimeError("cloud_ransac runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    s, t, c = source.detach().contiguous(), target.detach().contiguous(), corr.detach().contiguous()
+    ws_bytes = lib.mvsn_cloud_ransac_workspace_bytes()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    T, T64 = torch.empty((4, 4), dtype=torch.float32, device=dev), torch.empty((4, 4), dtype=torch.float64, device=dev)
+    best = torch.empty((3,), dtype=torch.int64, device=dev)
+    inlier = torch.empty((C,), dtype=torch.bool, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_cloud_ransac(_native.ptr(s), N, _native.ptr(t), M, _native.ptr(c), C, float(r2), es, hyp, sd,
+                                            _native.ptr(ws), ws_bytes, _native.ptr(T), _native.ptr(T64), _native.ptr(best),
+                                            _native.ptr(inlier), _native.stream()), "mvsn_cloud_ransac")
+    return CloudRansac(T, best[0], best[1], best[2], inlier)
+
+
+def _check_correspondences(corr, dev):
+    if not torch.is_tensor(corr) or corr.dim() != 2 or corr.shape[1] != 2 or corr.dtype != torch.int64:
+        raise ValueError("correspondences must be a (C,2) int64 tensor of (source row, target row)")
+    if corr.device != dev:
+        raise ValueError(f"correspondences is on {corr.device}, source on {dev}")
+    if int(corr.shape[0]) > 2 ** 31 - 1:
+        raise ValueError(f"at most 2^31 - 1 correspondences, got {int(corr.shape[0])}")
+
+
+def cloud_ransac(source: torch.Tensor, target: torch.Tensor, correspondences: torch.Tensor, max_dist: float, *,
+                 hypotheses: int = 100000, seed: int = 0, edge_similarity: float = 0.9) -> CloudRansac:
+    """The rigid pose that brings the most of ``correspondences`` (C,2) int64, rows of ``source`` (N,3) fp32 paired with
+    rows of ``target`` (M,3) fp32, within ``max_dist`` of each other: RANSAC over ``hypotheses`` (1 to 2^24) triples
+    (csrc/mvsn_cloud_ransac.hip; Open3D's ``registration_ransac_based_on_correspondence``).
+
+    Hypothesis h draws three correspondences from a counter-based generator (splitmix64 of ``seed`` and h: integer
+    operations only).  It is rejected when two draws coincide, a drawn row lies outside its cloud or is not finite, two
+    edges of the triangles differ in length by more than ``edge_similarity`` (inside (0, 1]; Open3D's edge-length
+    checker) or a triangle is degenerate.  Its pose comes from the two triangles' orthonormal frames in fp64, its score
+    is the number of correspondences within ``max_dist`` after the pose.  The winner has the most inliers, ties going
+    to the lowest h: the result is a bitwise-reproducible function of the inputs, ``seed`` included, and nothing is
+    read on the host.  ``status`` is 0, 1 where fewer than 3 correspondences are usable, 2 where every hypothesis was
+    rejected; ``T`` is then the identity.  A correspondence with a row outside its cloud takes no part.  The time is
+    hypotheses x C.  Everything is validated here, before any launch."""
+    N, M, dev, r2, hyp, sd, es = _check_ransac(source, target, max_dist, hypotheses, seed, edge_similarity)
+    _check_correspondences(correspondences, dev)
+    return _cloud_ransac(source, target, correspondences, N, M, dev, r2, hyp, sd, es)
+
+
+def cloud_register_global(source: torch.Tensor, target: torch.Tensor, max_dist: float, *, feature_radius: float = None,
+                          source_normals: Optional[torch.Tensor] = None, target_normals: Optional[torch.Tensor] = None,
+                          normal_radius: Optional[float] = None, mutual: bool = True, hypotheses: int = 100000,
+                          seed: int = 0, edge_similarity: float = 0.9, refine: bool = True,
+                          refine_iterations: int = 20) -> GlobalRegistration:
+    """Register ``source`` (N,3) fp32 to ``target`` (M,3) fp32 from unrelated frames: the start that ``cloud_register``
+    needs and ``cloud_metrics`` presumes.  Normals come from
+    ``cloud_normals(., normal_radius or feature_radius / 2)`` where they are not given; ``cloud_fpfh`` describes both
+    clouds at ``feature_radius``; ``feature_nearest(mutual=mutual)`` matches source rows to target rows; the rows with
+    a match (a mutual one where asked) are the correspondences of ``cloud_ransac`` with ``max_dist``, ``hypotheses``,
+    ``seed`` and ``edge_similarity``; with ``refine``, ``cloud_register(source, target, max_dist,
+    target_normals=..., T_init=coarse.T, iterations=refine_iterations)`` finishes the job.
+
+    Callers bring the clouds to 10^4 - 10^5 points first (``voxel_merge``): matching is brute force.  Every stage is a
+    bitwise-reproducible function of its inputs, so the whole result is one of (source, target, the arguments).  The
+    boolean selection of the matched rows is the composition's one extra host read (the size of the list), next to the
+    status words of the index builds.  Every argument is validated here, before any launch."""
+    N, M, dev, r2, hyp, sd, es = _check_ransac(source, target, max_dist, hypotheses, seed, edge_similarity)
+    fh = cloud_radius_scalars(feature_radius, "feature_radius")[0]
+    nh = cloud_radius_scalars(float(fh) / 2 if normal_radius is None else normal_radius, "normal_radius")[0]
+    if source_normals is not None:
+        _check_normals(source_normals, "source_normals", N, dev, "source")
+    if target_normals is not None:
+        _check_normals(target_normals, "target_normals", M, dev, "source")
+    it = _integer_in(refine_iterations, "refine_iterations", 0, 1000)
+    if N == 0 or M == 0:               # nothing to describe or to match, nothing to launch
+        coarse = _no_pose(0, 1, dev)
+        refined = cloud_register(source, target, max_dist, target_normals=target_normals, T_init=coarse.T,
+                                 iterations=it) if refine else None
+        return GlobalRegistration(coarse.T, coarse, torch.zeros((0, 2), dtype=torch.int64, device=dev), refined)
+    if not source.is_cuda:
+        raise RuntimeError("cloud_register_global runs on HIP devices only: move the clouds to 'cuda' "
+                           "(there is no CPU implementation)")
+    sn = cloud_normals(source, float(nh)).normals if source_normals is None else source_normals
+    tn = cloud_normals(target, float(nh)).normals if target_normals is None else target_normals
+    fs, ft = cloud_fpfh(source, sn, float(fh)), cloud_fpfh(target, tn, float(fh))
+    m = feature_nearest(fs.features, ft.features, mutual=bool(mutual))
+    keep = (m.index >= 0) & m.mutual if mutual else m.index >= 0
+    rows = torch.nonzero(keep).reshape(-1)               # the one extra host read: the length of the list
+    corr = torch.stack([rows, m.index[rows]], dim=1).contiguous()
+    coarse = _cloud_ransac(source, target, corr, N, M, dev, r2, hyp, sd, es)
+    refined = None
+    if refine:
+        refined = cloud_register(source, target, max_dist, target_normals=tn, T_init=coarse.T, iterations=it)
+    return GlobalRegistration(refined.T if refine else coarse.T, coarse, corr, refined)
 
 
 def frame_pair_poses(T_cam_in_world: torch.Tensor, ref: Sequence[int], src: Sequence[int]) -> torch.Tensor:

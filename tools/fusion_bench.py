@@ -59,7 +59,10 @@ extrapolation to all of them.  --knn: also searches each scene's fused cloud for
 the cloud against itself at the same radius (the same walk: the floor), the share of points with fewer than k neighbours,
 ms per statistical_outlier_mask call and the share kept, and the search composed from torch ops (torch.cdist over chunks of
 the cloud, topk per chunk, topk over the chunks' winners) on the first TORCH_QUERIES points, with its extrapolation to
-all of them."""
+all of them.  --global: also registers two samplings of an asymmetric height field from unrelated frames and prints, on a
+line of its own as "global", the points per cloud, ms for fusion.cloud_fpfh (each cloud), fusion.feature_nearest (one way
+and mutual) and fusion.cloud_ransac, ms of the match composed from torch ops (torch.cdist + min) and in how many rows its
+index differs, ms of the whole fusion.cloud_register_global, and the pose error before and after the refinement."""
 import argparse
 import json
 import os
@@ -73,6 +76,7 @@ import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
+                                             cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
@@ -720,6 +724,72 @@ def run_knn(res, steps, warmup):
     return {"knn": out}
 
 
+GLOBAL_GRID = 128                     # the target is a GLOBAL_GRID^2 sampling of a height field over [-1,1]^2
+GLOBAL_BUMPS = ((0.45, 0.50, 0.22, 0.55), (-0.50, 0.35, 0.35, -0.40), (-0.30, -0.55, 0.15, 0.45), (0.55, -0.40, 0.28, 0.30))
+GLOBAL_FEATURE_RADIUS, GLOBAL_MAX_DIST, GLOBAL_EDGE_SIMILARITY, GLOBAL_HYPOTHESES = 0.25, 0.15, 0.98, 100000
+
+
+def global_scene(dev):
+    """(source, target, T_true): an asymmetric height field (four Gaussian bumps and a step edge) sampled on a grid (target)
+    and on the same grid shifted by half a spacing with every fourth row dropped (source), the source moved by 2.5 rad
+    about (1, 2, -1.5) and by (3, -2, 5); T_true (4,4) fp64 takes it back."""
+    def height(x, y):
+        z = torch.zeros_like(x)
+        for cx, cy, width, h in GLOBAL_BUMPS:
+            z = z + h * torch.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * width * width))
+        return z + 0.12 * torch.tanh((x + 0.4 * y - 0.15) / (4.0 / (GLOBAL_GRID - 1)))
+    g = torch.linspace(-1.0, 1.0, GLOBAL_GRID, dtype=torch.float64, device=dev)
+    Y, X = torch.meshgrid(g, g, indexing="ij")
+    target = torch.stack([X, Y, height(X, Y)], dim=-1).reshape(-1, 3)
+    keep = torch.arange(GLOBAL_GRID, device=dev) % 4 != 3
+    half = 1.0 / (GLOBAL_GRID - 1)
+    Xs, Ys = X[keep] + half, Y[keep] + half
+    src = torch.stack([Xs, Ys, height(Xs, Ys)], dim=-1).reshape(-1, 3)
+    w = torch.nn.functional.normalize(torch.tensor([1.0, 2.0, -1.5], dtype=torch.float64), dim=0) * 2.5
+    Wx = torch.zeros(3, 3, dtype=torch.float64)
+    Wx[0, 1], Wx[0, 2], Wx[1, 0], Wx[1, 2], Wx[2, 0], Wx[2, 1] = -w[2], w[1], w[2], -w[0], -w[1], w[0]
+    M = torch.eye(4, dtype=torch.float64)
+    M[:3, :3], M[:3, 3] = torch.linalg.matrix_exp(Wx), torch.tensor([3.0, -2.0, 5.0], dtype=torch.float64)
+    M = M.to(dev)
+    source = (src @ M[:3, :3].T + M[:3, 3]).float()
+    return source.contiguous(), target.float().contiguous(), torch.linalg.inv(M)
+
+
+def run_global(steps, warmup):
+    """Global registration stage by stage (fusion.cloud_register_global's own composition), the descriptor match also from
+    torch ops (torch.cdist + min: what a caller had to write without feature_nearest)."""
+    steps, warmup = min(steps, 3), min(warmup, 1)
+    dev = torch.device("cuda:0")
+    source, target, T_true = global_scene(dev)
+    nr = GLOBAL_FEATURE_RADIUS / 2
+    sn, tn = cloud_normals(source, nr).normals, cloud_normals(target, nr).normals
+    fs, ftimes = timed(lambda: cloud_fpfh(source, sn, GLOBAL_FEATURE_RADIUS), steps, warmup)
+    ft, gtimes = timed(lambda: cloud_fpfh(target, tn, GLOBAL_FEATURE_RADIUS), steps, warmup)
+    m, mtimes = timed(lambda: feature_nearest(fs.features, ft.features, mutual=True), steps, warmup)
+    one, otimes = timed(lambda: feature_nearest(fs.features, ft.features), steps, warmup)
+    (td, ti), ttimes = timed(lambda: torch.cdist(fs.features, ft.features).min(dim=1), steps, warmup)
+    rows = torch.nonzero((m.index >= 0) & m.mutual).reshape(-1)
+    corr = torch.stack([rows, m.index[rows]], dim=1).contiguous()
+    kw = dict(hypotheses=GLOBAL_HYPOTHESES, seed=0, edge_similarity=GLOBAL_EDGE_SIMILARITY)
+    coarse, rtimes = timed(lambda: cloud_ransac(source, target, corr, GLOBAL_MAX_DIST, **kw), steps, warmup)
+    whole, wtimes = timed(lambda: cloud_register_global(source, target, GLOBAL_MAX_DIST, feature_radius=GLOBAL_FEATURE_RADIUS, **kw),
+                          steps, warmup)
+    before, after = pose_errors(coarse.T[None], T_true[None]), pose_errors(whole.T[None], T_true[None])
+    return {"global": {
+        "n_source": int(source.shape[0]), "n_target": int(target.shape[0]), "feature_radius": GLOBAL_FEATURE_RADIUS,
+        "max_dist": GLOBAL_MAX_DIST, "edge_similarity": GLOBAL_EDGE_SIMILARITY, "hypotheses": GLOBAL_HYPOTHESES,
+        "pairs_mean": float(fs.pairs.float().mean()), "pairs_max": int(fs.pairs.max()),
+        "fpfh_source_ms_mean": float(np.mean(ftimes)), "fpfh_target_ms_mean": float(np.mean(gtimes)),
+        "match_mutual_ms_mean": float(np.mean(mtimes)), "match_one_way_ms_mean": float(np.mean(otimes)),
+        "torch_cdist_min_ms_mean": float(np.mean(ttimes)), "torch_index_differs": int((ti != one.index).sum()),
+        "correspondences": int(corr.shape[0]), "ransac_ms_mean": float(np.mean(rtimes)), "ransac_inliers": int(coarse.inliers),
+        "ransac_status": int(coarse.status), "coarse_equals_the_stages": bool(torch.equal(whole.coarse.T, coarse.T)),
+        "cloud_register_global_ms_mean": float(np.mean(wtimes)),
+        "translation_error_coarse": float(before[0][0]), "rotation_error_coarse": float(before[1][0]),
+        "translation_error_refined": float(after[0][0]), "rotation_error_refined": float(after[1][0]),
+        "refine_status": int(whole.refined.status)}}
+
+
 MESH_MIN_FACES = 200
 
 
@@ -821,6 +891,9 @@ def main():
                     help="also register the fused cloud, moved by a small twist, back onto itself, and the torch form")
     ap.add_argument("--cloud-normals", action="store_true",
                     help="also estimate the fused cloud's normals from its bare points (cloud_normals), and the torch form")
+    ap.add_argument("--global", dest="global_too", action="store_true",
+                    help="also register two samplings of an asymmetric surface from unrelated frames (cloud_fpfh, "
+                         "feature_nearest, cloud_ransac, cloud_register_global), and the torch form of the match; its own line")
     ap.add_argument("--knn", action="store_true",
                     help="also search the fused cloud for every point's k nearest others (cloud_knn) and filter it "
                          "(statistical_outlier_mask), and the torch form of the search")
@@ -829,6 +902,8 @@ def main():
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn)), flush=True)
+    if a.global_too:
+        print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
 
 if __name__ == "__main__":
