@@ -994,6 +994,43 @@ int mvsn_mesh_compact(const float *vertices, const float *normals, const uint8_t
                       long n_faces_out, float *out_vertices, float *out_normals, uint8_t *out_colors, int64_t *out_cell,
                       int64_t *out_faces, int64_t *vertex_rows, int64_t *face_rows, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Density-based clusters of a cloud: DBSCAN, and with min_points = 1 Euclidean cluster extraction
+ * (multi_view_stereonet_amd/fusion.py: cloud_clusters, cloud_cluster_mask; the semantics and the argument are DESIGN.md
+ * section 24).  The index is mvsn_cloud_index_build's of the points themselves (index_workspace, its
+ * mvsn_cloud_workspace_bytes(n) bytes; inv_cell and r2 as given to the build and to mvsn_cloud_nearest).
+ *   points (n,3) fp32, 1 <= n <= 2^31 - 1; min_points >= 1
+ *   Row j is a neighbour of row i exactly when mvsn_cloud_nearest of the cloud against itself counts it (fp32 d2 <= r2,
+ *   both rows finite; a point is its own neighbour): a relation that is symmetric bit for bit.  A row is core when it is
+ *   finite and has at least min_points neighbours.  A cluster is a connected component of the core rows under the
+ *   relation; its id is its rank among the clusters ordered by their lowest core row.  A finite row that is not core
+ *   joins the cluster of the core neighbour with the least key (uint64(bits of d2) << 32) | row, and is noise (-1)
+ *   without one; a row that is not finite is noise.
+ *   workspace: mvsn_cloud_cluster_workspace_bytes(n) bytes (0 for sizes the entries refuse), 16-byte aligned: a head of
+ *     16 bytes, 8 bytes per point (parent, and the root -> id map), 12 bytes per 256 points.
+ * mvsn_cloud_cluster_label (core, hook, flatten, the scan and a 16-byte device copy): one thread per point; the
+ *   lock-free union-find of mvsn_mesh_components_label over the core rows, every edge united by its higher row.
+ *   -> within (n) int32: mvsn_cloud_nearest's `within` of the cloud against itself, bit for bit   core (n) bytes, 0 or 1
+ *      result (2 int64): [0] the number of clusters C, 0 <= C <= n, [1] status bits (MVSN_CLUSTER_STATUS_*; 0 = fine).
+ *      Reading the two words back (with the index build's status word) is the one host synchronisation.
+ * mvsn_cloud_cluster_emit (rank, labels; labels alone with n_clusters = 0), on both workspaces and `core` handed on
+ *   unchanged, n_clusters = C as read back (outside [0, n] it cannot be this workspace's: MVSN_E_BADARG):
+ *   -> label (n) int64: the cluster id, -1 for noise   count, core_count, first (C) int64 (may be NULL with C = 0): the
+ *      points of every cluster (border points included), its core points, and its lowest core row
+ * Integer atomics only (a compare-and-swap on a root, relaxed loads and stores of parent, sums) and no float arithmetic
+ * beyond d2: every output is a bitwise-reproducible function of the inputs, whatever order the index holds the points in.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_CLUSTER_STATUS_WORKSPACE 1   /* a walk over `parent` ran out of its bound or met a parent above its row: the
+                                             workspace was overwritten during the call (cannot happen otherwise) */
+size_t mvsn_cloud_cluster_workspace_bytes(long n);
+int mvsn_cloud_cluster_label(const float *points, long n, float inv_cell, float r2, long min_points,
+                             const void *index_workspace, size_t index_workspace_bytes, int *within, uint8_t *core,
+                             int64_t *result, void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_cloud_cluster_emit(const float *points, long n, float inv_cell, float r2, const void *index_workspace,
+                            size_t index_workspace_bytes, const uint8_t *core, void *workspace, size_t workspace_bytes,
+                            long n_clusters, int64_t *label, int64_t *count, int64_t *core_count, int64_t *first,
+                            mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -165,6 +165,11 @@ SIGNATURES = {
     "mvsn_mesh_select": (c_int, [c_void_p] * 3 + [c_long] * 3 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_mesh_compact": (c_int, [c_void_p] * 7 + [c_long] * 3 + [c_void_p, c_size_t, c_long, c_long] + [c_void_p] * 7 +
                           [c_void_p]),
+    "mvsn_cloud_cluster_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_cloud_cluster_label": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_long, c_void_p, c_size_t] +
+                                 [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),
+    "mvsn_cloud_cluster_emit": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_size_t, c_void_p] +
+                                [c_void_p, c_size_t, c_long] + [c_void_p] * 4 + [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

@@ -20,7 +20,9 @@ nearest neighbours within a radius themselves, and ``statistical_outlier_mask`` 
 whose threshold follows the cloud's own spacing.  ``cloud_register_global`` registers two clouds
 from unrelated frames, the start that ``cloud_register`` needs: ``cloud_fpfh`` (csrc/mvsn_cloud_fpfh.hip) describes every
 point by its FPFH histogram, ``feature_nearest`` (csrc/mvsn_cloud_match.hip) matches the descriptors, and ``cloud_ransac``
-(csrc/mvsn_cloud_ransac.hip) finds the pose that most correspondences agree on.  A dense TSDF volume that integrates the same
+(csrc/mvsn_cloud_ransac.hip) finds the pose that most correspondences agree on.  ``cloud_clusters`` (DESIGN.md section
+24, csrc/mvsn_cloud_cluster.hip) splits a cloud into its density-connected pieces (DBSCAN on the same radius query) and
+``cloud_cluster_mask`` keeps the pieces one asks for: the detached floaters that both local filters pass go.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -943,6 +945,141 @@ def statistical_outlier_mask(points: torch.Tensor, k: int, std_ratio: float, max
                                                 _native.stream()), "mvsn_cloud_mean_stats")
     keep = mean_dist <= stats[1] + ratio * stats[2]          # (a NaN compares false)
     return CloudOutliers(keep, mean_dist, stats[1], stats[2])
+
+
+class CloudClusters(NamedTuple):
+    label: torch.Tensor              # (N,) int64: cluster id of every point, -1 for noise
+    core: torch.Tensor               # (N,) bool: a finite point with at least min_points points within eps, itself included
+    within: torch.Tensor             # (N,) int32: points within eps of the point, itself included (cloud_nearest's `within`)
+    count: torch.Tensor              # (C,) int64: points per cluster, border points included
+    core_count: torch.Tensor         # (C,) int64: core points per cluster
+    first: torch.Tensor              # (C,) int64: lowest core row of each cluster, ascending
+
+
+CLUSTER_STATUS_WORKSPACE = 1
+
+
+def cloud_clusters(points: torch.Tensor, eps: float, min_points: int) -> CloudClusters:
+    """The density-based clusters (DBSCAN: Open3D's ``cluster_dbscan``, scikit-learn's ``DBSCAN``) of ``points`` (N,3)
+    fp32, and with ``min_points=1`` its Euclidean clusters (PCL's ``EuclideanClusterExtraction``); DESIGN.md section
+    24, csrc/mvsn_cloud_cluster.hip.  The cloud needs no order.
+
+    Row j is a *neighbour* of row i exactly when ``cloud_nearest(points, points, eps)`` counts it: both rows finite and
+    ``(dx*dx + dy*dy) + dz*dz <= h*h`` of the fp32 differences with h = float32(eps).  A point is its own neighbour,
+    exact duplicates are neighbours at distance 0, and the relation is symmetric bit for bit.  A point is *core* when
+    ``within >= min_points`` (``min_points`` an integer >= 1; the point itself is counted, as in Open3D and
+    scikit-learn).  A *cluster* is a connected component of the graph on the core points whose edges are the neighbour
+    relation.  A finite point that is not core but has a core neighbour is a *border* point and joins the cluster of its
+    nearest core neighbour, ties in the distance to the lowest row (the minimum of (d2 bits, row), the tie rule of
+    ``cloud_nearest``): a border point never connects two clusters, and which cluster it joins is a function of the
+    input, not of a visiting order.  Every other point, and every row with a non-finite coordinate, is *noise*: label
+    -1, never core, nobody's neighbour.  Cluster ids are dense, 0..C-1, ordered by ``first``, the lowest core row of
+    the cluster; C may be 0.  ``count`` includes the border points; ``within`` is ``cloud_nearest``'s bit for bit.
+
+    Every output is a bitwise-reproducible function of the inputs: integer work on top of the exact radius query, and
+    permuting the rows permutes ``core`` and ``within`` and leaves the partition alone (but for border points at
+    exactly tied distances).  N = 0 gives empties without a launch.  The time is ``cloud_nearest``'s, (points per cell)
+    x (cells visited, 27 almost always), paid three times, plus the unions: keep ``eps`` at a few sampling distances;
+    far above them it is quadratic within a neighbourhood.  A finite point more than 2^20 cells of ``eps`` from the
+    origin raises ValueError.  Everything is validated here, before any launch; the one host synchronisation is the
+    read of (C, the union-find's status, the index build's status) that sizes the outputs."""
+    check_cloud("points", points)
+    h, inv, r2 = cloud_radius_scalars(eps, "eps")
+    k = _integer_in(min_points, "min_points", 1, 2 ** 31 - 1)
+    N, dev = int(points.shape[0]), points.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    if N == 0:                         # no point, no cluster, nothing to launch
+        return CloudClusters(torch.empty((0,), **i64), torch.empty((0,), dtype=torch.bool, device=dev),
+                             torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), **i64),
+                             torch.empty((0,), **i64), torch.empty((0,), **i64))
+    if not points.is_cuda:
+        raise RuntimeError("cloud_clusters runs on HIP devices only: move the cloud to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    p = points.detach().contiguous()
+    index_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(N), lib.mvsn_cloud_cluster_workspace_bytes(N)
+    index_ws = torch.empty(index_bytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(3, **i64)       # (C, the union-find's status, the index build's status)
+    within = torch.empty((N,), dtype=torch.int32, device=dev)
+    core = torch.empty((N,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_cloud_index_build(_native.ptr(p), N, float(h), float(inv), _native.ptr(head[2:]),
+                                                 _native.ptr(index_ws), index_bytes, st), "mvsn_cloud_index_build")
+        _native.check(lib.mvsn_cloud_cluster_label(_native.ptr(p), N, float(inv), float(r2), k, _native.ptr(index_ws),
+                                                   index_bytes, _native.ptr(within), _native.ptr(core), _native.ptr(head),
+                                                   _native.ptr(ws), ws_bytes, st), "mvsn_cloud_cluster_label")
+        c, status, bits = head.tolist()    # the one host synchronisation: sizes the outputs
+        _raise_cloud_status(bits, h, "cloud_clusters")     # (eps is the index's max_dist, the cloud its target)
+        if status != 0 or not 0 <= c <= N:
+            raise RuntimeError(f"cloud_clusters: the union-find did not finish (status {status}, {c} clusters of {N} "
+                               "points): its workspace was overwritten during the call")
+        out = CloudClusters(torch.empty((N,), **i64), core.view(torch.bool), within, torch.empty((c,), **i64),
+                            torch.empty((c,), **i64), torch.empty((c,), **i64))
+        _native.check(lib.mvsn_cloud_cluster_emit(
+            _native.ptr(p), N, float(inv), float(r2), _native.ptr(index_ws), index_bytes, _native.ptr(core), _native.ptr(ws),
+            ws_bytes, c, _native.ptr(out.label), _native.ptr(out.count) if c else None,
+            _native.ptr(out.core_count) if c else None, _native.ptr(out.first) if c else None, st),
+            "mvsn_cloud_cluster_emit")
+    return out
+
+
+def _check_clusters(clusters):
+    """(N, C, dev) of a well-formed ``CloudClusters``; ValueError for anything else."""
+    if not isinstance(clusters, tuple) or len(clusters) != 6:
+        raise ValueError("clusters must be a CloudClusters (label, core, within, count, core_count, first)")
+    label, count = clusters[0], clusters[3]
+    if not torch.is_tensor(label) or label.dim() != 1:
+        raise ValueError("clusters.label must be a (N,) int64 tensor")
+    n, dev = int(label.shape[0]), label.device
+    c = int(count.shape[0]) if torch.is_tensor(count) and count.dim() == 1 else -1
+    dtypes = (torch.int64, torch.bool, torch.int32, torch.int64, torch.int64, torch.int64)
+    for name, t, size, dtype in zip(CloudClusters._fields, clusters, (n, n, n, c, c, c), dtypes):
+        if not torch.is_tensor(t) or tuple(t.shape) != (size,) or t.dtype != dtype:
+            raise ValueError(f"clusters.{name} must be a ({max(size, 0)},) {dtype} tensor of this cloud")
+        if t.device != dev:
+            raise ValueError(f"clusters.{name} is on {t.device}, clusters.label on {dev}")
+    if c > n:
+        raise ValueError(f"clusters holds {c} clusters for a cloud of {n} points")
+    return n, c, dev
+
+
+def cloud_cluster_mask(clusters: CloudClusters, *, min_size: Optional[int] = None, keep_largest: Optional[int] = None,
+                       keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(N,) bool: the points of the clusters of ``clusters`` (what ``cloud_clusters`` returned) one keeps, by
+    ``filter_mesh``'s rules on ``count``.  A cluster is kept when ``count >= min_size`` (if given) and, with
+    ``keep_largest`` = k, it is among the k largest of those that passed, by a stable descending sort: ties go to the
+    lower id.  ``keep``, a (C,) bool tensor, replaces both (combining it with one of them, or giving none of the three,
+    is a ValueError).  Noise is always False.  ``points[mask]`` is the cloud without its floaters.  Torch operations on
+    the tensors' own device, no host read."""
+    n, c, dev = _check_clusters(clusters)
+    rules = [r is not None for r in (min_size, keep_largest)]
+    if keep is not None and any(rules):
+        raise ValueError("keep replaces min_size and keep_largest: give it alone")
+    if keep is None and not any(rules):
+        raise ValueError("give one of min_size, keep_largest or keep")
+    lo = _integer_in(min_size, "min_size", 0, 2 ** 63 - 1) if min_size is not None else None
+    top = _integer_in(keep_largest, "keep_largest", 0, 2 ** 63 - 1) if keep_largest is not None else None
+    if keep is not None:
+        if not torch.is_tensor(keep) or tuple(keep.shape) != (c,) or keep.dtype != torch.bool:
+            raise ValueError(f"keep must be a ({c},) bool tensor, one entry per cluster")
+        if keep.device != dev:
+            raise ValueError(f"keep is on {keep.device}, the clusters on {dev}")
+    if c == 0:                         # no cluster: every point is noise
+        return torch.zeros((n,), dtype=torch.bool, device=dev)
+    if keep is None:
+        keep = torch.ones((c,), dtype=torch.bool, device=dev)
+        if lo is not None:
+            keep &= clusters.count >= lo
+        if top is not None:
+            # the passed clusters by falling size, a stable sort: ties keep the order of the ids
+            order = torch.argsort(torch.where(keep, clusters.count, -1), descending=True, stable=True)
+            among = torch.zeros_like(keep)
+            among[order[:top]] = True
+            keep &= among
+    label = clusters.label
+    return (label >= 0) & (label < c) & keep[label.clamp(0, c - 1)]
 
 
 class CloudFeatures(NamedTuple):

@@ -59,7 +59,15 @@ extrapolation to all of them.  --knn: also searches each scene's fused cloud for
 the cloud against itself at the same radius (the same walk: the floor), the share of points with fewer than k neighbours,
 ms per statistical_outlier_mask call and the share kept, and the search composed from torch ops (torch.cdist over chunks of
 the cloud, topk per chunk, topk over the chunks' winners) on the first TORCH_QUERIES points, with its extrapolation to
-all of them.  --global: also registers two samplings of an asymmetric height field from unrelated frames and prints, on a
+all of them.  --clusters: also splits each scene's fused cloud, merged on a voxel grid of one pixel's footprint
+(fusion.voxel_merge), into its density-connected pieces (fusion.cloud_clusters at eps = CLUSTER_EPS_VOXELS voxels,
+min_points = CLUSTER_MIN_POINTS) and reports, as "clusters", N, the number of clusters C, the share of noise, the largest
+cluster's share, ms per call, ms of one cloud_nearest query of the cloud against itself at the same radius (the walk that
+the call makes three times), and the same labelling composed from torch ops -- the edge list of fusion.cloud_knn at k = 64,
+min-label propagation over the core edges with scatter_reduce(amin) plus a pointer jump, repeated to a fixed point with a
+host read per round, the border points from the first core entry of their sorted neighbour list -- with its rounds, how
+many points have more than 64 neighbours (their edge lists are cut short), and whether it finds the same labelling.
+--global: also registers two samplings of an asymmetric height field from unrelated frames and prints, on a
 line of its own as "global", the points per cloud, ms for fusion.cloud_fpfh (each cloud), fusion.feature_nearest (one way
 and mutual) and fusion.cloud_ransac, ms of the match composed from torch ops (torch.cdist + min) and in how many rows its
 index differs, ms of the whole fusion.cloud_register_global, and the pose error before and after the refinement."""
@@ -75,7 +83,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
+from multi_view_stereonet_amd.fusion import (cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
@@ -724,6 +732,63 @@ def run_knn(res, steps, warmup):
     return {"knn": out}
 
 
+CLUSTER_EPS_VOXELS = 2.5
+CLUSTER_MIN_POINTS = 8
+
+
+def torch_cloud_clusters(points, eps, min_points):
+    """The labelling of cloud_clusters composed from torch ops on top of cloud_knn's edge list (k = 64, the most it
+    returns: a point with more neighbours loses edges): (root (N,) int64: the lowest core row of the point's cluster, -1
+    for noise; rounds)."""
+    N = points.shape[0]
+    knn = cloud_knn(points, points, 64, eps, exclude_self=True)
+    finite = torch.isfinite(points).all(dim=1)
+    core = finite & (knn.within + 1 >= min_points)
+    valid = knn.index >= 0
+    to = knn.index.clamp(min=0)
+    rows = torch.arange(N, device=points.device)
+    edge = valid & core[:, None] & core[to]
+    u, v = rows[:, None].expand_as(to)[edge], to[edge]
+    label = rows.clone()
+    rounds = 0
+    while True:
+        new = label.scatter_reduce(0, u, label[v], "amin")
+        new = new[new]
+        rounds += 1
+        if bool(torch.equal(new, label)):          # the host read of the round
+            break
+        label = new
+    near_core = valid & core[to]                  # the lists are sorted by (d2, row): the first core entry is the nearest
+    pos = near_core.int().argmax(dim=1)
+    joins = label[to[rows, pos]]
+    border = finite & ~core & near_core.any(dim=1)
+    return torch.where(core, label, torch.where(border, joins, torch.full_like(label, -1))), rounds
+
+
+def run_clusters(res, fx, steps, warmup):
+    voxel = float(np.float32(float(res.depth[res.depth > 0].median()) / fx))    # one pixel's footprint at the median depth
+    points = voxel_merge(res.points, voxel, colors=res.colors).points.contiguous()
+    eps = CLUSTER_EPS_VOXELS * voxel
+    N = int(points.shape[0])
+    got, times = timed(lambda: cloud_clusters(points, eps, CLUSTER_MIN_POINTS), steps, warmup)
+    nn, qtimes = timed(lambda: cloud_nearest(points, points, eps), steps, warmup)
+    assert torch.equal(got.within, nn.within)
+    (troot, rounds), ttimes = timed(lambda: torch_cloud_clusters(points, eps, CLUSTER_MIN_POINTS), min(steps, 3), 1)
+    C = int(got.first.shape[0])
+    root = torch.where(got.label >= 0, got.first[got.label.clamp(min=0)], got.label) if C else got.label
+    return {"clusters": {
+        "voxel_size": voxel, "eps": eps, "min_points": CLUSTER_MIN_POINTS, "N": N, "C": C,
+        "share_noise": float((got.label < 0).float().mean()), "share_core": float(got.core.float().mean()),
+        "largest_cluster_share": float(got.count.max()) / N if C else 0.0,
+        "neighbours_mean": float(got.within.float().mean()) - 1.0, "neighbours_max": int(got.within.max()) - 1,
+        "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+        "cloud_nearest_ms_mean": float(np.mean(qtimes)),
+        "torch_ms_per_call_mean": float(np.mean(ttimes)), "torch_ms_per_call_min": float(np.min(ttimes)),
+        "torch_rounds": rounds, "points_with_more_than_64_neighbours": int((got.within > 65).sum()),
+        "torch_labelling_equal": bool(torch.equal(troot, root)),
+        "torch_rows_that_differ": int((troot != root).sum())}}
+
+
 GLOBAL_GRID = 128                     # the target is a GLOBAL_GRID^2 sampling of a height field over [-1,1]^2
 GLOBAL_BUMPS = ((0.45, 0.50, 0.22, 0.55), (-0.50, 0.35, 0.35, -0.40), (-0.30, -0.55, 0.15, 0.45), (0.55, -0.40, 0.28, 0.30))
 GLOBAL_FEATURE_RADIUS, GLOBAL_MAX_DIST, GLOBAL_EDGE_SIMILARITY, GLOBAL_HYPOTHESES = 0.25, 0.15, 0.98, 100000
@@ -837,7 +902,7 @@ def run_mesh(sc, steps, warmup):
 
 
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -862,7 +927,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     registered = run_register(sc, res, steps, warmup) if register else {}
     estimated = run_cloud_normals(sc, res, steps, warmup) if cloud_normals_too else {}
     searched = run_knn(res, steps, warmup) if knn else {}
-    return {**gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    split = run_clusters(res, float(sc["K"][0, 0, 0]), steps, warmup) if clusters else {}
+    return {**split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -897,11 +963,14 @@ def main():
     ap.add_argument("--knn", action="store_true",
                     help="also search the fused cloud for every point's k nearest others (cloud_knn) and filter it "
                          "(statistical_outlier_mask), and the torch form of the search")
+    ap.add_argument("--clusters", action="store_true",
+                    help="also split the merged fused cloud into its density-connected pieces (cloud_clusters), and the "
+                         "torch form of the labelling")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
