@@ -170,6 +170,12 @@ SIGNATURES = {
                                  [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),
     "mvsn_cloud_cluster_emit": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_void_p, c_size_t, c_void_p] +
                                 [c_void_p, c_size_t, c_long] + [c_void_p] * 4 + [c_void_p]),
+    "mvsn_cloud_render_workspace_bytes": (c_size_t, [c_int] * 3),
+    "mvsn_cloud_render_camera_batch": (c_int, []),
+    "mvsn_cloud_render": (c_int, [c_void_p, c_long] + [c_void_p] * 4 + [c_int] * 4 + [ctypes.c_float] * 2 +
+                          [c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
+    "mvsn_cloud_visibility": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 3 +
+                              [ctypes.c_float] * 2 + [c_void_p] * 3 + [c_void_p]),
     "mvsn_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_gather_strided": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "mvsn_selftest_mfma": (c_int, [c_void_p]),

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvsn_hip.so")
-SOURCES = ["mvsn_error.hip", "mvsn_setup.hip", "mvsn_warp.hip", "mvsn_chain.hip", "mvsn_chain_wino.hip", "mvsn_chain_band.hip", "mvsn_chain_slab.hip", "mvsn_chain_steps.hip", "mvsn_conv.hip", "mvsn_groupnorm.hip", "mvsn_conv_bf16x3.hip", "mvsn_conv_wino.hip", "mvsn_conv_to1.hip", "mvsn_misc.hip", "mvsn_consistency.hip", "mvsn_prepare.hip", "mvsn_metrics.hip", "mvsn_tower.hip", "mvsn_fusion.hip", "mvsn_voxel.hip", "mvsn_normals.hip", "mvsn_cloud.hip", "mvsn_cloud_register.hip", "mvsn_cloud_normals.hip", "mvsn_cloud_knn.hip", "mvsn_cloud_cluster.hip", "mvsn_cloud_fpfh.hip", "mvsn_cloud_match.hip", "mvsn_cloud_ransac.hip", "mvsn_tsdf.hip", "mvsn_tsdf_raycast.hip", "mvsn_tsdf_align.hip", "mvsn_mesh.hip"]
+SOURCES = ["mvsn_error.hip", "mvsn_setup.hip", "mvsn_warp.hip", "mvsn_chain.hip", "mvsn_chain_wino.hip", "mvsn_chain_band.hip", "mvsn_chain_slab.hip", "mvsn_chain_steps.hip", "mvsn_conv.hip", "mvsn_groupnorm.hip", "mvsn_conv_bf16x3.hip", "mvsn_conv_wino.hip", "mvsn_conv_to1.hip", "mvsn_misc.hip", "mvsn_consistency.hip", "mvsn_prepare.hip", "mvsn_metrics.hip", "mvsn_tower.hip", "mvsn_fusion.hip", "mvsn_voxel.hip", "mvsn_normals.hip", "mvsn_cloud.hip", "mvsn_cloud_register.hip", "mvsn_cloud_normals.hip", "mvsn_cloud_knn.hip", "mvsn_cloud_cluster.hip", "mvsn_cloud_fpfh.hip", "mvsn_cloud_match.hip", "mvsn_cloud_ransac.hip", "mvsn_cloud_render.hip", "mvsn_tsdf.hip", "mvsn_tsdf_raycast.hip", "mvsn_tsdf_align.hip", "mvsn_mesh.hip"]
 
 
 def hipcc() -> str:
@@ -18,7 +18,7 @@ def hipcc() -> str:
 
 
 MANIFEST = LIB + ".sources"
-HEADERS = ["mvsn_common.h", "mvsn_conv_bf16x3.h", "mvsn_chain.h", "mvsn_conv_wino.h", "mvsn_resident.h", "mvsn_voxel.h", "mvsn_geom.h", "mvsn_tsdf_sample.h", "mvsn_cloud.h", "mvsn_pose.h", "mvsn_unionfind.h"]
+HEADERS = ["mvsn_common.h", "mvsn_conv_bf16x3.h", "mvsn_chain.h", "mvsn_conv_wino.h", "mvsn_resident.h", "mvsn_voxel.h", "mvsn_geom.h", "mvsn_tsdf_sample.h", "mvsn_cloud.h", "mvsn_pose.h", "mvsn_unionfind.h", "mvsn_camera.h"]
 # -fno-slp-vectorize: packed f32 VALU (v_pk_add_f32 ...) next to MFMAs costs more issue time than the two
 # scalar ops it replaces (measured: +1.3 % end to end, +3-4 % on the Winograd kernels)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize"]

@@ -23,6 +23,7 @@
 // is one fp32 operation.
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
+#include "mvsn_camera.h"
 #include "mvsn_geom.h"
 
 namespace mvsn {
@@ -30,28 +31,11 @@ namespace mvsn {
 constexpr int TS_THREADS = 256;
 constexpr int TS_VOX = 4;                               // voxels per thread, consecutive in x: one 16-byte access
 constexpr int TS_CAM_BATCH = 32;                        // cameras staged in LDS at once
-constexpr int TS_CAM = 12;                              // floats per camera: P = K T^-1 (3x4), row 2 = T^-1's (z)
 constexpr int TS_BLOCK_VOX = TS_THREADS * TS_VOX;       // voxels per workgroup of the classify / rank / faces kernels
 constexpr float TS_FLT_MAX = 3.4028234e38f;
 constexpr int TS_MAX_EXTENT = 1 << 24;                  // rows, cols and dims up to here: every index is an exact fp32
 
-// P = K T^-1 of one view, fp64, rounded once; K's bottom row is taken to be (0,0,1), so row 2 is T^-1's own
-__device__ inline void tsdf_camera(const float *K, const float *T, float *out) {
-  double Ai[9], Ti[12];
-  inv3_d(T, Ai);
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-#pragma unroll
-    for (int n = 0; n < 3; ++n) Ti[m * 4 + n] = Ai[m * 3 + n];
-    Ti[m * 4 + 3] = -(Ai[m * 3 + 0] * (double)T[3] + Ai[m * 3 + 1] * (double)T[7] + Ai[m * 3 + 2] * (double)T[11]);
-  }
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    out[0 + n] = (float)(((double)K[0] * Ti[n] + (double)K[1] * Ti[4 + n]) + (double)K[2] * Ti[8 + n]);
-    out[4 + n] = (float)(((double)K[4] * Ti[n] + (double)K[5] * Ti[4 + n]) + (double)K[6] * Ti[8 + n]);
-    out[8 + n] = (float)Ti[8 + n];
-  }
-}
+// (the camera of one view, P = K T^-1 as a 3x4: tsdf_camera of mvsn_camera.h, shared with mvsn_cloud_render.hip)
 
 // TS_VOX floats at p: one 16-byte access when `wide`, the first `n` of them one by one otherwise
 __device__ __forceinline__ void tsdf_load(const float *p, bool wide, int n, float *v) {

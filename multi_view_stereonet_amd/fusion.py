@@ -22,7 +22,10 @@ from unrelated frames, the start that ``cloud_register`` needs: ``cloud_fpfh`` (
 point by its FPFH histogram, ``feature_nearest`` (csrc/mvsn_cloud_match.hip) matches the descriptors, and ``cloud_ransac``
 (csrc/mvsn_cloud_ransac.hip) finds the pose that most correspondences agree on.  ``cloud_clusters`` (DESIGN.md section
 24, csrc/mvsn_cloud_cluster.hip) splits a cloud into its density-connected pieces (DBSCAN on the same radius query) and
-``cloud_cluster_mask`` keeps the pieces one asks for: the detached floaters that both local filters pass go.  A dense TSDF volume that integrates the same
+``cloud_cluster_mask`` keeps the pieces one asks for: the detached floaters that both local filters pass go.
+``cloud_render`` (csrc/mvsn_cloud_render.hip) renders a cloud into posed cameras, the nearest point
+per pixel; ``cloud_visibility`` tests every point against depth maps for occlusion and reads per-view maps at the points
+that are seen, and ``cloud_colorize`` colours a bare cloud that way.  A dense TSDF volume that integrates the same
 depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
@@ -1080,6 +1083,202 @@ def cloud_cluster_mask(clusters: CloudClusters, *, min_size: Optional[int] = Non
             keep &= among
     label = clusters.label
     return (label >= 0) & (label < c) & keep[label.clamp(0, c - 1)]
+
+
+class CloudRender(NamedTuple):
+    depth: torch.Tensor              # (V,1,H,W) fp32: z-depth of the nearest point per pixel, 0 where no point hit
+    index: torch.Tensor              # (V,H,W) int64: that point's row, -1 where none
+    colors: Optional[torch.Tensor]   # (V,3,H,W) uint8: its colour (zeros where none), or None without colors
+    normals: Optional[torch.Tensor]  # (V,3,H,W) fp32: its normal (zeros where none), or None without normals
+
+
+class CloudVisibility(NamedTuple):
+    visible: torch.Tensor            # (N,V) bool: view v sees point i
+    count: torch.Tensor              # (N,) int32: the views that see the point
+    values: Optional[torch.Tensor]   # (N,C) fp32: the mean of maps over those views (0 where none), or None without maps
+
+
+RENDER_MAX_RADIUS = 8
+VISIBILITY_MAX_CHANNELS = 16
+_RENDER_MAX_EXTENT, _RENDER_MAX_PIXELS, _RENDER_MAX_VIEWS = 2 ** 24, 2 ** 31 - 1, 65535
+
+
+def _depth_limit_f32(value, name, *, infinite=False, positive=False):
+    """``value`` as np.float32: a finite number >= 0 (> 0 with ``positive``; +inf allowed with ``infinite``);
+    ValueError for anything else, a NaN included."""
+    what = f"{name} must be a {'number > 0 (inf: no limit)' if positive else 'finite number >= 0'}, got {value!r}"
+    if isinstance(value, (bool, str)) or value is None:
+        raise ValueError(what)
+    with np.errstate(all="ignore"):
+        try:
+            v = np.float32(value)
+        except (TypeError, ValueError):
+            raise ValueError(what) from None
+    if np.ndim(v) != 0 or not (v > 0 if positive else v >= 0) or (not infinite and not np.isfinite(v)):
+        raise ValueError(what)
+    return v
+
+
+def _check_render_cameras(K, T_cam_in_world, dev, what):
+    """V of the (V,4,4) floating-point tensors ``K`` and ``T_cam_in_world`` on ``dev``, 1 <= V <= 65535."""
+    if not torch.is_tensor(K) or K.dim() != 3 or tuple(K.shape[1:]) != (4, 4):
+        raise ValueError("K must be a (V,4,4) tensor")
+    V = int(K.shape[0])
+    if not 1 <= V <= _RENDER_MAX_VIEWS:
+        raise ValueError(f"1..65535 views, got {V}")
+    for name, m in (("K", K), ("T_cam_in_world", T_cam_in_world)):
+        if not torch.is_tensor(m) or tuple(m.shape) != (V, 4, 4):
+            raise ValueError(f"{name} must be a ({V},4,4) tensor")
+        if not m.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point tensor, got {m.dtype}")
+        if m.device != dev:
+            raise ValueError(f"{name} is on {m.device}, {what} on {dev}")
+    return V
+
+
+def _check_rows(name, t, N, dtype, dev):
+    if not torch.is_tensor(t) or tuple(t.shape) != (N, 3) or t.dtype != dtype:
+        raise ValueError(f"{name} must be a ({N},3) {dtype} tensor, one row per point")
+    if t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, points on {dev}")
+
+
+def cloud_render(points: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, size, *, radius: int = 0,
+                 colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, min_depth: float = 0.0,
+                 max_depth: float = float("inf")) -> CloudRender:
+    """Render ``points`` (N,3) fp32 into the V cameras ``K``, ``T_cam_in_world`` (V,4,4) with maps of ``size`` = (H,W):
+    per pixel the z-depth and the row of the nearest point that lands on it, and that point's ``colors`` (N,3) uint8 and
+    ``normals`` (N,3) fp32 if given; DESIGN.md section 25, csrc/mvsn_cloud_render.hip.  The cloud needs no order.
+
+    The camera is ``TSDFVolume.integrate``'s: P = K T^-1 formed in fp64 from the float32 values and rounded once, z = P
+    row 2 . (p,1), the pixel (c, r) = floor((u, v) + 0.5) with (u, v) = rows 0, 1 over z, every step one fp32 operation.
+    A point takes part in a view when its coordinates and z are finite, ``min_depth`` < z <= ``max_depth`` and its pixel
+    is within ``radius`` of the map; it covers the flat, screen-aligned square of 2 ``radius`` + 1 pixels around its
+    pixel, clipped to the map.  A pixel takes the least (z, row) of the points that cover it: the nearest point, a tie
+    on z to the lowest row.  ``radius=0`` is the exact point render; ``radius`` up to 8 closes the holes between the
+    points through which a farther surface would show, at a price: a covered neighbour pixel takes the point's own z, so
+    a slanted surface comes forward by up to ``radius`` pixels' worth of its depth gradient and silhouettes grow by
+    ``radius`` pixels.  Where no point lands the depth is 0, the index -1 and colour and normal are zero.
+
+    Every output is a bitwise-reproducible function of the inputs whatever the order of the points: the only atomic is
+    an integer minimum.  N = 0 gives the all-miss render without a launch.  Everything is validated here, before any
+    launch; no host synchronisation."""
+    check_cloud("points", points)
+    N, dev = int(points.shape[0]), points.device
+    V = _check_render_cameras(K, T_cam_in_world, dev, "points")
+    try:
+        H, W = (_integer_in(x, "size", 1, _RENDER_MAX_EXTENT) for x in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be two integers (H,W), each in [1, 2^24], got {size!r}") from None
+    if H * W > _RENDER_MAX_PIXELS:
+        raise ValueError(f"at most 2^31 - 1 pixels per map, got {H} x {W}")
+    R = _integer_in(radius, "radius", 0, RENDER_MAX_RADIUS)
+    if colors is not None:
+        _check_rows("colors", colors, N, torch.uint8, dev)
+    if normals is not None:
+        _check_rows("normals", normals, N, torch.float32, dev)
+    lo = _depth_limit_f32(min_depth, "min_depth")
+    hi = _depth_limit_f32(max_depth, "max_depth", infinite=True, positive=True)
+    if N == 0:                         # no point: every pixel is a miss, nothing to launch
+        return CloudRender(torch.zeros((V, 1, H, W), dtype=torch.float32, device=dev),
+                           torch.full((V, H, W), -1, dtype=torch.int64, device=dev),
+                           torch.zeros((V, 3, H, W), dtype=torch.uint8, device=dev) if colors is not None else None,
+                           torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev) if normals is not None else None)
+    if not points.is_cuda:
+        raise RuntimeError("cloud_render runs on HIP devices only: move the cloud and the cameras to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+    dense = lambda t: t.detach().contiguous() if t is not None else None   # noqa: E731
+    # (every converted copy is held until the launches are enqueued: a temporary's memory could be handed out again)
+    p_c, col_c, nor_c, K_c, T_c = dense(points), dense(colors), dense(normals), f32(K), f32(T_cam_in_world)
+    ws_bytes = lib.mvsn_cloud_render_workspace_bytes(V, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = CloudRender(torch.empty((V, 1, H, W), dtype=torch.float32, device=dev),
+                      torch.empty((V, H, W), dtype=torch.int64, device=dev),
+                      torch.empty((V, 3, H, W), dtype=torch.uint8, device=dev) if colors is not None else None,
+                      torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if normals is not None else None)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_cloud_render(
+            _native.ptr(p_c), N, _native.ptr(col_c), _native.ptr(nor_c), _native.ptr(K_c), _native.ptr(T_c), V, H, W, R,
+            float(lo), float(hi), _native.ptr(ws), ws_bytes,
+            _native.ptr(out.depth), _native.ptr(out.index), _native.ptr(out.colors), _native.ptr(out.normals),
+            _native.stream()), "mvsn_cloud_render")
+    return out
+
+
+def cloud_visibility(points: torch.Tensor, depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, *,
+                     rel_tol: float = 0.01, maps: Optional[torch.Tensor] = None,
+                     min_depth: float = 0.0) -> CloudVisibility:
+    """Which of the V views ``depth`` (V,1,H,W) fp32 with cameras ``K``, ``T_cam_in_world`` (V,4,4) sees each of
+    ``points`` (N,3) fp32 (hidden-point removal), and with ``maps`` (V,C,H,W) fp32, 1 <= C <= 16, the mean of the maps at
+    the point over the views that see it; DESIGN.md section 25, csrc/mvsn_cloud_render.hip.
+
+    Point i is visible in view v when it takes part in ``cloud_render`` at ``radius=0`` (finite, z > ``min_depth``, its
+    nearest pixel inside the map: the same fp32 steps, the same bits of z), the depth D at that pixel is finite and > 0
+    and z <= fma(rel_tol, D, D) in fp32: the point is not behind what the view sees there, by more than ``rel_tol`` of
+    it.  ``depth`` is any z-depth map: a render (with ``rel_tol=0`` every row in ``cloud_render(...).index[v]`` at
+    ``radius=0`` is visible in v against that render's depth, exactly), the network's output, ``TSDFVolume.raycast``'s.
+    ``values`` is the sum of ``maps[v, :, r, c]`` over the visible views in view order, plain fp32 additions, divided
+    once by ``count``; 0 where no view sees the point.  The sample is the nearest pixel's, not a bilinear one, and a
+    visible sample that is not finite is added like any other: mask the maps' holes in ``depth``.
+
+    No atomics: every output is a bitwise-reproducible function of the inputs.  N = 0 gives empties without a launch.
+    Everything is validated here, before the launch; no host synchronisation."""
+    check_cloud("points", points)
+    N = int(points.shape[0])
+
+    def limits(V, H, W, dev):
+        if V > _RENDER_MAX_VIEWS or H * W > _RENDER_MAX_PIXELS or max(H, W) > _RENDER_MAX_EXTENT:
+            raise ValueError(f"at most 65535 views of 2^31 - 1 pixels and 2^24 rows or columns, got {V} of {H} x {W}")
+        if dev != points.device:
+            raise ValueError(f"depth is on {dev}, points on {points.device}")
+    V, H, W, dev = _check_views(depth, K, T_cam_in_world, limits=limits, floating=True)
+    C = None
+    if maps is not None:
+        if not torch.is_tensor(maps) or maps.dim() != 4 or not 1 <= maps.shape[1] <= VISIBILITY_MAX_CHANNELS:
+            raise ValueError(f"maps must be a ({V},C,{H},{W}) tensor with 1 <= C <= {VISIBILITY_MAX_CHANNELS}")
+        C = int(maps.shape[1])
+        _check_frames("maps", maps, V, H, W, C, (torch.float32,), dev)
+    tol = _depth_limit_f32(rel_tol, "rel_tol")
+    lo = _depth_limit_f32(min_depth, "min_depth")
+    if N == 0:                         # no point, nothing to launch
+        return CloudVisibility(torch.empty((0, V), dtype=torch.bool, device=dev),
+                               torch.empty((0,), dtype=torch.int32, device=dev),
+                               torch.empty((0, C), dtype=torch.float32, device=dev) if C else None)
+    if not points.is_cuda:
+        raise RuntimeError("cloud_visibility runs on HIP devices only: move the cloud and the depth maps to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+    # (every converted copy is held until the launch is enqueued: a temporary's memory could be handed out again)
+    p_c, d_c, K_c, T_c = points.detach().contiguous(), depth.detach().contiguous(), f32(K), f32(T_cam_in_world)
+    m_c = maps.detach().contiguous() if C else None
+    visible = torch.empty((N, V), dtype=torch.uint8, device=dev)
+    count = torch.empty((N,), dtype=torch.int32, device=dev)
+    values = torch.empty((N, C), dtype=torch.float32, device=dev) if C else None
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_cloud_visibility(
+            _native.ptr(p_c), N, _native.ptr(d_c), _native.ptr(m_c), C or 0, _native.ptr(K_c), _native.ptr(T_c), V, H, W,
+            float(tol), float(lo), _native.ptr(visible), _native.ptr(count),
+            _native.ptr(values), _native.stream()), "mvsn_cloud_visibility")
+    return CloudVisibility(visible.view(torch.bool), count, values)
+
+
+def cloud_colorize(points: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, K: torch.Tensor,
+                   T_cam_in_world: torch.Tensor, *, rel_tol: float = 0.01):
+    """Colours for a bare cloud -- one that was merged, registered or read back from a file and has lost the pixels it
+    came from: (colors (N,3) uint8, count (N,) int32).  ``cloud_visibility(points, depth, ..., maps=images)`` with
+    ``images`` (V,3,H,W) fp32 in [-1,1], then the conversion ``fuse_depthmaps`` applies, rint((c + 1) * 127.5) in fp64
+    clamped to 0..255: the mean colour over the views that see the point, so a point never takes the colour of what
+    stands in front of it.  A point no view sees gets (0,0,0) and ``count`` 0."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError("images must be a (V,3,H,W) tensor")
+    vis = cloud_visibility(points, depth, K, T_cam_in_world, rel_tol=rel_tol, maps=images)
+    q = torch.round((vis.values.to(torch.float64) + 1.0) * 127.5)         # (ties to even, as rint)
+    q = torch.nan_to_num(q, nan=0.0).clamp_(0.0, 255.0)                  # (a NaN gives 0, as mvsn_fusion_emit's)
+    q = torch.where((vis.count > 0)[:, None], q, torch.zeros_like(q))
+    return q.to(torch.uint8), vis.count
 
 
 class CloudFeatures(NamedTuple):

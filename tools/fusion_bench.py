@@ -67,6 +67,14 @@ the call makes three times), and the same labelling composed from torch ops -- t
 min-label propagation over the core edges with scatter_reduce(amin) plus a pointer jump, repeated to a fixed point with a
 host read per round, the border points from the first core entry of their sorted neighbour list -- with its rounds, how
 many points have more than 64 neighbours (their edge lists are cut short), and whether it finds the same labelling.
+--render: also renders each scene's fused cloud back into the scene's views (fusion.cloud_render) and reports, as
+"render", N, V, the map size, the share of pixels hit and ms per call at radius 0 and 1, ms per fusion.cloud_visibility of
+the cloud against the scene's depth maps with and without the images as maps, whether every rendered row is visible
+against its own render with no tolerance, and the radius-0 render composed from torch ops (the projection as nested
+addcmul, then scatter_reduce_(amin) on int64 keys, view by view) with the pixels whose depth bits differ from the
+kernel's, and its exact form (every fused multiply-add of a row formed in fp64 and rounded once) with whether that gives
+the same depth bits; with a library built with -DMVSN_RENDER_COUNT (MVSN_HIPCC_FLAGS) also the splat's candidates and the
+atomics it issued.
 --global: also registers two samplings of an asymmetric height field from unrelated frames and prints, on a
 line of its own as "global", the points per cloud, ms for fusion.cloud_fpfh (each cloud), fusion.feature_nearest (one way
 and mutual) and fusion.cloud_ransac, ms of the match composed from torch ops (torch.cdist + min) and in how many rows its
@@ -83,7 +91,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
-from multi_view_stereonet_amd.fusion import (cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
+from multi_view_stereonet_amd.fusion import (cloud_render, cloud_visibility, cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
 from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
@@ -789,6 +797,102 @@ def run_clusters(res, fx, steps, warmup):
         "torch_rows_that_differ": int((troot != root).sum())}}
 
 
+def torch_cloud_render(points, K, T, H, W, exact=False):
+    """cloud_render at radius 0 composed from torch ops on the same device: per view the same camera (K T^-1 in fp64,
+    rounded once), the rows as nested addcmul, the same pixel rule, then scatter_reduce_(amin) on int64 keys
+    (bits of z << 32) | row -- what a caller had to write without the kernel.  addcmul rounds the product before the sum,
+    so its z differs from the kernel's fused multiply-add in the last bit at many pixels; with ``exact`` every step of a
+    row is formed in fp64 (the product of two fp32 numbers is exact there) and rounded to fp32 once: the kernel's fused
+    multiply-add but for a double rounding, about once in 2^29 operations.  Returns (depth (V,H,W), index (V,H,W))."""
+    V, N = K.shape[0], points.shape[0]
+    Ti = torch.linalg.inv(T.double())
+    P = torch.cat([K[:, :2, :3].double() @ Ti[:, :3, :], Ti[:, 2:3, :]], dim=1).float()             # (V,3,4)
+    x, y, z = (points[:, k].contiguous() for k in range(3))
+    rows = torch.arange(N, dtype=torch.int64, device=points.device)
+    finite = torch.isfinite(points).all(dim=1)
+    keys = torch.full((V, H * W), torch.iinfo(torch.int64).max, dtype=torch.int64, device=points.device)
+
+    xd, yd, zd = (x.double(), y.double(), z.double()) if exact else (None, None, None)
+
+    def row(p):
+        if not exact:
+            return torch.addcmul(torch.addcmul(torch.addcmul(p[3].expand(N), z, p[2]), y, p[1]), x, p[0])
+        acc = p[3].double().expand(N)
+        for coord, entry in ((zd, p[2]), (yd, p[1]), (xd, p[0])):
+            acc = (coord * entry.double() + acc).float().double()
+        return acc.float()
+    for v in range(V):
+        zc = row(P[v, 2])
+        fc, fr = torch.floor(row(P[v, 0]) / zc + 0.5), torch.floor(row(P[v, 1]) / zc + 0.5)
+        ok = finite & torch.isfinite(zc) & (zc > 0) & (fc >= 0) & (fc < W) & (fr >= 0) & (fr < H)
+        pix = (fr[ok].to(torch.int64) * W + fc[ok].to(torch.int64))
+        key = (zc[ok].view(torch.int32).to(torch.int64) << 32) | rows[ok]
+        keys[v].scatter_reduce_(0, pix, key, "amin")
+    hit = keys != torch.iinfo(torch.int64).max
+    depth = torch.where(hit, (keys >> 32).to(torch.int32).view(torch.float32), torch.zeros((), device=points.device))
+    index = torch.where(hit, keys & 0xFFFFFFFF, torch.full_like(keys, -1))
+    return depth.reshape(V, H, W), index.reshape(V, H, W)
+
+
+def render_debug_counts():
+    """(candidates, atomics) so far of a library built with -DMVSN_RENDER_COUNT, None of the usual build."""
+    import ctypes
+    fn = getattr(_native.load(), "mvsn_cloud_render_debug_counts", None)
+    if fn is None:
+        return None
+    out = (ctypes.c_uint64 * 2)()
+    torch.cuda.synchronize()
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p]
+    if fn(out) != 0:
+        return None
+    return int(out[0]), int(out[1])
+
+
+def run_render(sc, res, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    V, _, H, W = depth.shape
+    points = res.points
+    N = int(points.shape[0])
+    out = {"N": N, "V": V, "rows": H, "cols": W,
+           "workspace_bytes": int(_native.load().mvsn_cloud_render_workspace_bytes(V, H, W))}
+    for radius in (0, 1):
+        before = render_debug_counts()
+        r = cloud_render(points, K, T, (H, W), radius=radius)
+        after = render_debug_counts()
+        if before is not None and after is not None:
+            cand, atom = after[0] - before[0], after[1] - before[1]
+            out[f"radius{radius}_candidates"], out[f"radius{radius}_atomics"] = cand, atom
+            out[f"radius{radius}_atomics_per_candidate"] = atom / max(cand, 1)
+        _, times = timed(lambda: cloud_render(points, K, T, (H, W), radius=radius), steps, warmup)
+        out[f"radius{radius}_ms_mean"], out[f"radius{radius}_ms_min"] = float(np.mean(times)), float(np.min(times))
+        out[f"radius{radius}_share_of_pixels_hit"] = float((r.index >= 0).float().mean())
+        if radius == 0:
+            exact = r
+    _, times = timed(lambda: cloud_render(points, K, T, (H, W), colors=res.colors), steps, warmup)
+    out["radius0_with_colors_ms_mean"] = float(np.mean(times))
+    vis, times = timed(lambda: cloud_visibility(points, depth, K, T), steps, warmup)
+    out["visibility_ms_mean"], out["visibility_ms_min"] = float(np.mean(times)), float(np.min(times))
+    out["views_per_point_mean"] = float(vis.count.float().mean())
+    _, times = timed(lambda: cloud_visibility(points, depth, K, T, maps=images), steps, warmup)
+    out["visibility_with_maps_ms_mean"], out["visibility_with_maps_ms_min"] = float(np.mean(times)), float(np.min(times))
+    own = cloud_visibility(points, exact.depth, K, T, rel_tol=0.0)
+    out["rendered_rows_visible_with_no_tolerance"] = all(      # (section 25's exact property, at the workload's size)
+        bool(own.visible[exact.index[v][exact.index[v] >= 0], v].all()) for v in range(V))
+    (tdepth, tindex), ttimes = timed(lambda: torch_cloud_render(points, K, T, H, W), min(steps, 3), 1)
+    out["torch_ms_mean"], out["torch_ms_min"] = float(np.mean(ttimes)), float(np.min(ttimes))
+    same = tdepth.view(torch.int32) == exact.depth[:, 0].view(torch.int32)
+    out["torch_pixels_whose_depth_bits_differ"] = int((~same).sum())
+    out["torch_pixels_whose_index_differs"] = int((tindex != exact.index).sum())
+    # the same composition with every fused multiply-add formed exactly: the check that both compute the same thing
+    (edepth, eindex), etimes = timed(lambda: torch_cloud_render(points, K, T, H, W, exact=True), min(steps, 3), 1)
+    same = edepth.view(torch.int32) == exact.depth[:, 0].view(torch.int32)
+    out["torch_exact_ms_mean"] = float(np.mean(etimes))
+    out["torch_exact_depth_bits_equal"] = bool(same.all())
+    out["torch_exact_pixels_whose_depth_bits_differ"] = int((~same).sum())
+    out["torch_exact_pixels_whose_index_differs"] = int((eindex != exact.index).sum())
+    return {"render": out}
+
+
 GLOBAL_GRID = 128                     # the target is a GLOBAL_GRID^2 sampling of a height field over [-1,1]^2
 GLOBAL_BUMPS = ((0.45, 0.50, 0.22, 0.55), (-0.50, 0.35, 0.35, -0.40), (-0.30, -0.55, 0.15, 0.45), (0.55, -0.40, 0.28, 0.30))
 GLOBAL_FEATURE_RADIUS, GLOBAL_MAX_DIST, GLOBAL_EDGE_SIMILARITY, GLOBAL_HYPOTHESES = 0.25, 0.15, 0.98, 100000
@@ -902,7 +1006,7 @@ def run_mesh(sc, steps, warmup):
 
 
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -928,7 +1032,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     estimated = run_cloud_normals(sc, res, steps, warmup) if cloud_normals_too else {}
     searched = run_knn(res, steps, warmup) if knn else {}
     split = run_clusters(res, float(sc["K"][0, 0, 0]), steps, warmup) if clusters else {}
-    return {**split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    drawn = run_render(sc, res, steps, warmup) if render else {}
+    return {**drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -966,11 +1071,15 @@ def main():
     ap.add_argument("--clusters", action="store_true",
                     help="also split the merged fused cloud into its density-connected pieces (cloud_clusters), and the "
                          "torch form of the labelling")
+    ap.add_argument("--render", action="store_true",
+                    help="also render the fused cloud back into the input views (cloud_render at radius 0 and 1), test its "
+                         "points for occlusion (cloud_visibility, with and without maps), and the torch form of the render")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
-                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters)), flush=True)
+                             a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
+                             a.render)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
