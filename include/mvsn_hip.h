@@ -1075,6 +1075,86 @@ int mvsn_cloud_visibility(const float *points, long n, const float *depth, const
                           const float *K, const float *T_cam_in_world, int n_views, int rows, int cols, float rel_tol,
                           float min_depth, uint8_t *visible, int *count, float *values, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Area-uniform samples of a triangle mesh's surface (multi_view_stereonet_amd/mesh.py: mesh_sample; the semantics and
+ * every operation are DESIGN.md section 26).
+ *   vertices (n_vertices,3) fp32   faces (n_faces,3) int64   1 <= n_vertices, n_faces, n <= 2^31 - 1
+ *   A face with an index outside [0, n_vertices) or a vertex that is not finite takes no part (area 0; its indices are
+ *   never used as addresses).  The area of a face is 0.5 sqrt(|(b - a) x (c - a)|^2) in fp64, every step one operation;
+ *   with A_max the largest and e = ilogb(A_max), q_f = (uint64) floor(area_f 2^(31 - e)) < 2^32 and
+ *   P[f] = q_0 + ... + q_f, an integer scan: a pure function of the mesh.  A face below 2^-31 of the largest has q = 0.
+ *   workspace: mvsn_mesh_sample_workspace_bytes(n_faces) bytes (0 for sizes the entries refuse), 16-byte aligned: a head
+ *     of 32 bytes, 8 bytes per face (the area, then q, then P, in place), 16 bytes per 256 faces.
+ * mvsn_mesh_sample_prefix (the head cleared, area, quantise, the 64-bit scan, prefix, a 16-byte device copy):
+ *   -> result (2 int64): [0] P[n_faces - 1], [1] status bits (MVSN_MESH_SAMPLE_STATUS_*; 0 = fine).  Reading the two
+ *      words back is the one host synchronisation of a sampling; the workspace holds P.
+ * mvsn_mesh_sample_draw (one launch), on the workspace handed on unchanged: sample i draws
+ *   z_j = fin(seed + (3 i + j) 0x9E3779B97F4A7C15), j = 1, 2, 3, with splitmix64's finaliser as mvsn_cloud_ransac forms
+ *   it; pick = umul64hi(z_1, P[n_faces - 1]); the face is the first f with P[f] > pick; u = (z_2 >> 11) 2^-53,
+ *   v = (z_3 >> 11) 2^-53, and (1 - u, 1 - v) in their place where u + v > 1; the weights are ((1 - u) - v, u, v) and the
+ *   point a + u (b - a) + v (c - a), in fp64, rounded to fp32 once.
+ *   -> points (n,3) fp32   face (n) int64   weights (n,3) fp32
+ *      out_normals (n,3) fp32 with normals (n_vertices,3) fp32, or both NULL: the weighted sum of the three vertex
+ *      normals in fp64, normalised; (0,0,0) where its length is 0 or not finite
+ *      out_colors (n,3) u8 with colors (n_vertices,3) u8, or both NULL: the weighted sum in fp64, floor(x + 0.5),
+ *      clamped to [0, 255]
+ *   With a total of 0 (the status says so) every face is -1 and everything else 0.
+ * Integer atomics only (one 64-bit maximum), integer sums: every output is a bitwise-reproducible function of
+ * (vertices, faces, n, seed), and sample i does not depend on n.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_MESH_SAMPLE_STATUS_NO_AREA 1   /* every face has weight 0: there is nothing to draw from */
+size_t mvsn_mesh_sample_workspace_bytes(long n_faces);
+int mvsn_mesh_sample_prefix(const float *vertices, long n_vertices, const int64_t *faces, long n_faces, int64_t *result,
+                            void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_sample_draw(const float *vertices, long n_vertices, const int64_t *faces, long n_faces,
+                          const void *workspace, size_t workspace_bytes, long n, uint64_t seed, const float *normals,
+                          const uint8_t *colors, float *points, int64_t *face, float *weights, float *out_normals,
+                          uint8_t *out_colors, mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exact point-to-triangle-mesh distance within a radius (multi_view_stereonet_amd/mesh.py: mesh_nearest; the semantics,
+ * the distance operation by operation and the proof that the cells visited are enough are DESIGN.md section 26).  The
+ * mesh counterpart of mvsn_cloud_nearest: the result is that of the brute force over every (query, face) pair.
+ *   query (nq,3), vertices (n_vertices,3) fp32   faces (n_faces,3) int64   1 <= nq, n_vertices, n_faces <= 2^31 - 1
+ *   inv_cell = 1 / max_dist and r2 = max_dist^2, each formed once in fp32 by the caller.
+ *   A face with an index outside [0, n_vertices) or a vertex that is not finite takes no part (never dereferenced).  The
+ *   closest point x of a face to q is formed in fp64 with + - x / and compares alone (the plane's barycentric weights
+ *   where all three are >= 0, else the nearest of the three sides in the order (a,b), (b,c), (c,a), ties to the earlier:
+ *   a collinear face degenerates to its sides, a face (v,v,v) to the point); x32 = fp32(x) clamped per axis to the
+ *   face's box; d2 = (dx dx + dy dy) + dz dz in fp32 of q - x32, mvsn_cloud_nearest's operations; a face is within when
+ *   d2 <= r2; the nearest is the least key (uint64(bits of d2) << 32) | row: ties to the lowest row.
+ *   The index is mvsn_cloud_index_build's hash grid over (cell, face) pairs: a face goes into every cell of the box
+ *   floor(min inv_cell) .. floor(max inv_cell) per axis; a face whose box holds more than
+ *   MVSN_MESH_NEAREST_BOX_CELLS cells goes on the list of large faces that every query tests directly.
+ * mvsn_mesh_nearest_count (one launch):
+ *   -> result (3 int64): [0] the pairs, [1] the large faces, [2] status bits (MVSN_MESH_NEAREST_STATUS_*; 0 = fine).
+ *      Reading the three words back is the one host synchronisation of a query: it sizes the workspace.
+ *   workspace: mvsn_mesh_nearest_workspace_bytes(pairs, large) bytes (0 for counts above 2^31 - 1), 16-byte aligned: a
+ *     head of 16 bytes, 20 bytes per slot of the table (a power of two >= 2 pairs, at least 1024), 4 bytes per pair and
+ *     per large face, 12 bytes per 1024 slots.
+ * mvsn_mesh_nearest_build (six launches), with the counts as read back.
+ * mvsn_mesh_nearest (one launch, one thread per query), on the workspace handed on unchanged:
+ *   -> dist2 (nq) fp32, +inf where no face is within   face (nq) int64, -1 where none   point (nq,3) fp32: x32 of the
+ *      winner, 0 where none   weights (nq,3) fp32: its barycentric weights, 0 where none   within (nq) int32: the faces
+ *      within, each counted once
+ *   A query that is not finite gets (+inf, -1, 0, 0, 0); a query may lie anywhere.
+ * mvsn_mesh_nearest_box_cells: MVSN_MESH_NEAREST_BOX_CELLS as the library was built with it.
+ * Integer atomics only: every output is a bitwise-reproducible function of the inputs, whatever order the faces come in
+ * (`face` follows the rows) and whatever order the atomics arrive in.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_MESH_NEAREST_BOX_CELLS 512
+#define MVSN_MESH_NEAREST_STATUS_RANGE 1   /* a finite vertex's cell lies outside [-2^20, 2^20): max_dist too small */
+int mvsn_mesh_nearest_box_cells(void);
+size_t mvsn_mesh_nearest_workspace_bytes(long n_pairs, long n_large);
+int mvsn_mesh_nearest_count(const float *vertices, long n_vertices, const int64_t *faces, long n_faces, float inv_cell,
+                            int64_t *result, mvsn_stream_t stream);
+int mvsn_mesh_nearest_build(const float *vertices, long n_vertices, const int64_t *faces, long n_faces, float inv_cell,
+                            long n_pairs, long n_large, void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_nearest(const float *query, long nq, const float *vertices, long n_vertices, const int64_t *faces,
+                      long n_faces, float inv_cell, float r2, long n_pairs, long n_large, const void *workspace,
+                      size_t workspace_bytes, float *dist2, int64_t *face, float *point, float *weights, int *within,
+                      mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -165,6 +165,17 @@ SIGNATURES = {
     "mvsn_mesh_select": (c_int, [c_void_p] * 3 + [c_long] * 3 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_mesh_compact": (c_int, [c_void_p] * 7 + [c_long] * 3 + [c_void_p, c_size_t, c_long, c_long] + [c_void_p] * 7 +
                           [c_void_p]),
+    "mvsn_mesh_sample_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_mesh_sample_prefix": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_sample_draw": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_size_t, c_long, ctypes.c_uint64] +
+                              [c_void_p] * 7 + [c_void_p]),
+    "mvsn_mesh_nearest_box_cells": (c_int, []),
+    "mvsn_mesh_nearest_workspace_bytes": (c_size_t, [c_long] * 2),
+    "mvsn_mesh_nearest_count": (c_int, [c_void_p, c_long, c_void_p, c_long, ctypes.c_float, c_void_p, c_void_p]),
+    "mvsn_mesh_nearest_build": (c_int, [c_void_p, c_long, c_void_p, c_long, ctypes.c_float, c_long, c_long, c_void_p,
+                                        c_size_t, c_void_p]),
+    "mvsn_mesh_nearest": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long] + [ctypes.c_float] * 2 +
+                          [c_long, c_long, c_void_p, c_size_t] + [c_void_p] * 5 + [c_void_p]),
     "mvsn_cloud_cluster_workspace_bytes": (c_size_t, [c_long]),
     "mvsn_cloud_cluster_label": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_long, c_void_p, c_size_t] +
                                  [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),

@@ -9,6 +9,10 @@ components one asks for and renumbers the faces, and ``fusion.write_ply(..., fac
 The graph has the vertex rows as nodes and the sides of the faces as edges: two faces that share one vertex are
 connected, two vertices at one position in different rows are not.  Everything is integer work and a pure function of
 the mesh: the outputs do not depend on the order of the faces, on the order of a face's indices, or on any race.
+
+Scoring a mesh (csrc/mvsn_mesh_sample.hip, csrc/mvsn_mesh_nearest.hip): ``mesh_sample`` draws an
+area-uniform cloud from the surface, reproducibly, and ``mesh_nearest`` is the exact distance of points to the surface
+within a radius, the mesh counterpart of ``fusion.cloud_nearest``; ``metrics.mesh_metrics`` is built on the two.
 """
 from typing import NamedTuple, Optional
 
@@ -202,3 +206,163 @@ def filter_mesh(mesh: TSDFMesh, *, min_faces: Optional[int] = None, min_vertices
             _native.ptr(res.mesh.colors), _native.ptr(res.mesh.cell), _native.ptr(res.mesh.faces) if fo else None,
             _native.ptr(res.vertex_rows), _native.ptr(res.face_rows) if fo else None, st), "mvsn_mesh_compact")
     return res
+
+
+# ---- scoring a mesh: surface samples and the point-to-mesh distance ---------------------------
+NEAREST_BOX_CELLS = 512              # a face whose box of cells is larger goes on the list every query tests directly
+MESH_SAMPLE_STATUS_NO_AREA = 1
+MESH_NEAREST_STATUS_RANGE = 1
+
+
+class MeshSamples(NamedTuple):
+    points: torch.Tensor             # (n,3) fp32 the sample positions
+    face: torch.Tensor               # (n,) int64 the face each sample was drawn from
+    weights: torch.Tensor            # (n,3) fp32 barycentric weights
+    normals: Optional[torch.Tensor]  # (n,3) fp32 interpolated vertex normals, or None
+    colors: Optional[torch.Tensor]   # (n,3) uint8 interpolated vertex colours, or None
+
+
+class MeshNearest(NamedTuple):
+    dist2: torch.Tensor              # (N,) fp32 squared distance to the mesh, +inf where no face is within max_dist
+    face: torch.Tensor               # (N,) int64 the nearest face's row, -1 where none
+    point: torch.Tensor              # (N,3) fp32 the closest point on the mesh, 0 where none
+    weights: torch.Tensor            # (N,3) fp32 its barycentric weights, 0 where none
+    within: torch.Tensor             # (N,) int32 the number of faces within max_dist
+
+
+def _check_surface(vertices, faces):
+    """(M, F, device) of a mesh given as vertices (M,3) fp32 and faces (F,3) int64 on one device; ValueError otherwise."""
+    if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError("vertices must be a (M,3) float32 tensor")
+    m, f = _check_faces(faces, int(vertices.shape[0]))
+    if faces.device != vertices.device:
+        raise ValueError(f"faces are on {faces.device}, vertices on {vertices.device}")
+    return m, f, vertices.device
+
+
+def mesh_sample(vertices: torch.Tensor, faces: torch.Tensor, n: int, *, seed: int = 0,
+                normals: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None) -> MeshSamples:
+    """``n`` points drawn uniformly by area from the surface of the mesh ``vertices`` (M,3) fp32, ``faces`` (F,3) int64:
+    what turns a mesh into a cloud for ``metrics.cloud_metrics`` (csrc/mvsn_mesh_sample.hip).
+
+    The areas are taken in fp64 and turned into exact integers, ``q = floor(area * 2^(31 - ilogb(largest area)))``; their
+    prefix is an integer scan, so it does not depend on any order of summation.  A face with an index outside [0, M) or
+    a vertex that is not finite has area 0, and so has a face below 2^-31 of the largest face: none of them is ever
+    drawn.  Sample i takes three splitmix64 draws of ``seed`` (an integer in [0, 2^64)): the first picks the face through
+    the prefix, the other two are the barycentric pair (u, v), folded at u + v > 1; no square root is taken.  The point
+    is ``a + u (b - a) + v (c - a)`` in fp64, rounded to fp32 once, and ``weights`` are ``((1 - u) - v, u, v)``.
+    ``normals`` (M,3) fp32 gives the normalised weighted sum of the face's vertex normals, (0,0,0) where the sum has no
+    direction; ``colors`` (M,3) uint8 the weighted sum rounded to nearest.
+
+    The result is a bitwise-reproducible function of ``(vertices, faces, n, seed)``, and sample i does not depend on
+    ``n``: ``mesh_sample(.., n)[:m]`` is ``mesh_sample(.., m)``.  It does depend on the order of the faces: a permuted
+    mesh has another prefix, so the same draw lands in another face (the distribution is the same).  ``n`` = 0 is
+    answered without a launch; ``n`` > 0 on a mesh without area is a ValueError.  Everything is validated here, before
+    any launch; the one host synchronisation is the read of (total, status) between the prefix and the draws."""
+    m, f, dev = _check_surface(vertices, faces)
+    n = _integer(n, "n", 0)
+    if n > MAX_ROWS:
+        raise ValueError(f"at most 2^31 - 1 samples, got n = {n}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    for name, t, dtype in (("normals", normals, torch.float32), ("colors", colors, torch.uint8)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (m, 3) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a ({m},3) {dtype} tensor, one row per vertex")
+        if t.device != dev:
+            raise ValueError(f"{name} are on {t.device}, vertices on {dev}")
+    out = MeshSamples(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
+                      torch.empty((n, 3), dtype=torch.float32, device=dev),
+                      torch.empty((n, 3), dtype=torch.float32, device=dev) if normals is not None else None,
+                      torch.empty((n, 3), dtype=torch.uint8, device=dev) if colors is not None else None)
+    if n == 0:                         # nothing to draw, nothing to launch
+        return out
+    if m == 0 or f == 0:               # no face, no area: known without a launch
+        raise ValueError("the mesh has no area: nothing to draw samples from")
+    if not vertices.is_cuda:
+        raise RuntimeError("mesh_sample runs on HIP devices only: make the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    v, fc = vertices.detach().contiguous(), faces.detach().contiguous()
+    nor = normals.detach().contiguous() if normals is not None else None
+    col = colors.detach().contiguous() if colors is not None else None
+    ws_bytes = lib.mvsn_mesh_sample_workspace_bytes(f)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_mesh_sample_prefix(_native.ptr(v), m, _native.ptr(fc), f, _native.ptr(head), _native.ptr(ws),
+                                                  ws_bytes, st), "mvsn_mesh_sample_prefix")
+        total, status = head.tolist()  # the one host synchronisation
+        if status & MESH_SAMPLE_STATUS_NO_AREA or total <= 0:
+            raise ValueError("the mesh has no area: nothing to draw samples from")
+        _native.check(lib.mvsn_mesh_sample_draw(_native.ptr(v), m, _native.ptr(fc), f, _native.ptr(ws), ws_bytes, n, seed,
+                                                _native.ptr(nor), _native.ptr(col), _native.ptr(out.points),
+                                                _native.ptr(out.face), _native.ptr(out.weights), _native.ptr(out.normals),
+                                                _native.ptr(out.colors), st), "mvsn_mesh_sample_draw")
+    return out
+
+
+def mesh_nearest(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, max_dist: float) -> MeshNearest:
+    """For every row of ``points`` (N,3) fp32 the nearest face of the mesh ``vertices`` (M,3) fp32, ``faces`` (F,3) int64
+    within ``max_dist``: the squared distance, the face's row, the closest point on it with its barycentric weights, and
+    how many faces lie within ``max_dist``.  The mesh counterpart of ``fusion.cloud_nearest`` (DESIGN.md section 26,
+    csrc/mvsn_mesh_nearest.hip), and the same contract: the result is exactly that of the brute force over every (point,
+    face) pair in the stated arithmetic, ties to the lowest face row, bitwise reproducible, and independent of the order
+    of the faces except that ``face`` follows the rows.
+
+    The closest point x of a face is formed in fp64 (the plane's barycentric weights where all three are >= 0, else the
+    nearest of the three sides; a collinear face degenerates to its sides, a face (v,v,v) to the point), rounded to fp32
+    once and clamped to the face's box; the squared distance is ``cloud_nearest``'s fp32 ``(dx*dx + dy*dy) + dz*dz`` to
+    it, within when ``<= float32(max_dist)**2``.  A face with an index outside [0, M) or a vertex that is not finite
+    takes no part; a point that is not finite gets (+inf, -1, 0, 0, 0).  The faces go on a grid of cell size ``max_dist``
+    anchored at (0,0,0), each into every cell of its box; a face of more than ``NEAREST_BOX_CELLS`` cells is tested by
+    every point directly.  A finite vertex 2^20 cells or more from the origin raises ValueError, and so do more than
+    2^31 - 1 (cell, face) pairs: ``max_dist`` is too small for the mesh.  N = 0, F = 0 or M = 0 gives the all-miss
+    answer without a launch.  Everything is validated here, before any launch; the one host synchronisation is the read
+    of (pairs, large faces, status) that sizes the workspace."""
+    from .fusion import VOXEL_CELL_LIMIT, check_cloud, cloud_radius_scalars
+    check_cloud("points", points)
+    m, f, dev = _check_surface(vertices, faces)
+    if points.device != dev:
+        raise ValueError(f"points are on {points.device}, vertices on {dev}")
+    h, inv, r2 = cloud_radius_scalars(max_dist)
+    N = int(points.shape[0])
+    out = MeshNearest(torch.empty((N,), dtype=torch.float32, device=dev), torch.empty((N,), dtype=torch.int64, device=dev),
+                      torch.empty((N, 3), dtype=torch.float32, device=dev), torch.empty((N, 3), dtype=torch.float32, device=dev),
+                      torch.empty((N,), dtype=torch.int32, device=dev))
+
+    def miss():
+        out.dist2.fill_(float("inf")), out.face.fill_(-1), out.point.zero_(), out.weights.zero_(), out.within.zero_()
+        return out
+    if N == 0 or f == 0 or m == 0:     # nothing to find, nothing to launch
+        return miss()
+    if not points.is_cuda:
+        raise RuntimeError("mesh_nearest runs on HIP devices only: make the points and the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    q, v, fc = points.detach().contiguous(), vertices.detach().contiguous(), faces.detach().contiguous()
+    head = torch.empty(3, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_mesh_nearest_count(_native.ptr(v), m, _native.ptr(fc), f, float(inv), _native.ptr(head), st),
+                      "mvsn_mesh_nearest_count")
+        pairs, large, status = head.tolist()   # the one host synchronisation: sizes the workspace
+        if status & MESH_NEAREST_STATUS_RANGE:
+            raise ValueError(f"max_dist too small for the mesh's extent: a vertex lies 2^20 = {VOXEL_CELL_LIMIT} "
+                             f"cells of {float(h):g} or more from the origin")
+        if pairs > MAX_ROWS:
+            raise ValueError(f"max_dist ({float(h):g}) too small for the mesh's faces: {pairs} (cell, face) pairs, "
+                             "at most 2^31 - 1")
+        if pairs == 0 and large == 0:  # no face takes part
+            return miss()
+        ws_bytes = lib.mvsn_mesh_nearest_workspace_bytes(pairs, large)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.mvsn_mesh_nearest_build(_native.ptr(v), m, _native.ptr(fc), f, float(inv), pairs, large,
+                                                  _native.ptr(ws), ws_bytes, st), "mvsn_mesh_nearest_build")
+        _native.check(lib.mvsn_mesh_nearest(_native.ptr(q), N, _native.ptr(v), m, _native.ptr(fc), f, float(inv), float(r2),
+                                            pairs, large, _native.ptr(ws), ws_bytes, _native.ptr(out.dist2),
+                                            _native.ptr(out.face), _native.ptr(out.point), _native.ptr(out.weights),
+                                            _native.ptr(out.within), st), "mvsn_mesh_nearest")
+    return out

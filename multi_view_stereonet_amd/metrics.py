@@ -227,6 +227,16 @@ def _host_nearest_dist2(query: torch.Tensor, target: torch.Tensor, h, inv, r2) -
     return out
 
 
+def _capped_sums(points, d2, h, tau2):
+    """[the finite rows of ``points``, the fp64 sum over them of min(sqrt(d2), h), those with d2 <= tau2] as fp64
+    scalars where the tensors live: what ``cloud_metrics`` and ``mesh_metrics`` read back at the end."""
+    finite = torch.isfinite(points).all(dim=1)
+    capped = d2.to(torch.float64).sqrt().clamp(max=float(h))
+    zero = torch.zeros((), dtype=torch.float64, device=points.device)
+    return [finite.sum().to(torch.float64), torch.where(finite, capped, zero).sum(),
+            (finite & (d2 <= float(tau2))).sum().to(torch.float64)]
+
+
 def cloud_metrics(pred: torch.Tensor, truth: torch.Tensor, threshold: float, max_dist: Optional[float] = None
                   ) -> Dict[str, float]:
     """Accuracy / completeness (DTU) and precision / recall / F-score at ``threshold`` (Tanks and Temples) of the
@@ -256,17 +266,45 @@ def cloud_metrics(pred: torch.Tensor, truth: torch.Tensor, threshold: float, max
         d_pt = _host_nearest_dist2(pred, truth, h, inv, r2)
         d_tp = _host_nearest_dist2(truth, pred, h, inv, r2)
 
-    def sums(points, d2):
-        finite = torch.isfinite(points).all(dim=1)
-        capped = d2.to(torch.float64).sqrt().clamp(max=float(h))
-        zero = torch.zeros((), dtype=torch.float64, device=points.device)
-        return [finite.sum().to(torch.float64), torch.where(finite, capped, zero).sum(),
-                (finite & (d2 <= float(tau2))).sum().to(torch.float64)]
-
-    n_p, s_p, k_p, n_t, s_t, k_t = torch.stack(sums(pred, d_pt) + sums(truth, d_tp)).tolist()    # the one host read
+    n_p, s_p, k_p, n_t, s_t, k_t = torch.stack(_capped_sums(pred, d_pt, h, tau2) +
+                                               _capped_sums(truth, d_tp, h, tau2)).tolist()    # the one host read
     if n_p == 0 or n_t == 0:
         raise ValueError(f"a cloud has no finite point ({int(n_p)} in pred, {int(n_t)} in truth)")
     precision, recall = k_p / n_p, k_t / n_t
     fscore = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
     return {"accuracy": s_p / n_p, "completeness": s_t / n_t, "precision": precision, "recall": recall,
             "fscore": fscore, "n_pred": int(n_p), "n_truth": int(n_t)}
+
+
+def mesh_metrics(vertices: torch.Tensor, faces: torch.Tensor, truth: torch.Tensor, threshold: float,
+                 max_dist: Optional[float] = None, *, samples: int, seed: int = 0) -> Dict[str, float]:
+    """``cloud_metrics`` for a reconstruction that is a triangle mesh, ``vertices`` (M,3) fp32 and ``faces`` (F,3) int64,
+    against the cloud ``truth`` (T,3) fp32; device tensors only.
+
+    ``accuracy`` and ``precision`` are those of ``mesh.mesh_sample(vertices, faces, samples, seed=seed)``, an
+    area-uniform cloud of the surface, against ``truth`` through ``fusion.cloud_nearest``: the vertex set would not do,
+    it is not area-uniform and one large triangle is a surface that no vertex represents.  ``completeness`` and
+    ``recall`` are those of ``truth`` against the surface itself through ``mesh.mesh_nearest``, the exact point-to-mesh
+    distance.  The caps, the fp32 rounding of the threshold, the fp64 sums and the one host read at the end are
+    ``cloud_metrics``'s; the keys are its keys (``n_pred`` counts the finite samples) and ``n_samples``."""
+    from . import fusion, mesh
+    fusion.check_cloud("truth", truth)
+    tau, _, tau2 = fusion.cloud_radius_scalars(threshold, "threshold")
+    h, _, _ = fusion.cloud_radius_scalars(threshold if max_dist is None else max_dist, "max_dist")
+    if h < tau:
+        raise ValueError(f"max_dist ({float(h):g}) must not be below threshold ({float(tau):g})")
+    if not torch.is_tensor(vertices) or truth.device != vertices.device:
+        raise ValueError("vertices, faces and truth must be tensors on one device")
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"samples must be an integer >= 1 (the accuracy side is measured on them), got {samples!r}")
+    pred = mesh.mesh_sample(vertices, faces, samples, seed=seed)       # (validates the mesh, samples and seed)
+    d_pt = fusion.cloud_nearest(pred.points, truth, float(h)).dist2
+    d_tp = mesh.mesh_nearest(truth, vertices, faces, float(h)).dist2
+    n_p, s_p, k_p, n_t, s_t, k_t = torch.stack(_capped_sums(pred.points, d_pt, h, tau2) +
+                                               _capped_sums(truth, d_tp, h, tau2)).tolist()    # the one host read
+    if n_p == 0 or n_t == 0:
+        raise ValueError(f"a side has no finite point ({int(n_p)} samples, {int(n_t)} in truth)")
+    precision, recall = k_p / n_p, k_t / n_t
+    fscore = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {"accuracy": s_p / n_p, "completeness": s_t / n_t, "precision": precision, "recall": recall,
+            "fscore": fscore, "n_pred": int(n_p), "n_truth": int(n_t), "n_samples": int(pred.points.shape[0])}

@@ -78,7 +78,13 @@ atomics it issued.
 --global: also registers two samplings of an asymmetric height field from unrelated frames and prints, on a
 line of its own as "global", the points per cloud, ms for fusion.cloud_fpfh (each cloud), fusion.feature_nearest (one way
 and mutual) and fusion.cloud_ransac, ms of the match composed from torch ops (torch.cdist + min) and in how many rows its
-index differs, ms of the whole fusion.cloud_register_global, and the pose error before and after the refinement."""
+index differs, ms of the whole fusion.cloud_register_global, and the pose error before and after the refinement.
+--mesh-metrics: also scores the mesh of each scene's --tsdf volume against the fused cloud (metrics.mesh_metrics at a
+threshold of one voxel) and reports, as "mesh_metrics", M, F, the (cell, face) pairs and the large faces of the index, ms
+per mesh.mesh_sample of MESH_SAMPLES points, per mesh.mesh_nearest of the N fused points against the mesh and per
+mesh_metrics, ms of fusion.cloud_nearest of the same N points against the mesh's vertices (for scale), the same distance by
+brute force from torch ops (fp64, every face against the first TORCH_QUERIES points, in chunks of faces) with the rows whose
+dist2 bits or face differ, and the scores next to cloud_metrics of the vertices."""
 import argparse
 import json
 import os
@@ -94,8 +100,8 @@ from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_render, cloud_visibility, cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
-from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components  # noqa: E402
-from multi_view_stereonet_amd.metrics import cloud_metrics  # noqa: E402
+from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_sample  # noqa: E402
+from multi_view_stereonet_amd.metrics import cloud_metrics, mesh_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
 SCENES = [(64, 256, 512, 4), (16, 512, 1024, 8)]
@@ -1005,8 +1011,96 @@ def run_mesh(sc, steps, warmup):
         "torch_rounds": rounds, "torch_partition_equal": bool(torch.equal(tlabel, comp.first[comp.vertex_label]))}}
 
 
+MESH_SAMPLES = 1 << 20
+TORCH_FACE_CHUNK = 1 << 14
+
+
+def torch_mesh_nearest(query, vertices, faces, max_dist):
+    """mesh_nearest's distance from torch ops, every face against every query in chunks of faces: the normative fp64
+    steps, one torch op each, then the fp32 clamp and d2; the running minimum over
+    (d2, face).  Returns (dist2, face)."""
+    dot = lambda a, b: (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]      # noqa: E731
+    cross = lambda a, b: torch.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],                # noqa: E731
+                                      a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
+    h = torch.tensor(max_dist, dtype=torch.float32, device=query.device)
+    r2 = h * h
+    best = torch.full((query.shape[0],), float("inf"), device=query.device)
+    index = torch.full((query.shape[0],), -1, dtype=torch.int64, device=query.device)
+    qd = query.double()[:, None, :]
+    for s0 in range(0, faces.shape[0], TORCH_FACE_CHUNK):
+        p32 = vertices[faces[s0:s0 + TORCH_FACE_CHUNK]][None]                # (1, f, 3, 3)
+        P = p32.double()
+        a = P[..., 0, :]
+        ab, ac, aq = P[..., 1, :] - a, P[..., 2, :] - a, qd - a
+        n = cross(ab, ac)
+        nn = dot(n, n)
+        wb, wc = dot(cross(aq, ac), n) / nn, dot(cross(ab, aq), n) / nn
+        wa = (1.0 - wb) - wc
+        inside = (nn > 0) & (wb >= 0) & (wc >= 0) & (wa >= 0)
+        x = (a + wb[..., None] * ab) + wc[..., None] * ac
+        bestd, xe = None, None
+        for k in range(3):
+            p0 = P[..., k, :]
+            e, d = P[..., (k + 1) % 3, :] - p0, qd - p0
+            ee = dot(e, e)
+            r = dot(d, e) / ee
+            t = torch.where(ee > 0, torch.where(r > 0, torch.where(r < 1, r, torch.ones_like(r)), torch.zeros_like(r)),
+                            torch.zeros_like(r))
+            xs = p0 + t[..., None] * e
+            d = qd - xs
+            dd = dot(d, d)
+            take = dd < bestd if bestd is not None else None
+            bestd = dd if take is None else torch.where(take, dd, bestd)
+            xe = xs if take is None else torch.where(take[..., None], xs, xe)
+        x = torch.where(inside[..., None], x, xe).float()
+        x = torch.maximum(torch.minimum(x, p32.amax(dim=-2)), p32.amin(dim=-2))
+        df = query[:, None, :] - x
+        d2 = (df[..., 0] * df[..., 0] + df[..., 1] * df[..., 1]) + df[..., 2] * df[..., 2]
+        d2 = torch.where(d2 <= r2, d2, torch.full_like(d2, float("inf")))
+        m, i = d2.min(dim=1)
+        closer = m < best
+        best, index = torch.where(closer, m, best), torch.where(closer, i + s0, index)
+    return best, index
+
+
+def run_mesh_metrics(sc, res, steps, warmup):
+    steps, warmup = min(steps, 5), min(warmup, 1)           # (the calls are long: milliseconds)
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, 4 * TSDF_VOXEL, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    mesh = vol.extract_mesh()
+    v, f, truth = mesh.vertices, mesh.faces, res.points
+    m, nf, n = int(v.shape[0]), int(f.shape[0]), int(truth.shape[0])
+    _, inv, _ = cloud_radius_scalars(TSDF_VOXEL)
+    head = torch.empty(3, dtype=torch.int64, device=v.device)
+    _native.check(_native.load().mvsn_mesh_nearest_count(_native.ptr(v), m, _native.ptr(f), nf, float(inv),
+                                                         _native.ptr(head), _native.stream()), "mvsn_mesh_nearest_count")
+    pairs, large, _ = head.tolist()
+    _, stimes = timed(lambda: mesh_sample(v, f, MESH_SAMPLES, normals=mesh.normals, colors=mesh.colors), steps, warmup)
+    near, ntimes = timed(lambda: mesh_nearest(truth, v, f, TSDF_VOXEL), steps, warmup)
+    scores, mtimes = timed(lambda: mesh_metrics(v, f, truth, TSDF_VOXEL, samples=MESH_SAMPLES), steps, warmup)
+    _, ctimes = timed(lambda: cloud_nearest(truth, v, TSDF_VOXEL), steps, warmup)
+    q = truth[:TORCH_QUERIES]
+    (td2, tface), ttimes = timed(lambda: torch_mesh_nearest(q, v, f, TSDF_VOXEL), 2, 1)
+    found = torch.isfinite(near.dist2)
+    return {"mesh_metrics": {
+        "M": m, "F": nf, "N": n, "pairs": pairs, "large_faces": large, "max_dist": TSDF_VOXEL, "samples": MESH_SAMPLES,
+        "workspace_bytes": int(_native.load().mvsn_mesh_nearest_workspace_bytes(pairs, large)),
+        "sample_ms_per_call_mean": float(np.mean(stimes)), "sample_ms_per_call_min": float(np.min(stimes)),
+        "nearest_ms_per_call_mean": float(np.mean(ntimes)), "nearest_ms_per_call_min": float(np.min(ntimes)),
+        "metrics_ms_per_call_mean": float(np.mean(mtimes)), "metrics_ms_per_call_min": float(np.min(mtimes)),
+        "cloud_nearest_against_vertices_ms_mean": float(np.mean(ctimes)),
+        "found_fraction": float(found.float().mean()), "within_mean_where_found": float(near.within[found].float().mean()),
+        "torch_queries": int(q.shape[0]), "torch_ms_per_call_mean": float(np.mean(ttimes)),
+        "torch_extrapolated_ms_all_queries": float(np.mean(ttimes)) * n / max(int(q.shape[0]), 1),
+        "torch_rows_whose_dist2_bits_differ": int((td2.view(torch.int32) != near.dist2[:TORCH_QUERIES].view(torch.int32)).sum()),
+        "torch_rows_whose_face_differs": int((tface != near.face[:TORCH_QUERIES]).sum()),
+        "scores": scores, "vertices_as_a_cloud": cloud_metrics(v, truth, TSDF_VOXEL)}}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -1033,7 +1127,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     searched = run_knn(res, steps, warmup) if knn else {}
     split = run_clusters(res, float(sc["K"][0, 0, 0]), steps, warmup) if clusters else {}
     drawn = run_render(sc, res, steps, warmup) if render else {}
-    return {**drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    mesh_scored = run_mesh_metrics(sc, res, steps, warmup) if mesh_metrics_too else {}
+    return {**mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -1074,12 +1169,15 @@ def main():
     ap.add_argument("--render", action="store_true",
                     help="also render the fused cloud back into the input views (cloud_render at radius 0 and 1), test its "
                          "points for occlusion (cloud_visibility, with and without maps), and the torch form of the render")
+    ap.add_argument("--mesh-metrics", action="store_true",
+                    help="also score the volume's mesh against the fused cloud (mesh_metrics) and time mesh_sample and "
+                         "mesh_nearest, cloud_nearest against the vertices, and the torch brute force of the distance")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
-                             a.render)), flush=True)
+                             a.render, a.mesh_metrics)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
