@@ -1,7 +1,14 @@
-// What the kernels that query a cloud's hash grid share (mvsn_cloud.hip builds the grid and answers the nearest-neighbour
-// query, mvsn_cloud_register.hip matches a moved cloud against it, mvsn_cloud_normals.hip takes every point's
-// neighbourhood from it): the workspace layout of an index, the cells a query visits, and the walk of one query over them.  DESIGN.md section 14 has the semantics and the proof that the cells
-// visited are enough.
+// What the kernels that query a cloud's hash grid share (DESIGN.md section 14 has the semantics and the proof that the
+// cells visited are enough; sections 20, 21, 22, 23, 24 and 26 all query through this file): the workspace layout of an
+// index, the view of a built one that a kernel takes (CloudIndex) with the check of the workspace it lies in, and the
+// query in three layers, each built on the one before:
+//   cloud_cells   the cells a query visits: finite test, reach, the range per axis, the probe for every cell's key and
+//                 the clamp of its record range; the caller's on_cell gets (cell, the range's lower corner, from, to)
+//   cloud_visit   cloud_cells over 16-byte point records: the fp32 differences and d2 <= r2; the caller's visit gets
+//                 every accepted record
+//   cloud_walk    cloud_visit with the visitor that counts and keeps the minimum of (d2 bits, row)
+// mvsn_cloud.hip builds the grid and answers the nearest-neighbour query; the mesh's point-to-face query
+// (mvsn_mesh_nearest.hip) runs cloud_cells over its own 4-byte pair records.
 #pragma once
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
@@ -50,101 +57,113 @@ __device__ __forceinline__ void cloud_cell_range(float t, float reach, int *lo, 
   *hi = (int)fmaxf(fminf(floorf(u), (float)(VX_CELL_BIAS - 1)), -(float)VX_CELL_BIAS - 1.0f);
 }
 
-// One query (qx, qy, qz) against a built index: for every cell of its range a bounded probe for the cell's key (stop at
-// the key or at the first empty slot), then a walk over the cell's records with 16-byte loads: d2 in fp32, the count of
-// d2 <= r2 added to `count`, and `best` lowered to the minimum of (d2 bits, row) as one 64-bit key.  The caller starts
-// them at 0 and ~0 (~0 afterwards: nothing within).
-__device__ __forceinline__ void cloud_walk(float qx, float qy, float qz, float inv, float r2,
-                                           const unsigned long long *__restrict__ keys, const int *__restrict__ pop,
-                                           const int *__restrict__ start, const floatx4 *__restrict__ records,
-                                           size_t slots, long n, unsigned long long &best, int &count) {
-#pragma clang fp contract(off)
-  const float tx = qx * inv, ty = qy * inv, tz = qz * inv;
-  // a query whose t overflows is farther than max_dist from every point that has a cell: nothing to visit
-  if (isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(tx) && isfinite(ty) && isfinite(tz)) {
-    const float reach = r2 < 0x1p-100f ? 2.0f : 1.0f;
-    int lo[3], hi[3];
-    cloud_cell_range(tx, reach, lo + 0, hi + 0);
-    cloud_cell_range(ty, reach, lo + 1, hi + 1);
-    cloud_cell_range(tz, reach, lo + 2, hi + 2);
-    const size_t mask = slots - 1;
-    int c[3];
-    for (c[0] = lo[0]; c[0] <= hi[0]; ++c[0])
-      for (c[1] = lo[1]; c[1] <= hi[1]; ++c[1])
-        for (c[2] = lo[2]; c[2] <= hi[2]; ++c[2]) {
-          const unsigned long long key = voxel_key(c);
-          size_t h = (size_t)voxel_hash(key) & mask;
-          long from = 0, to = 0;
-          for (size_t probe = 0; probe < slots; ++probe) {  // bounded: every slot at most once
-            const unsigned long long seen = keys[h];
-            if (seen == key) {
-              from = (long)start[h];
-              to = from + (long)pop[h];
-              break;
-            }
-            if (seen == VX_EMPTY) break;
-            h = (h + 1) & mask;
-          }
-          from = max(from, 0L), to = min(to, n);           // (a built table's ranges are inside; any other stays inside too)
-          for (long j = from; j < to; ++j) {
-            const floatx4 r = records[j];
-            const float dx = qx - r[0], dy = qy - r[1], dz = qz - r[2];
-            const float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 <= r2) {
-              ++count;
-              const unsigned long long k =
-                  ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(r[3]);
-              best = k < best ? k : best;
-            }
-          }
-        }
-  }
+// What a query needs of a built index.  The records are a separate, typed kernel argument: floatx4 points for a cloud,
+// int face rows for the mesh's (cell, face) pairs.
+struct CloudIndex {
+  const unsigned long long *keys;
+  const int *pop, *start;
+  size_t slots;
+};
+
+// The view of the index in `workspace`, and its records.  Layout is CloudLayout, or any layout with the same sections
+// (the mesh's NearestLayout).
+template <class Layout, class Record>
+inline CloudIndex cloud_index(const void *workspace, const Layout &l, const Record **records) {
+  const char *ws = (const char *)workspace;
+  *records = (const Record *)(ws + l.records);
+  return {(const unsigned long long *)(ws + l.keys), (const int *)(ws + l.pop), (const int *)(ws + l.start), l.slots};
 }
 
-// The visitor form of cloud_walk: the same range, probe, clamp and record loop, and the same fp32 differences and
-// d2 <= r2; every accepted record is handed to visit(dx, dy, dz, d2, record) in walk order (which depends on the order in
-// which the scatter's atomics arrived: a visitor must not let its result depend on it).  cloud_walk's own text stays as
-// it is, so that its two users compile to what they compiled to before this form existed.
-template <class Visit>
-__device__ __forceinline__ void cloud_visit(float qx, float qy, float qz, float inv, float r2,
-                                            const unsigned long long *__restrict__ keys, const int *__restrict__ pop,
-                                            const int *__restrict__ start, const floatx4 *__restrict__ records,
-                                            size_t slots, long n, Visit &&visit) {
+// The two requirements on the workspace of an index of n points, `what` its noun in the entry's message ("workspace",
+// "index workspace"); 0 and the layout in `l`, or the error code.
+inline int cloud_index_check(const char *who, const char *what, const void *workspace, size_t workspace_bytes, long n,
+                             CloudLayout *l) {
+  *l = cloud_layout(n);
+  MVSN_REQUIRE(workspace && workspace_bytes >= l->bytes, MVSN_E_WORKSPACE, "%s: %s of %zu bytes, %zu needed", who, what,
+               workspace_bytes, l->bytes);
+  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
+  return 0;
+}
+
+// defined in mvsn_cloud.hip, launched by the mesh's pair index too: the table init, the per-workgroup population sums
+// and the starts of an index
+__global__ __launch_bounds__(CL_THREADS) void cloud_init_kernel(unsigned long long *__restrict__ keys,
+                                                                int *__restrict__ pop, int *__restrict__ cursor,
+                                                                unsigned long long *__restrict__ status);
+__global__ __launch_bounds__(CL_THREADS) void cloud_count_kernel(const int *__restrict__ pop,
+                                                                 int *__restrict__ block_counts);
+__global__ __launch_bounds__(CL_THREADS) void cloud_start_kernel(const int *__restrict__ pop,
+                                                                 const int64_t *__restrict__ offsets,
+                                                                 int *__restrict__ start);
+
+// The cells of one query (qx, qy, qz) against a built index: for every cell c of its range a bounded probe for the
+// cell's key (stop at the key or at the first empty slot), then on_cell(c, lo, from, to) with lo the range's lower
+// corner and [from, to) the cell's records, clamped to [0, limit); a cell without a key gets the empty range.  False
+// when the query has no cells at all: it is not finite, or its t overflows.
+template <class OnCell>
+__device__ __forceinline__ bool cloud_cells(float qx, float qy, float qz, float inv, float r2, const CloudIndex &ix,
+                                            long limit, OnCell &&on_cell) {
 #pragma clang fp contract(off)
   const float tx = qx * inv, ty = qy * inv, tz = qz * inv;
-  if (isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(tx) && isfinite(ty) && isfinite(tz)) {
-    const float reach = r2 < 0x1p-100f ? 2.0f : 1.0f;
-    int lo[3], hi[3];
-    cloud_cell_range(tx, reach, lo + 0, hi + 0);
-    cloud_cell_range(ty, reach, lo + 1, hi + 1);
-    cloud_cell_range(tz, reach, lo + 2, hi + 2);
-    const size_t mask = slots - 1;
-    int c[3];
-    for (c[0] = lo[0]; c[0] <= hi[0]; ++c[0])
-      for (c[1] = lo[1]; c[1] <= hi[1]; ++c[1])
-        for (c[2] = lo[2]; c[2] <= hi[2]; ++c[2]) {
-          const unsigned long long key = voxel_key(c);
-          size_t h = (size_t)voxel_hash(key) & mask;
-          long from = 0, to = 0;
-          for (size_t probe = 0; probe < slots; ++probe) {  // bounded: every slot at most once
-            const unsigned long long seen = keys[h];
-            if (seen == key) {
-              from = (long)start[h];
-              to = from + (long)pop[h];
-              break;
-            }
-            if (seen == VX_EMPTY) break;
-            h = (h + 1) & mask;
+  // a query whose t overflows is farther than max_dist from everything that has a cell: nothing to visit
+  if (!(isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(tx) && isfinite(ty) && isfinite(tz))) return false;
+  const float reach = r2 < 0x1p-100f ? 2.0f : 1.0f;
+  int lo[3], hi[3];
+  cloud_cell_range(tx, reach, lo + 0, hi + 0);
+  cloud_cell_range(ty, reach, lo + 1, hi + 1);
+  cloud_cell_range(tz, reach, lo + 2, hi + 2);
+  const size_t mask = ix.slots - 1;
+  int c[3];
+  for (c[0] = lo[0]; c[0] <= hi[0]; ++c[0])
+    for (c[1] = lo[1]; c[1] <= hi[1]; ++c[1])
+      for (c[2] = lo[2]; c[2] <= hi[2]; ++c[2]) {
+        const unsigned long long key = voxel_key(c);
+        size_t h = (size_t)voxel_hash(key) & mask;
+        long from = 0, to = 0;
+        for (size_t probe = 0; probe < ix.slots; ++probe) {  // bounded: every slot at most once
+          const unsigned long long seen = ix.keys[h];
+          if (seen == key) {
+            from = (long)ix.start[h];
+            to = from + (long)ix.pop[h];
+            break;
           }
-          from = max(from, 0L), to = min(to, n);
-          for (long j = from; j < to; ++j) {
-            const floatx4 r = records[j];
-            const float dx = qx - r[0], dy = qy - r[1], dz = qz - r[2];
-            const float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 <= r2) visit(dx, dy, dz, d2, r);
-          }
+          if (seen == VX_EMPTY) break;
+          h = (h + 1) & mask;
         }
-  }
+        from = max(from, 0L), to = min(to, limit);        // (a built table's ranges are inside; any other stays inside too)
+        on_cell(c, lo, from, to);
+      }
+  return true;
+}
+
+// cloud_cells over the n point records of a cloud's index, with 16-byte loads: d2 in fp32, and every record with
+// d2 <= r2 handed to visit(dx, dy, dz, d2, record) in walk order (which depends on the order in which the scatter's
+// atomics arrived: a visitor must not let its result depend on it).
+template <class Visit>
+__device__ __forceinline__ void cloud_visit(float qx, float qy, float qz, float inv, float r2, const CloudIndex &ix,
+                                            const floatx4 *__restrict__ records, long n, Visit &&visit) {
+#pragma clang fp contract(off)
+  cloud_cells(qx, qy, qz, inv, r2, ix, n, [&](const int *, const int *, long from, long to) {
+    for (long j = from; j < to; ++j) {
+      const floatx4 r = records[j];
+      const float dx = qx - r[0], dy = qy - r[1], dz = qz - r[2];
+      const float d2 = (dx * dx + dy * dy) + dz * dz;
+      if (d2 <= r2) visit(dx, dy, dz, d2, r);
+    }
+  });
+}
+
+// cloud_visit with the count of the accepted records added to `count` and `best` lowered to the minimum of
+// (d2 bits, row) as one 64-bit key.  The caller starts them at 0 and ~0 (~0 afterwards: nothing within).
+__device__ __forceinline__ void cloud_walk(float qx, float qy, float qz, float inv, float r2, const CloudIndex &ix,
+                                           const floatx4 *__restrict__ records, long n, unsigned long long &best,
+                                           int &count) {
+  cloud_visit(qx, qy, qz, inv, r2, ix, records, n, [&](float, float, float, float d2, const floatx4 &r) {
+    ++count;
+    const unsigned long long k =
+        ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(r[3]);
+    best = k < best ? k : best;
+  });
 }
 
 }  // namespace mvsn

@@ -126,9 +126,10 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_nearest_kernel(const float *
   const long i = (long)blockIdx.x * CL_THREADS + threadIdx.x;
   if (i >= nq) return;
   const float qx = query[(size_t)i * 3], qy = query[(size_t)i * 3 + 1], qz = query[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
   int count = 0;
   unsigned long long best = ~0ull;
-  cloud_walk(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n, best, count);
+  cloud_walk(qx, qy, qz, inv, r2, ix, records, n, best, count);
   const bool any = best != ~0ull;
   dist2[i] = any ? __uint_as_float((unsigned)(best >> 32)) : __builtin_inff();
   index[i] = any ? (int64_t)(unsigned)(best & 0xffffffffull) : (int64_t)-1;
@@ -151,11 +152,8 @@ extern "C" int mvsn_cloud_index_build(const float *target, long n, float cell, f
   MVSN_REQUIRE(cell > 0.0f && cell <= 3.0e38f && inv_cell > 0.0f && inv_cell <= 3.0e38f, MVSN_E_BADARG,
                "mvsn_cloud_index_build: cell size %g (inverse %g) is not a positive finite number", (double)cell,
                (double)inv_cell);
-  const CloudLayout l = cloud_layout(n);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l.bytes, MVSN_E_WORKSPACE,
-               "mvsn_cloud_index_build: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG,
-               "mvsn_cloud_index_build: workspace not 16-byte aligned");
+  CloudLayout l;
+  if (int e = cloud_index_check("mvsn_cloud_index_build", "workspace", workspace, workspace_bytes, n, &l)) return e;
   char *ws = (char *)workspace;
   unsigned long long *keys = (unsigned long long *)(ws + l.keys), *st_word = (unsigned long long *)status;
   int *pop = (int *)(ws + l.pop), *start = (int *)(ws + l.start), *cursor = (int *)(ws + l.cursor);
@@ -193,14 +191,12 @@ extern "C" int mvsn_cloud_nearest(const float *query, long nq, float inv_cell, f
   MVSN_REQUIRE(inv_cell > 0.0f && inv_cell <= 3.0e38f && r2 > 0.0f && r2 <= 3.0e38f, MVSN_E_BADARG,
                "mvsn_cloud_nearest: inverse cell size %g or squared radius %g is not a positive finite number",
                (double)inv_cell, (double)r2);
-  const CloudLayout l = cloud_layout(n_target);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l.bytes, MVSN_E_WORKSPACE,
-               "mvsn_cloud_nearest: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "mvsn_cloud_nearest: workspace not 16-byte aligned");
-  const char *ws = (const char *)workspace;
+  CloudLayout l;
+  if (int e = cloud_index_check("mvsn_cloud_nearest", "workspace", workspace, workspace_bytes, n_target, &l)) return e;
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(workspace, l, &records);
   hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)((nq + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0,
-                     (hipStream_t)stream, query, nq, inv_cell, r2, (const unsigned long long *)(ws + l.keys),
-                     (const int *)(ws + l.pop), (const int *)(ws + l.start), (const floatx4 *)(ws + l.records), l.slots,
-                     n_target, dist2, index, within);
+                     (hipStream_t)stream, query, nq, inv_cell, r2, ix.keys, ix.pop, ix.start, records, ix.slots, n_target,
+                     dist2, index, within);
   return check_launch("mvsn_cloud_nearest: nearest");
 }

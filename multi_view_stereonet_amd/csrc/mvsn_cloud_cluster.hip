@@ -54,15 +54,6 @@ inline ClusterLayout cluster_layout(long n) {
   return l;
 }
 
-// what the kernels need of a built index (handed to them as plain arguments, so that every buffer of a launch is visible
-// as one)
-struct ClusterIndex {
-  const unsigned long long *keys;
-  const int *pop, *start;
-  const floatx4 *records;
-  size_t slots;
-};
-
 __global__ __launch_bounds__(CC_THREADS) void cluster_core_kernel(
     const float *__restrict__ points, long n, float inv, float r2, long min_points,
     const unsigned long long *__restrict__ keys, const int *__restrict__ pop, const int *__restrict__ start,
@@ -72,9 +63,10 @@ __global__ __launch_bounds__(CC_THREADS) void cluster_core_kernel(
   if (i == 0) head[0] = 0, head[1] = 0;
   if (i >= n) return;
   const float qx = points[(size_t)i * 3], qy = points[(size_t)i * 3 + 1], qz = points[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
   int count = 0;
   unsigned long long best = ~0ull;
-  cloud_walk(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n, best, count);
+  cloud_walk(qx, qy, qz, inv, r2, ix, records, n, best, count);
   const bool finite = isfinite(qx) && isfinite(qy) && isfinite(qz);
   within[i] = count;
   core[i] = finite && (long)count >= min_points ? 1 : 0;
@@ -89,9 +81,10 @@ __global__ __launch_bounds__(CC_THREADS) void cluster_hook_kernel(
   const long i = (long)blockIdx.x * CC_THREADS + threadIdx.x;
   if (i >= n || !core[i]) return;                                   // only core rows are nodes
   const float qx = points[(size_t)i * 3], qy = points[(size_t)i * 3 + 1], qz = points[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
   int last = -1;                                                    // the root this thread last reached from i
   bool ok = true;
-  cloud_visit(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n,
+  cloud_visit(qx, qy, qz, inv, r2, ix, records, n,
               [&](float, float, float, float, const floatx4 &r) {
                 const long j = (long)__float_as_uint(r[3]);
                 if (!ok || j >= i || !core[j]) return;              // the edge belongs to its higher row; j < i <= n - 1
@@ -178,9 +171,10 @@ __global__ __launch_bounds__(CC_THREADS) void cluster_label_kernel(
     long from = is_core ? i : -1;                                   // the core row whose cluster this row joins
     if (!is_core) {
       const float qx = points[(size_t)i * 3], qy = points[(size_t)i * 3 + 1], qz = points[(size_t)i * 3 + 2];
+      const CloudIndex ix = {keys, pop, start, slots};
       unsigned long long best = ~0ull;
       // (a row that is not finite visits nothing and stays noise)
-      cloud_visit(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n,
+      cloud_visit(qx, qy, qz, inv, r2, ix, records, n,
                   [&](float, float, float, float d2, const floatx4 &r) {
                     const unsigned row = __float_as_uint(r[3]);
                     if ((long)row >= n || !core[row]) return;
@@ -195,18 +189,6 @@ __global__ __launch_bounds__(CC_THREADS) void cluster_label_kernel(
   }
   mesh_count(count, id);
   mesh_count(core_count, is_core ? id : -1);
-}
-
-inline ClusterIndex cluster_index(const void *index_workspace, long n) {
-  const CloudLayout l = cloud_layout(n);
-  const char *ws = (const char *)index_workspace;
-  ClusterIndex ix;
-  ix.keys = (const unsigned long long *)(ws + l.keys);
-  ix.pop = (const int *)(ws + l.pop);
-  ix.start = (const int *)(ws + l.start);
-  ix.records = (const floatx4 *)(ws + l.records);
-  ix.slots = l.slots;
-  return ix;
 }
 
 }  // namespace mvsn
@@ -255,14 +237,15 @@ extern "C" int mvsn_cloud_cluster_label(const float *points, long n, float inv_c
   unsigned long long *head = (unsigned long long *)(ws + l.head);
   int *parent = (int *)(ws + l.parent), *counts = (int *)(ws + l.counts);
   int64_t *offsets = (int64_t *)(ws + l.offsets);
-  const ClusterIndex ix = cluster_index(index_workspace, n);
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(index_workspace, cloud_layout(n), &records);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)l.blocks), block(CC_THREADS);
   hipLaunchKernelGGL(cluster_core_kernel, grid, block, 0, st, points, n, inv_cell, r2, min_points, ix.keys, ix.pop,
-                     ix.start, ix.records, ix.slots, within, core, parent, head);
+                     ix.start, records, ix.slots, within, core, parent, head);
   if (int e = check_launch("mvsn_cloud_cluster_label: core")) return e;
   hipLaunchKernelGGL(cluster_hook_kernel, grid, block, 0, st, points, n, inv_cell, r2, ix.keys, ix.pop, ix.start,
-                     ix.records, ix.slots, (const uint8_t *)core, parent, head);
+                     records, ix.slots, (const uint8_t *)core, parent, head);
   if (int e = check_launch("mvsn_cloud_cluster_label: hook")) return e;
   hipLaunchKernelGGL(cluster_flatten_kernel, grid, block, 0, st, parent, (const uint8_t *)core, n, counts, head);
   if (int e = check_launch("mvsn_cloud_cluster_label: flatten")) return e;
@@ -290,7 +273,8 @@ extern "C" int mvsn_cloud_cluster_emit(const float *points, long n, float inv_ce
   const int *parent = (const int *)(ws + l.parent);
   int *id_of = (int *)(ws + l.map);
   const int64_t *offsets = (const int64_t *)(ws + l.offsets);
-  const ClusterIndex ix = cluster_index(index_workspace, n);
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(index_workspace, cloud_layout(n), &records);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)l.blocks), block(CC_THREADS);
   if (n_clusters > 0) {
@@ -300,6 +284,6 @@ extern "C" int mvsn_cloud_cluster_emit(const float *points, long n, float inv_ce
   }
   // (with no cluster there is no core row: nothing reads id_of, and every label is -1)
   hipLaunchKernelGGL(cluster_label_kernel, grid, block, 0, st, points, n, inv_cell, r2, ix.keys, ix.pop, ix.start,
-                     ix.records, ix.slots, core, parent, (const int *)id_of, n_clusters, label, count, core_count);
+                     records, ix.slots, core, parent, (const int *)id_of, n_clusters, label, count, core_count);
   return check_launch("mvsn_cloud_cluster_emit: labels");
 }

@@ -96,9 +96,10 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_spfh_kernel(const float *__r
   for (int b = 0; b < FP_DIM; ++b) hist[b][tid] = 0;
   const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
   const float nx = normals[(size_t)i * 3], ny = normals[(size_t)i * 3 + 1], nz = normals[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
   int count = 0;
   if (fpfh_normal_ok(nx, ny, nz))
-    cloud_visit(px, py, pz, inv, r2, keys, pop, start, records, slots, n,
+    cloud_visit(px, py, pz, inv, r2, ix, records, n,
                 [&](float dx, float dy, float dz, float d2, const floatx4 &r) {
                   const unsigned row = __float_as_uint(r[3]);
                   if (row == (unsigned)i || d2 == 0.0f || (long)row >= n) return;
@@ -129,6 +130,7 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_fpfh_kernel(const float *__r
   const float px = points[(size_t)i * 3], py = points[(size_t)i * 3 + 1], pz = points[(size_t)i * 3 + 2];
   const float nx = normals[(size_t)i * 3], ny = normals[(size_t)i * 3 + 1], nz = normals[(size_t)i * 3 + 2];
   const int ki = pairs[i];
+  const CloudIndex ix = {keys, pop, start, slots};
   float *out = features + (size_t)i * FP_DIM;
 
   long long acc[FP_DIM];
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_fpfh_kernel(const float *__r
   const double r2d = (double)r2;
   const double floor_d2 = r2d * 0x1p-20;
   if (ki > 0 && (long)ki >= min_neighbours && fpfh_normal_ok(nx, ny, nz))
-    cloud_visit(px, py, pz, inv, r2, keys, pop, start, records, slots, n,
+    cloud_visit(px, py, pz, inv, r2, ix, records, n,
                 [&](float, float, float, float d2, const floatx4 &r) {
                   const unsigned row = __float_as_uint(r[3]);
                   if (row == (unsigned)i || d2 == 0.0f || (long)row >= n) return;
@@ -195,20 +197,16 @@ extern "C" int mvsn_cloud_fpfh(const float *points, const float *normals, long n
                (double)cell, (double)inv_cell, (double)r2);
   MVSN_REQUIRE(min_neighbours >= 1, MVSN_E_BADARG, "%s: min_neighbours = %ld (at least 1)", who, min_neighbours);
   MVSN_REQUIRE(n <= 0x7fffffffL, MVSN_E_TOOLARGE, "%s: %ld points (at most 2^31 - 1)", who, n);
-  const CloudLayout l = cloud_layout(n);
-  MVSN_REQUIRE(index_workspace && index_workspace_bytes >= l.bytes, MVSN_E_WORKSPACE,
-               "%s: index workspace of %zu bytes, %zu needed", who, index_workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)index_workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  const char *ws = (const char *)index_workspace;
+  CloudLayout l;
+  if (int e = cloud_index_check(who, "index workspace", index_workspace, index_workspace_bytes, n, &l)) return e;
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(index_workspace, l, &records);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((n + CL_THREADS - 1) / CL_THREADS)), block(CL_THREADS);
-  const unsigned long long *keys = (const unsigned long long *)(ws + l.keys);
-  const int *pop = (const int *)(ws + l.pop), *start = (const int *)(ws + l.start);
-  const floatx4 *records = (const floatx4 *)(ws + l.records);
-  hipLaunchKernelGGL(cloud_spfh_kernel, grid, block, 0, st, points, normals, n, inv_cell, r2, keys, pop, start, records,
-                     l.slots, spfh, pairs);
+  hipLaunchKernelGGL(cloud_spfh_kernel, grid, block, 0, st, points, normals, n, inv_cell, r2, ix.keys, ix.pop, ix.start,
+                     records, ix.slots, spfh, pairs);
   if (int e = check_launch("mvsn_cloud_fpfh: spfh")) return e;
-  hipLaunchKernelGGL(cloud_fpfh_kernel, grid, block, 0, st, points, normals, n, inv_cell, r2, min_neighbours, keys, pop,
-                     start, records, l.slots, (const int *)spfh, (const int *)pairs, features);
+  hipLaunchKernelGGL(cloud_fpfh_kernel, grid, block, 0, st, points, normals, n, inv_cell, r2, min_neighbours, ix.keys,
+                     ix.pop, ix.start, records, ix.slots, (const int *)spfh, (const int *)pairs, features);
   return check_launch("mvsn_cloud_fpfh: fpfh");
 }

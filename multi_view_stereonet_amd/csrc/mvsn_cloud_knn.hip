@@ -49,6 +49,7 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_knn_kernel(
   const long i = (long)blockIdx.x * CL_THREADS + threadIdx.x;
   if (i >= nq) return;
   const float qx = query[(size_t)i * 3], qy = query[(size_t)i * 3 + 1], qz = query[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
   const int pad = CAP - k;                                // sentinels in front of the list
   const unsigned self = exclude_self ? (unsigned)i : 0xffffffffu;   // (rows are below 2^31: ~0 is nobody's)
 
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_knn_kernel(
 #pragma unroll
   for (int j = 0; j < CAP; ++j) key[j] = j < pad ? 0ull : ~0ull;
   int count = 0;
-  cloud_visit(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n,
+  cloud_visit(qx, qy, qz, inv, r2, ix, records, n,
               [&](float, float, float, float d2, const floatx4 &r) {
                 const unsigned row = __float_as_uint(r[3]);
                 if (row == self) return;
@@ -175,13 +176,12 @@ inline MeanLayout mean_layout(long n) {
 }
 
 template <int CAP>
-static void launch_knn(const float *query, long nq, int k, int exclude_self, float inv, float r2, const char *ws,
-                       const CloudLayout &l, long n_target, float *dist2, int64_t *index, int *within, double *mean,
+static void launch_knn(const float *query, long nq, int k, int exclude_self, float inv, float r2, const CloudIndex &ix,
+                       const floatx4 *records, long n_target, float *dist2, int64_t *index, int *within, double *mean,
                        hipStream_t st) {
   hipLaunchKernelGGL(cloud_knn_kernel<CAP>, dim3((unsigned)((nq + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, st,
-                     query, nq, k, exclude_self, inv, r2, (const unsigned long long *)(ws + l.keys),
-                     (const int *)(ws + l.pop), (const int *)(ws + l.start), (const floatx4 *)(ws + l.records), l.slots,
-                     n_target, dist2, index, within, mean);
+                     query, nq, k, exclude_self, inv, r2, ix.keys, ix.pop, ix.start, records, ix.slots, n_target, dist2, index,
+                     within, mean);
 }
 
 }  // namespace mvsn
@@ -199,21 +199,20 @@ extern "C" int mvsn_cloud_knn(const float *query, long nq, int k, int exclude_se
                (double)cell, (double)inv_cell, (double)r2);
   MVSN_REQUIRE(nq <= 0x7fffffffL && n_target <= 0x7fffffffL, MVSN_E_TOOLARGE,
                "%s: %ld queries against %ld points (at most 2^31 - 1 each)", who, nq, n_target);
-  const CloudLayout l = cloud_layout(n_target);
-  MVSN_REQUIRE(index_workspace && index_workspace_bytes >= l.bytes, MVSN_E_WORKSPACE,
-               "%s: index workspace of %zu bytes, %zu needed", who, index_workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)index_workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  const char *ws = (const char *)index_workspace;
+  CloudLayout l;
+  if (int e = cloud_index_check(who, "index workspace", index_workspace, index_workspace_bytes, n_target, &l)) return e;
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(index_workspace, l, &records);
   const hipStream_t st = (hipStream_t)stream;
   const int self = exclude_self ? 1 : 0;
   if (k <= 8)
-    launch_knn<8>(query, nq, k, self, inv_cell, r2, ws, l, n_target, dist2, index, within, mean, st);
+    launch_knn<8>(query, nq, k, self, inv_cell, r2, ix, records, n_target, dist2, index, within, mean, st);
   else if (k <= 16)
-    launch_knn<16>(query, nq, k, self, inv_cell, r2, ws, l, n_target, dist2, index, within, mean, st);
+    launch_knn<16>(query, nq, k, self, inv_cell, r2, ix, records, n_target, dist2, index, within, mean, st);
   else if (k <= 32)
-    launch_knn<32>(query, nq, k, self, inv_cell, r2, ws, l, n_target, dist2, index, within, mean, st);
+    launch_knn<32>(query, nq, k, self, inv_cell, r2, ix, records, n_target, dist2, index, within, mean, st);
   else
-    launch_knn<64>(query, nq, k, self, inv_cell, r2, ws, l, n_target, dist2, index, within, mean, st);
+    launch_knn<64>(query, nq, k, self, inv_cell, r2, ix, records, n_target, dist2, index, within, mean, st);
   return check_launch("mvsn_cloud_knn: knn");
 }
 

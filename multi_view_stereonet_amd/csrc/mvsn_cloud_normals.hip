@@ -71,12 +71,13 @@ __global__ __launch_bounds__(CL_THREADS) void cloud_normals_kernel(
   const long i = (long)blockIdx.x * CL_THREADS + threadIdx.x;
   if (i >= nq) return;
   const float qx = query[(size_t)i * 3], qy = query[(size_t)i * 3 + 1], qz = query[(size_t)i * 3 + 2];
+  const CloudIndex ix = {keys, pop, start, slots};
 
   // the sums are unsigned so that a neighbourhood past the limit wraps instead of overflowing; each product is formed
   // from two ints as a signed 64-bit number and is exact
   int within = 0;
   unsigned long long sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
-  cloud_visit(qx, qy, qz, inv, r2, keys, pop, start, records, slots, n,
+  cloud_visit(qx, qy, qz, inv, r2, ix, records, n,
               [&](float dx, float dy, float dz, float, const floatx4 &) {
                 const int ux = (int)rintf((dx * inv) * CN_QUANTUM);
                 const int uy = (int)rintf((dy * inv) * CN_QUANTUM);
@@ -160,14 +161,12 @@ extern "C" int mvsn_cloud_normals(const float *query, long nq, const float *view
   MVSN_REQUIRE(min_gap >= 0.0 && min_gap < 1.0, MVSN_E_BADARG, "%s: min_gap %g (inside [0, 1))", who, min_gap);
   MVSN_REQUIRE(nq <= 0x7fffffffL && n_target <= 0x7fffffffL, MVSN_E_TOOLARGE,
                "%s: %ld queries against %ld points (at most 2^31 - 1 each)", who, nq, n_target);
-  const CloudLayout l = cloud_layout(n_target);
-  MVSN_REQUIRE(index_workspace && index_workspace_bytes >= l.bytes, MVSN_E_WORKSPACE,
-               "%s: index workspace of %zu bytes, %zu needed", who, index_workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)index_workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  const char *ws = (const char *)index_workspace;
+  CloudLayout l;
+  if (int e = cloud_index_check(who, "index workspace", index_workspace, index_workspace_bytes, n_target, &l)) return e;
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(index_workspace, l, &records);
   hipLaunchKernelGGL(cloud_normals_kernel, dim3((unsigned)((nq + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0,
                      (hipStream_t)stream, query, nq, viewpoint, viewpoint_rows, cell, inv_cell, r2, min_neighbours, min_gap,
-                     (const unsigned long long *)(ws + l.keys), (const int *)(ws + l.pop), (const int *)(ws + l.start),
-                     (const floatx4 *)(ws + l.records), l.slots, n_target, normals, eigenvalues, count);
+                     ix.keys, ix.pop, ix.start, records, ix.slots, n_target, normals, eigenvalues, count);
   return check_launch("mvsn_cloud_normals: normals");
 }

@@ -78,6 +78,7 @@ __global__ __launch_bounds__(CR_THREADS) void cloud_register_accumulate_kernel(
   }
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const CloudIndex ix = {keys, pop, start, slots};
   float R[9], t[3], c[3];
 #pragma unroll
   for (int i = 0; i < 9; ++i) R[i] = spose[i];
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(CR_THREADS) void cloud_register_accumulate_kernel(
       if (takes) {
         unsigned long long best = ~0ull;
         int within = 0;
-        cloud_walk(p[0], p[1], p[2], inv, r2, keys, pop, start, records, slots, n_target, best, within);
+        cloud_walk(p[0], p[1], p[2], inv, r2, ix, records, n_target, best, within);
         const long j = (long)(unsigned)(best & 0xffffffffull);
         takes = best != ~0ull && j < n_target;                      // (a built index holds rows below n_target only)
         if (takes) {
@@ -306,25 +307,24 @@ inline int register_check(const char *who, const RegisterArgs &a) {
 }
 
 template <bool PLANE, bool MATCHES>
-inline void register_launch(const RegisterArgs &a, const RegisterPlan &p, const CloudLayout &l, const double *pose,
-                            double *sums, int64_t *index, float *residual, hipStream_t st) {
-  const char *ws = (const char *)a.index_ws;
+inline void register_launch(const RegisterArgs &a, const RegisterPlan &p, const double *pose, double *sums,
+                            int64_t *index, float *residual, hipStream_t st) {
+  const floatx4 *records;
+  const CloudIndex ix = cloud_index(a.index_ws, cloud_layout(a.n_target), &records);
   hipLaunchKernelGGL((cloud_register_accumulate_kernel<PLANE, MATCHES>), dim3((unsigned)p.groups), dim3(CR_THREADS), 0, st,
-                     a.source, a.n, a.weights, a.target, a.normals, a.n_target, a.inv, a.r2,
-                     (const unsigned long long *)(ws + l.keys), (const int *)(ws + l.pop), (const int *)(ws + l.start),
-                     (const floatx4 *)(ws + l.records), l.slots, a.T, pose, a.centre, p.blocks, sums, index, residual);
+                     a.source, a.n, a.weights, a.target, a.normals, a.n_target, a.inv, a.r2, ix.keys, ix.pop, ix.start,
+                     records, ix.slots, a.T, pose, a.centre, p.blocks, sums, index, residual);
 }
 
 inline int register_accumulate(const RegisterArgs &a, const RegisterPlan &p, const double *pose, double *sums,
                                int64_t *index, float *residual, hipStream_t st, const char *what) {
-  const CloudLayout l = cloud_layout(a.n_target);
   const bool matches = index != nullptr;
   if (a.normals) {
-    if (matches) register_launch<true, true>(a, p, l, pose, sums, index, residual, st);
-    else register_launch<true, false>(a, p, l, pose, sums, index, residual, st);
+    if (matches) register_launch<true, true>(a, p, pose, sums, index, residual, st);
+    else register_launch<true, false>(a, p, pose, sums, index, residual, st);
   } else {
-    if (matches) register_launch<false, true>(a, p, l, pose, sums, index, residual, st);
-    else register_launch<false, false>(a, p, l, pose, sums, index, residual, st);
+    if (matches) register_launch<false, true>(a, p, pose, sums, index, residual, st);
+    else register_launch<false, false>(a, p, pose, sums, index, residual, st);
   }
   return check_launch(what);
 }

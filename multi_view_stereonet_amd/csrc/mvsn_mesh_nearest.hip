@@ -15,7 +15,7 @@
 //   nearest_scatter_kernel  one thread per face: its row into the records of every cell of its box (a returning
 //                           atomicAdd on the cell's cursor), or onto the list of large faces
 // mvsn_mesh_nearest, one launch:
-//   nearest_query_kernel    one thread per query: cloud_walk's cells and probe; a face met in cell c is evaluated only
+//   nearest_query_kernel    one thread per query: cloud_cells (mvsn_cloud.h); a face met in cell c is evaluated only
 //                           where c is the componentwise maximum of the lower corners of the query's range and of the
 //                           face's box (once per query); then every large face; the minimum of (d2 bits, row) as one
 //                           64-bit key and the count; the winner's point and weights recomputed once after the walk
@@ -28,16 +28,6 @@
 #include "mvsn_cloud.h"
 
 namespace mvsn {
-
-// defined in mvsn_cloud.hip: the table init, the per-workgroup population sums and the starts of a cloud index
-__global__ __launch_bounds__(CL_THREADS) void cloud_init_kernel(unsigned long long *__restrict__ keys,
-                                                                int *__restrict__ pop, int *__restrict__ cursor,
-                                                                unsigned long long *__restrict__ status);
-__global__ __launch_bounds__(CL_THREADS) void cloud_count_kernel(const int *__restrict__ pop,
-                                                                 int *__restrict__ block_counts);
-__global__ __launch_bounds__(CL_THREADS) void cloud_start_kernel(const int *__restrict__ pop,
-                                                                 const int64_t *__restrict__ offsets,
-                                                                 int *__restrict__ start);
 
 constexpr int MN_THREADS = 256;                         // one face, or one query, per thread
 constexpr long MN_MAX = 0x7fffffffL;                    // vertices, faces, queries, pairs: a row is an int32
@@ -254,53 +244,31 @@ __global__ __launch_bounds__(MN_THREADS) void nearest_query_kernel(
   const long i = (long)blockIdx.x * MN_THREADS + threadIdx.x;
   if (i >= nq) return;
   const float q[3] = {query[i * 3], query[i * 3 + 1], query[i * 3 + 2]};
+  const CloudIndex ix = {keys, pop, start, slots};
   int count = 0;
   unsigned long long best = ~0ull;
-  const float tx = q[0] * inv, ty = q[1] * inv, tz = q[2] * inv;
-  // a query whose t overflows is farther than max_dist from every point of a face that has a box: nothing to visit
-  if (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]) && isfinite(tx) && isfinite(ty) && isfinite(tz)) {
-    const float reach = r2 < 0x1p-100f ? 2.0f : 1.0f;
-    int lo[3], hi[3];
-    cloud_cell_range(tx, reach, lo + 0, hi + 0);
-    cloud_cell_range(ty, reach, lo + 1, hi + 1);
-    cloud_cell_range(tz, reach, lo + 2, hi + 2);
-    const size_t mask = slots - 1;
-    int c[3];
-    for (c[0] = lo[0]; c[0] <= hi[0]; ++c[0])
-      for (c[1] = lo[1]; c[1] <= hi[1]; ++c[1])
-        for (c[2] = lo[2]; c[2] <= hi[2]; ++c[2]) {
-          const unsigned long long key = voxel_key(c);
-          size_t h = (size_t)voxel_hash(key) & mask;
-          long from = 0, to = 0;
-          for (size_t probe = 0; probe < slots; ++probe) {  // bounded: every slot at most once
-            const unsigned long long seen = keys[h];
-            if (seen == key) {
-              from = (long)start[h];
-              to = from + (long)pop[h];
-              break;
-            }
-            if (seen == VX_EMPTY) break;
-            h = (h + 1) & mask;
-          }
-          from = max(from, 0L), to = min(to, pairs);       // (a built table's ranges are inside; any other stays inside too)
-          for (long j = from; j < to; ++j) {
-            const long row = (long)records[j];
-            if (row < 0 || row >= f) continue;             // (a built record is a face row: always inside)
-            float p[3][3];
-            int flo[3], fhi[3];
-            if (nearest_face_box(vertices, m, faces, row, inv, p, flo, fhi) != MN_BOXED) continue;
-            // once per query: only in the lowest cell that the query's range and the face's box share
-            if (c[0] != max(lo[0], flo[0]) || c[1] != max(lo[1], flo[1]) || c[2] != max(lo[2], flo[2])) continue;
-            float x32[3];
-            double w[3];
-            const float d2 = nearest_closest(q, p, x32, w);
-            if (d2 <= r2) {
-              ++count;
-              const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)row;
-              best = k < best ? k : best;
-            }
-          }
-        }
+  const bool visits = cloud_cells(q[0], q[1], q[2], inv, r2, ix, pairs,
+                                  [&](const int *c, const int *lo, long from, long to) {
+    for (long j = from; j < to; ++j) {
+      const long row = (long)records[j];
+      if (row < 0 || row >= f) continue;                   // (a built record is a face row: always inside)
+      float p[3][3];
+      int flo[3], fhi[3];
+      if (nearest_face_box(vertices, m, faces, row, inv, p, flo, fhi) != MN_BOXED) continue;
+      // once per query: only in the lowest cell that the query's range and the face's box share
+      if (c[0] != max(lo[0], flo[0]) || c[1] != max(lo[1], flo[1]) || c[2] != max(lo[2], flo[2])) continue;
+      float x32[3];
+      double w[3];
+      const float d2 = nearest_closest(q, p, x32, w);
+      if (d2 <= r2) {
+        ++count;
+        const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)row;
+        best = k < best ? k : best;
+      }
+    }
+  });
+  // (a query without cells is farther than max_dist from every point of a face that has a box)
+  if (visits) {
     for (long j = 0; j < large; ++j) {                     // the large faces: every query tests each directly
       const long row = (long)large_rows[j];
       if (row < 0 || row >= f) continue;
@@ -431,11 +399,11 @@ extern "C" int mvsn_mesh_nearest(const float *query, long nq, const float *verti
                "mvsn_mesh_nearest: squared radius %g is not a positive finite number", (double)r2);
   NearestLayout l;
   if (int e = nearest_check_workspace("mvsn_mesh_nearest", n_pairs, n_large, workspace, workspace_bytes, &l)) return e;
-  const char *ws = (const char *)workspace;
+  const int *records;
+  const CloudIndex ix = cloud_index(workspace, l, &records);
   hipLaunchKernelGGL(nearest_query_kernel, dim3((unsigned)((nq + MN_THREADS - 1) / MN_THREADS)), dim3(MN_THREADS), 0,
-                     (hipStream_t)stream, query, nq, vertices, n_vertices, faces, n_faces, inv_cell, r2,
-                     (const unsigned long long *)(ws + l.keys), (const int *)(ws + l.pop), (const int *)(ws + l.start),
-                     (const int *)(ws + l.records), l.slots, n_pairs, (const int *)(ws + l.large), n_large, dist2, face,
-                     point, weights, within);
+                     (hipStream_t)stream, query, nq, vertices, n_vertices, faces, n_faces, inv_cell, r2, ix.keys, ix.pop,
+                     ix.start, records, ix.slots, n_pairs, (const int *)((const char *)workspace + l.large), n_large, dist2,
+                     face, point, weights, within);
   return check_launch("mvsn_mesh_nearest: query");
 }

@@ -443,6 +443,34 @@ def cloud_radius_scalars(max_dist, name="max_dist"):
     return _positive_f32(max_dist, name, inverse=True, square=True)
 
 
+def _require_hip(who, t, noun="clouds"):
+    if not t.is_cuda:
+        raise RuntimeError(f"{who} runs on HIP devices only: move the {noun} to 'cuda' "
+                           "(there is no CPU implementation)")
+
+
+def _raise_cloud_status(bits, h, who):
+    if bits & CLOUD_STATUS_RANGE:
+        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
+                         f"cells of {float(h):g} or more from the origin")
+    if bits:
+        raise RuntimeError(f"{who}: the hash grid overflowed (status {bits})")
+
+
+def _cloud_index_build(lib, target, n, h, inv, dev, st, status=None):
+    """``(ws, ws_bytes, status)``: the hash-grid index of ``target`` (n,3) fp32, contiguous on ``dev``, enqueued on
+    stream ``st`` in a workspace made here.  The build's status word goes to ``status`` (an int64 word on ``dev``; made
+    here without one): the caller reads it after its own launches, its one host synchronisation, and hands it to
+    ``_raise_cloud_status``."""
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int64, device=dev)
+    _native.check(lib.mvsn_cloud_index_build(_native.ptr(target), n, float(h), float(inv), _native.ptr(status),
+                                             _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+    return ws, ws_bytes, status
+
+
 def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) -> CloudNeighbours:
     """For every row of ``query`` (N,3) fp32 the nearest row of ``target`` (T,3) fp32 within ``max_dist``: its squared
     distance, its row, and how many target points lie within ``max_dist``.  Neither cloud needs any order.
@@ -465,30 +493,20 @@ def cloud_nearest(query: torch.Tensor, target: torch.Tensor, max_dist: float) ->
         return CloudNeighbours(torch.full((N,), float("inf"), dtype=torch.float32, device=dev),
                                torch.full((N,), -1, dtype=torch.int64, device=dev),
                                torch.zeros((N,), dtype=torch.int32, device=dev))
-    if not query.is_cuda:
-        raise RuntimeError("cloud_nearest runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_nearest", query)
     lib = _native.load()
     q, t = query.detach().contiguous(), target.detach().contiguous()
-    ws_bytes = lib.mvsn_cloud_workspace_bytes(T)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     out = CloudNeighbours(torch.empty((N,), dtype=torch.float32, device=dev),
                           torch.empty((N,), dtype=torch.int64, device=dev),
                           torch.empty((N,), dtype=torch.int32, device=dev))
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), T, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        ws, ws_bytes, status = _cloud_index_build(lib, t, T, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_nearest(_native.ptr(q), N, float(inv), float(r2), _native.ptr(ws), ws_bytes, T,
                                              _native.ptr(out.dist2), _native.ptr(out.index), _native.ptr(out.within),
                                              st), "mvsn_cloud_nearest")
         bits = int(status.item())      # the one host synchronisation (the query never leaves its buffers, whatever the table holds)
-    if bits & CLOUD_STATUS_RANGE:
-        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
-                         f"cells of {float(h):g} or more from the origin")
-    if bits:
-        raise RuntimeError(f"cloud_nearest: the hash grid overflowed (status {bits})")
+    _raise_cloud_status(bits, h, "cloud_nearest")
     return out
 
 
@@ -573,25 +591,19 @@ def cloud_normals(points: torch.Tensor, radius: float, *, support: Optional[torc
         return CloudNormals(torch.zeros((N, 3), dtype=torch.float32, device=dev),
                             torch.zeros((N, 3), dtype=torch.float32, device=dev),
                             torch.zeros((N,), dtype=torch.int32, device=dev))
-    if not points.is_cuda:
-        raise RuntimeError("cloud_normals runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_normals", points)
     lib = _native.load()
     q = points.detach().contiguous()
     t = q if own else support.detach().contiguous()
     if view is not None:
         view = view.to(dev).contiguous()
     rows = 0 if view is None else int(view.shape[0])
-    ws_bytes = lib.mvsn_cloud_workspace_bytes(M)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     out = CloudNormals(torch.empty((N, 3), dtype=torch.float32, device=dev),
                        torch.empty((N, 3), dtype=torch.float32, device=dev),
                        torch.empty((N,), dtype=torch.int32, device=dev))
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        ws, ws_bytes, status = _cloud_index_build(lib, t, M, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_normals(_native.ptr(q), N, _native.ptr(view), rows, float(h), float(inv), float(r2),
                                              k, gap, _native.ptr(ws), ws_bytes, M, _native.ptr(out.normals),
                                              _native.ptr(out.eigenvalues), _native.ptr(out.count), st),
@@ -683,14 +695,6 @@ def _register_centre(c, target, dev):
     return (total / ok.sum().clamp(min=1).to(torch.float64)).to(torch.float32).contiguous()
 
 
-def _raise_cloud_status(bits, h, who):
-    if bits & CLOUD_STATUS_RANGE:
-        raise ValueError(f"max_dist too small for the target's extent: a target point lies 2^20 = {VOXEL_CELL_LIMIT} "
-                         f"cells of {float(h):g} or more from the origin")
-    if bits:
-        raise RuntimeError(f"{who}: the hash grid overflowed (status {bits})")
-
-
 def cloud_register_system(source: torch.Tensor, target: torch.Tensor, max_dist: float, T: torch.Tensor, *,
                           target_normals: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
                           centre=None, with_matches: bool = False):
@@ -708,25 +712,20 @@ def cloud_register_system(source: torch.Tensor, target: torch.Tensor, max_dist: 
         res = torch.full((N,), float("nan"), dtype=torch.float32, device=dev) if with_matches else None
         return (torch.zeros((6, 6), **f64), torch.zeros((6,), **f64), torch.zeros((), dtype=torch.int64, device=dev),
                 torch.zeros((), **f64), torch.zeros((), **f64), index, res)
-    if not source.is_cuda:
-        raise RuntimeError("cloud_register_system runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_register_system", source)
     lib = _native.load()
     s, t = source.detach().contiguous(), target.detach().contiguous()
     nm = target_normals.detach().contiguous() if target_normals is not None else None
     wt = weights.detach().contiguous() if weights is not None else None
     cen = _register_centre(c, t, dev)
-    idx_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(M), lib.mvsn_cloud_register_workspace_bytes(N)
-    idx_ws = torch.empty(idx_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = lib.mvsn_cloud_register_workspace_bytes(N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     Hm, b, sums = torch.empty((6, 6), **f64), torch.empty((6,), **f64), torch.empty((3,), **f64)
     index = torch.empty((N,), dtype=torch.int64, device=dev) if with_matches else None
     res = torch.empty((N,), dtype=torch.float32, device=dev) if with_matches else None
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(idx_ws), idx_bytes, st), "mvsn_cloud_index_build")
+        idx_ws, idx_bytes, status = _cloud_index_build(lib, t, M, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_register_system(
             _native.ptr(s), N, _native.ptr(wt), _native.ptr(t), _native.ptr(nm), M, float(inv), float(r2),
             _native.ptr(idx_ws), idx_bytes, _native.ptr(T32), _native.ptr(cen), _native.ptr(ws), ws_bytes, _native.ptr(Hm),
@@ -775,25 +774,20 @@ def cloud_register(source: torch.Tensor, target: torch.Tensor, max_dist: float, 
     if N == 0 or M == 0:               # nothing to match, nothing to launch: the run stops at once
         return CloudRegistration(T32.clone(), torch.zeros((it + 1, 3), **f64),
                                  torch.ones((), dtype=torch.int32, device=dev), torch.zeros((6, 6), **f64))
-    if not source.is_cuda:
-        raise RuntimeError("cloud_register runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_register", source)
     lib = _native.load()
     s, t = source.detach().contiguous(), target.detach().contiguous()
     nm = target_normals.detach().contiguous() if target_normals is not None else None
     wt = weights.detach().contiguous() if weights is not None else None
     cen = _register_centre(c, t, dev)
-    idx_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(M), lib.mvsn_cloud_register_workspace_bytes(N)
-    idx_ws = torch.empty(idx_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = lib.mvsn_cloud_register_workspace_bytes(N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     run = torch.empty(1, dtype=torch.int32, device=dev)
     out = CloudRegistration(torch.empty((4, 4), dtype=torch.float32, device=dev), torch.empty((it + 1, 3), **f64),
                             run[0], torch.empty((6, 6), **f64))
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), M, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(idx_ws), idx_bytes, st), "mvsn_cloud_index_build")
+        idx_ws, idx_bytes, status = _cloud_index_build(lib, t, M, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_register(
             _native.ptr(s), N, _native.ptr(wt), _native.ptr(t), _native.ptr(nm), M, float(inv), float(r2),
             _native.ptr(idx_ws), idx_bytes, _native.ptr(T32), _native.ptr(cen), it, mp, pv, _native.ptr(ws), ws_bytes,
@@ -859,23 +853,17 @@ def _cloud_knn(who, query, target, N, T, dev, k, h, inv, r2, exclude_self, with_
                        torch.full((N, k), -1, dtype=torch.int64, device=dev),
                        torch.zeros((N,), dtype=torch.int32, device=dev))
         return out, (torch.full((N,), float("nan"), dtype=torch.float64, device=dev) if with_mean else None)
-    if not query.is_cuda:
-        raise RuntimeError(f"{who} runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip(who, query)
     lib = _native.load()
     q = query.detach().contiguous()
     t = q if target is query else target.detach().contiguous()
-    ws_bytes = lib.mvsn_cloud_workspace_bytes(T)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     out = CloudKNN(torch.empty((N, k), dtype=torch.float32, device=dev),
                    torch.empty((N, k), dtype=torch.int64, device=dev),
                    torch.empty((N,), dtype=torch.int32, device=dev))
     mean = torch.empty((N,), dtype=torch.float64, device=dev) if with_mean else None
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(t), T, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        ws, ws_bytes, status = _cloud_index_build(lib, t, T, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_knn(_native.ptr(q), N, k, 1 if exclude_self else 0, float(h), float(inv), float(r2),
                                          _native.ptr(ws), ws_bytes, T, _native.ptr(out.dist2), _native.ptr(out.index),
                                          _native.ptr(out.within), _native.ptr(mean), st), "mvsn_cloud_knn")
@@ -995,21 +983,17 @@ def cloud_clusters(points: torch.Tensor, eps: float, min_points: int) -> CloudCl
         return CloudClusters(torch.empty((0,), **i64), torch.empty((0,), dtype=torch.bool, device=dev),
                              torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), **i64),
                              torch.empty((0,), **i64), torch.empty((0,), **i64))
-    if not points.is_cuda:
-        raise RuntimeError("cloud_clusters runs on HIP devices only: move the cloud to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_clusters", points, "cloud")
     lib = _native.load()
     p = points.detach().contiguous()
-    index_bytes, ws_bytes = lib.mvsn_cloud_workspace_bytes(N), lib.mvsn_cloud_cluster_workspace_bytes(N)
-    index_ws = torch.empty(index_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = lib.mvsn_cloud_cluster_workspace_bytes(N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     head = torch.empty(3, **i64)       # (C, the union-find's status, the index build's status)
     within = torch.empty((N,), dtype=torch.int32, device=dev)
     core = torch.empty((N,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(p), N, float(h), float(inv), _native.ptr(head[2:]),
-                                                 _native.ptr(index_ws), index_bytes, st), "mvsn_cloud_index_build")
+        index_ws, index_bytes, _ = _cloud_index_build(lib, p, N, h, inv, dev, st, status=head[2:])
         _native.check(lib.mvsn_cloud_cluster_label(_native.ptr(p), N, float(inv), float(r2), k, _native.ptr(index_ws),
                                                    index_bytes, _native.ptr(within), _native.ptr(core), _native.ptr(head),
                                                    _native.ptr(ws), ws_bytes, st), "mvsn_cloud_cluster_label")
@@ -1352,21 +1336,15 @@ def cloud_fpfh(points: torch.Tensor, normals: torch.Tensor, radius: float, *, mi
         return CloudFeatures(torch.zeros((0, FEATURE_DIM), dtype=torch.float32, device=dev),
                              torch.zeros((0, FEATURE_DIM), dtype=torch.int32, device=dev),
                              torch.zeros((0,), dtype=torch.int32, device=dev))
-    if not points.is_cuda:
-        raise RuntimeError("cloud_fpfh runs on HIP devices only: move the clouds to 'cuda' "
-                           "(there is no CPU implementation)")
+    _require_hip("cloud_fpfh", points)
     lib = _native.load()
     p, nm = points.detach().contiguous(), normals.detach().contiguous()
-    ws_bytes = lib.mvsn_cloud_workspace_bytes(N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    status = torch.empty(1, dtype=torch.int64, device=dev)
     out = CloudFeatures(torch.empty((N, FEATURE_DIM), dtype=torch.float32, device=dev),
                         torch.empty((N, FEATURE_DIM), dtype=torch.int32, device=dev),
                         torch.empty((N,), dtype=torch.int32, device=dev))
     with torch.cuda.device(dev):
         st = _native.stream()
-        _native.check(lib.mvsn_cloud_index_build(_native.ptr(p), N, float(h), float(inv), _native.ptr(status),
-                                                 _native.ptr(ws), ws_bytes, st), "mvsn_cloud_index_build")
+        ws, ws_bytes, status = _cloud_index_build(lib, p, N, h, inv, dev, st)
         _native.check(lib.mvsn_cloud_fpfh(_native.ptr(p), _native.ptr(nm), N, float(h), float(inv), float(r2), k,
                                           _native.ptr(ws), ws_bytes, _native.ptr(out.spfh), _native.ptr(out.pairs),
                                           _native.ptr(out.features), st), "mvsn_cloud_fpfh")

@@ -13,7 +13,8 @@ import functools
 
 import numpy as np
 
-from cloud_reference import CHUNK_ELEMENTS, radius_scalars, squared_distances, target_cells
+from cloud_reference import (CHUNK_ELEMENTS, grid_edge_clouds, radius_scalars, reach2_clouds, squared_distances,
+                             target_cells)
 from multi_view_stereonet_amd.fusion import CloudClusters
 
 MAX_POINTS = 16384                 # per case: the brute force stays within a few seconds
@@ -272,6 +273,10 @@ _CASES = {
     "nonfinite": lambda: (_nonfinite(), H, (1, 4)),
     "far": lambda: (_far(), H, (3,)),
     "tiny": lambda: (_tiny(), H * 2.0 ** -72, (4,)),
+    # cloud_nearest's two hard inputs at a few dozen points (cloud_reference.py): both clouds of the two-cell reach as one,
+    # and the targets in the grid's last cells (a query beyond the edge has no cell to be indexed in)
+    "reach2": lambda: (np.concatenate(reach2_clouds()[:2]), reach2_clouds()[2], (1,)),
+    "grid_edge": lambda: (grid_edge_clouds()[1], grid_edge_clouds()[2], (1,)),
     "many_small": lambda: (_many_small(), H, (1, 3, 4)),
     "mixed_2000": lambda: (_mixed(2000, 307), H, (5, 14)),
     "scene": lambda: (_scene(), 0.08, (1, 4, 10)),                       # (at 10 the permutation case: no tied border distance)

@@ -112,3 +112,38 @@ def cloud_metrics_reference(pred, truth, threshold, max_dist=None):
     fscore = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
     return {"accuracy": s_p / n_p, "completeness": s_t / n_t, "precision": precision, "recall": recall,
             "fscore": fscore, "n_pred": n_p, "n_truth": n_t, "close_pred": k_p, "close_truth": k_t}
+
+
+# ---- two inputs of tests/test_cloud_gpu.py at a few dozen points, for the kernels that query through the visitor --------
+def reach2_clouds():
+    """(query (36,3), target (60,3), h) of test_tiny_max_dist_whose_square_is_a_denormal: h = 2^-74, so r2 = 2^-148 is two
+    quanta of the denormal range and the kernel reaches two cells; query 0 and target 0 lie in cells 2 and 0 of x, 1.1 h
+    apart, and are within."""
+    h = 2.0 ** -74
+    rng = np.random.default_rng(45)
+    t = (rng.uniform(-2, 2, (60, 3)) * h).astype(np.float32)
+    q = (rng.uniform(-2.5, 2.5, (36, 3)) * h).astype(np.float32)
+    t[0], q[0] = (0.95 * h, 0, 0), (2.05 * h, 0, 0)
+    return q, t, h
+
+
+def grid_edge_clouds():
+    """(query (48,3), target (60,3), h) of test_cluster_at_half_a_million_cells_and_at_the_grids_edge, its second half: on
+    each axis and on either side ten targets in the last cells of the grid, up to its edge (cell 2^20 - 1 above, cell
+    -2^20 below), and eight queries on both sides of the edge."""
+    h = 0.25
+    edge = np.float32(2.0 ** 20 * h)
+    top = np.nextafter(edge, np.float32(0))                  # the largest coordinate of cell 2^20 - 1
+    rng = np.random.default_rng(44)
+    q, t = [], []
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            shift = np.zeros(3, np.float32)
+            shift[axis] = sign * (edge - 0.5)
+            width = np.full(3, 0.25)
+            width[axis] = 0.5
+            tt = rng.uniform(-width, width, (10, 3)).astype(np.float32) + shift
+            tt[:, axis] = np.clip(tt[:, axis], -edge, top)   # (-edge is in cell -2^20, the lowest)
+            t.append(tt)
+            q.append(rng.uniform(-1.2 * width, 1.2 * width, (8, 3)).astype(np.float32) + shift)
+    return np.concatenate(q), np.concatenate(t), h

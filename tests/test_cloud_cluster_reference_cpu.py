@@ -206,3 +206,22 @@ def test_the_mask_rules():
     assert m(ref, keep_largest=0).tolist() == [False] * 10 and m(ref, min_size=0).tolist() == (ref["label"] >= 0).tolist()
     assert m(ref, keep=[True, False, False, True]).tolist() == [True, False, False, False, False, False, False, True, True, False]
     assert m(ref, min_size=9).tolist() == [False] * 10 and m(ref, keep_largest=9).tolist() == (ref["label"] >= 0).tolist()
+
+
+def test_the_walk_cases_are_cloud_nearests_hard_inputs():
+    points, eps, mps = cc.case("reach2")
+    h, inv, r2 = radius_scalars(eps)
+    assert mps == (1,) and len(points) == 96 and 0 < r2 < np.float32(2.0 ** -100)
+    ref = cc.case_reference("reach2", 1)
+    i, j, _ = cc._case_pairs("reach2")
+    c = np.floor(points * inv)
+    assert (np.abs(c[i] - c[j]).max(axis=1) == 2).sum() >= 6                       # neighbours two cells apart
+    assert ref["core"].all() and 1 < len(ref["first"]) < 96 and ref["count"].max() > 1
+    points, eps, mps = cc.case("grid_edge")
+    ref = cc.case_reference("grid_edge", 1)
+    c = np.floor(points * radius_scalars(eps)[1])
+    assert mps == (1,) and len(points) == 60 and c.max() == 2 ** 20 - 1 and c.min() == -2 ** 20
+    assert ref["core"].all() and 6 <= len(ref["first"]) < 60 and ref["count"].max() > 1
+    for name in ("reach2", "grid_edge"):                                          # min_points = 1: no border, no noise
+        r = cc.case_reference(name, 1)
+        assert (r["label"] >= 0).all() and r["within"].tobytes() == cloud_nearest_reference(*(cc.case(name)[0],) * 2, cc.case(name)[1])["within"].tobytes()

@@ -167,3 +167,27 @@ def test_no_point_within_the_margin_of_its_threshold(name):
     gap = np.abs(ref["mean_dist"] - ref["threshold"])
     assert has.sum() >= 1600 and (gap[has] > margin[has]).all()                 # not one point excluded from the comparison
     assert margin[has].max() < 1e-12
+
+
+@pytest.mark.parametrize("name", ck.WALK_IDS)
+def test_the_walk_cases_are_cloud_nearests_hard_inputs(name):
+    c = ck.case(name)
+    q, t = c["query"], c["target"]
+    assert c["ks"] == (1, 9) and len(q) <= 60 and len(t) <= 60
+    h, inv, r2 = radius_scalars(c["h"])
+    one, nine = ck.case_reference(name, 1), ck.case_reference(name, 9)
+    want = cloud_nearest_reference(q, t, c["h"])
+    for key in ("dist2", "index", "within"):
+        assert one[key].reshape(-1).tobytes() == want[key].tobytes(), key
+    assert nine["within"].tobytes() == want["within"].tobytes() and 0 < (want["within"] > 0).mean() < 1
+    assert (want["within"] > 1).any() and (want["within"] < 9).any()
+    cq, ct = np.floor(q * inv), np.floor(t * inv)
+    if name == "reach2":
+        assert 0 < r2 < np.float32(2.0 ** -100) and want["within"][0] >= 1 and want["dist2"][0] <= r2
+        assert (want["within"] >= 9).any()                                        # a full list too
+        accepted = squared_distances(q, t) <= r2
+        assert (accepted & (np.abs(cq[:, None] - ct[None]).max(axis=2) == 2)).sum() >= 3     # pairs two cells apart
+    else:
+        assert ct.max() == 2 ** 20 - 1 and ct.min() == -2 ** 20                     # the grid's last cells, both ends
+        beyond = (np.abs(q) > np.float32(2.0 ** 20 * c["h"])).any(axis=1)
+        assert beyond.any() and (want["within"][beyond] > 0).any()                # a query beyond the edge with a neighbour
