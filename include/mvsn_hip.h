@@ -1155,6 +1155,50 @@ int mvsn_mesh_nearest(const float *query, long nq, const float *vertices, long n
                       size_t workspace_bytes, float *dist2, int64_t *face, float *point, float *weights, int *within,
                       mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A triangle mesh rendered into posed cameras: z-buffered depth, the winning face, its perspective-correct barycentric
+ * weights, and the interpolated vertex normal and colour (multi_view_stereonet_amd/mesh.py: mesh_render; the semantics and
+ * every operation are DESIGN.md section 27).
+ *   vertices (n_vertices,3) fp32   faces (n_faces,3) int64   1 <= n_vertices, n_faces <= 2^31 - 1; K, T_cam_in_world
+ *   (V,4,4), 1 <= V <= 65535; maps of rows x cols pixels, each 1..2^15.  A size outside these limits, a min_depth that is
+ *   not a finite number >= 0 or a max_depth that is not > 0 (+inf: no limit) is MVSN_E_BADARG; a workspace that is missing
+ *   or too small MVSN_E_WORKSPACE; all before any launch.
+ *   A face is valid when its three rows lie in [0, n_vertices) and its nine coordinates are finite (otherwise its indices
+ *   are never used as addresses).  Each vertex is projected by mvsn_cloud_render's steps on mvsn_tsdf_integrate's camera:
+ *   zc = P row 2 . (p,1), (u, v) = rows 0, 1 over zc, every step one fp32 operation; pixel centres are the integers.  A
+ *   valid face takes part in view v when every zc is finite and > min_depth and every |u|, |v| <= 2^16 (compared as
+ *   floats: a NaN fails); one that does not, although a vertex has zc > min_depth, adds 1 to clipped[v]: there is no
+ *   near-plane clipping.  X = rintf(256 u), Y = rintf(256 v) (8 sub-pixel bits, |X|, |Y| <= 2^24); coverage is decided on
+ *   these integers alone: A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0), A = 0 covers nothing, A < 0 swaps vertices 1 and 2 (both
+ *   sides are rendered); for the centre (256 c, 256 r) and every directed edge p->q of the oriented face,
+ *   E = (Xq-Xp)(256 r - Yp) - (Yq-Yp)(256 c - Xp); the pixel is covered when for all three E > 0, or E = 0 and (dy < 0, or
+ *   dy = 0 and dx < 0): of two faces that share an edge exactly one owns a centre on it.  At a covered pixel, in fp64 and
+ *   the face's own vertex order: lambda_k = E_k / A (E_k of the edge opposite vertex k), q_k = 1 / zc_k,
+ *   S = (lambda_0 q_0 + lambda_1 q_1) + lambda_2 q_2, z = (float)(1 / S); the pixel takes the face when z is finite and
+ *   min_depth < z <= max_depth.  Per view and pixel the least key (uint64(bits of z) << 32) | face row wins: the nearest
+ *   face, a tie on z to the lowest row.
+ * mvsn_mesh_render (clear, raster, resolve):
+ *   workspace: mvsn_mesh_render_workspace_bytes(V, rows, cols) = 8 V (rows cols + 1) bytes (0 for sizes the entry refuses),
+ *     16-byte aligned: one 64-bit key per pixel per view and one counter per view; it may arrive uninitialised.
+ *   -> depth (V,rows,cols) fp32: the winner's z, 0 where no face hit   face (V,rows,cols) int64: its row, -1 where none
+ *      weights (V,3,rows,cols) fp32: (float)((lambda_k q_k) / S), 0 where none
+ *      out_normals (V,3,rows,cols) fp32 with normals (n_vertices,3) fp32, or both NULL, and out_colors (V,3,rows,cols) u8
+ *      with colors (n_vertices,3) u8, or both NULL: mvsn_mesh_sample_draw's interpolation with the fp64 weights before
+ *      their rounding; zeros where none   clipped (V) int64.  Every element of every output is written once.
+ * mvsn_mesh_render_small_pixels: a face whose clipped box of pixels holds more than this many is rasterised by a whole
+ *   wave instead of one thread (a tuning constant: no output depends on it).
+ * Integer atomics only (the 64-bit minimum of mvsn_cloud_render with its skip, and a sum): every output is a
+ * bitwise-reproducible function of the inputs, whatever the order of the atomics; depth does not depend on the order of
+ * the faces.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_mesh_render_workspace_bytes(int n_views, int rows, int cols);
+int mvsn_mesh_render_small_pixels(void);
+int mvsn_mesh_render(const float *vertices, long n_vertices, const int64_t *faces, long n_faces, const float *normals,
+                     const uint8_t *colors, const float *K, const float *T_cam_in_world, int n_views, int rows, int cols,
+                     float min_depth, float max_depth, void *workspace, size_t workspace_bytes, float *depth,
+                     int64_t *face, float *weights, float *out_normals, uint8_t *out_colors, int64_t *clipped,
+                     mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

@@ -13,6 +13,10 @@ the mesh: the outputs do not depend on the order of the faces, on the order of a
 Scoring a mesh (csrc/mvsn_mesh_sample.hip, csrc/mvsn_mesh_nearest.hip): ``mesh_sample`` draws an
 area-uniform cloud from the surface, reproducibly, and ``mesh_nearest`` is the exact distance of points to the surface
 within a radius, the mesh counterpart of ``fusion.cloud_nearest``; ``metrics.mesh_metrics`` is built on the two.
+
+Rendering a mesh (csrc/mvsn_mesh_render.hip): ``mesh_render`` rasterises the faces into posed
+cameras, the mesh counterpart of ``fusion.cloud_render`` without its holes: depth, face and barycentric maps, and the
+interpolated normals and colours.
 """
 from typing import NamedTuple, Optional
 
@@ -365,4 +369,89 @@ def mesh_nearest(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tens
                                             pairs, large, _native.ptr(ws), ws_bytes, _native.ptr(out.dist2),
                                             _native.ptr(out.face), _native.ptr(out.point), _native.ptr(out.weights),
                                             _native.ptr(out.within), st), "mvsn_mesh_nearest")
+    return out
+
+
+# ---- a mesh rendered into posed cameras --------------------------------------------------------
+RENDER_MAX_EXTENT = 2 ** 15          # rows and columns of a rendered map
+
+
+class MeshRender(NamedTuple):
+    depth: torch.Tensor              # (V,1,H,W) fp32: z-depth of the nearest face per pixel, 0 where no face hit
+    face: torch.Tensor               # (V,H,W) int64: that face's row, -1 where none
+    weights: torch.Tensor            # (V,3,H,W) fp32: perspective-correct barycentric weights in the face's vertex order
+    normals: Optional[torch.Tensor]  # (V,3,H,W) fp32: the interpolated vertex normal (zeros where none), or None
+    colors: Optional[torch.Tensor]   # (V,3,H,W) uint8: the interpolated vertex colour (zeros where none), or None
+    clipped: torch.Tensor            # (V,) int64: faces in front of the camera that the view left out
+
+
+def mesh_render(vertices: torch.Tensor, faces: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.Tensor, size, *,
+                normals: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None, min_depth: float = 0.0,
+                max_depth: float = float("inf")) -> MeshRender:
+    """Render the mesh ``vertices`` (M,3) fp32, ``faces`` (F,3) int64 into the V cameras ``K``, ``T_cam_in_world``
+    (V,4,4) with maps of ``size`` = (H,W): per pixel the z-depth of the nearest face whose projection holds the pixel
+    centre, that face's row and the perspective-correct barycentric weights of the centre in it, and with ``normals``
+    (M,3) fp32 and ``colors`` (M,3) uint8 the interpolated vertex normal and colour; DESIGN.md section 27,
+    csrc/mvsn_mesh_render.hip.  What turns a mesh -- one that went through ``filter_mesh``, was read back from a file,
+    or is somebody's ground truth -- into depth maps for ``metrics.depth_metric_rows``, and into a hole-free occluder
+    for ``fusion.cloud_visibility`` and ``fusion.cloud_colorize``.
+
+    The camera and the projection are ``fusion.cloud_render``'s, step for step, and pixel centres are the integers.  A
+    face takes part in a view when its rows lie in [0, M), its coordinates are finite, every vertex has a finite z >
+    ``min_depth`` and projects within 2^16 pixels of the origin.  There is no near-plane clipping: a face that crosses
+    the near plane or leaves that guard band is missing from the picture, and ``clipped[v]`` counts the faces view v
+    lost that way (a face wholly behind the camera is not counted).  The projected vertices are snapped to 1/256 of a
+    pixel and coverage is exact integer work on the snapped triangle: both sides of a face are rendered, a face without
+    area covers nothing, and of two faces that share an edge exactly one owns a pixel centre on it, so a watertight
+    mesh is rendered without gaps and without double hits.  The depth at a covered pixel is 1 / sum(lambda_k / z_k) in
+    fp64, rounded once; the pixel takes the face when ``min_depth`` < z <= ``max_depth``; the nearest face wins, a tie
+    on z goes to the lowest row.  ``weights`` are (lambda_k / z_k) z, and the gathers are ``mesh_sample``'s
+    interpolation with them: the normal is the normalised weighted sum, (0,0,0) where it has no direction, the colour
+    the weighted sum rounded to nearest.  Where no face lands the depth is 0, the face -1, everything else zero.
+
+    Every output is a bitwise-reproducible function of the inputs: the only atomics are an integer minimum and an
+    integer sum.  ``depth`` does not depend on the order of the faces.  F = 0 or M = 0 gives the all-miss render
+    without a launch.  Everything is validated here, before any launch; no host synchronisation."""
+    from .fusion import _check_render_cameras, _depth_limit_f32, _integer_in
+    m, f, dev = _check_surface(vertices, faces)
+    V = _check_render_cameras(K, T_cam_in_world, dev, "vertices")
+    try:
+        H, W = (_integer_in(x, "size", 1, RENDER_MAX_EXTENT) for x in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be two integers (H,W), each in [1, 2^15], got {size!r}") from None
+    for name, t, dtype in (("normals", normals, torch.float32), ("colors", colors, torch.uint8)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (m, 3) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a ({m},3) {dtype} tensor, one row per vertex")
+        if t.device != dev:
+            raise ValueError(f"{name} are on {t.device}, vertices on {dev}")
+    lo = _depth_limit_f32(min_depth, "min_depth")
+    hi = _depth_limit_f32(max_depth, "max_depth", infinite=True, positive=True)
+    launch = f > 0 and m > 0
+    make = torch.empty if launch else torch.zeros
+    out = MeshRender(make((V, 1, H, W), dtype=torch.float32, device=dev), make((V, H, W), dtype=torch.int64, device=dev),
+                     make((V, 3, H, W), dtype=torch.float32, device=dev),
+                     make((V, 3, H, W), dtype=torch.float32, device=dev) if normals is not None else None,
+                     make((V, 3, H, W), dtype=torch.uint8, device=dev) if colors is not None else None,
+                     make((V,), dtype=torch.int64, device=dev))
+    if not launch:                     # no face: every pixel is a miss, nothing to launch
+        out.face.fill_(-1)
+        return out
+    if not vertices.is_cuda:
+        raise RuntimeError("mesh_render runs on HIP devices only: move the mesh and the cameras to 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
+    dense = lambda t: t.detach().contiguous() if t is not None else None   # noqa: E731
+    # (every converted copy is held until the launches are enqueued: a temporary's memory could be handed out again)
+    v_c, f_c, nor_c, col_c, K_c, T_c = dense(vertices), dense(faces), dense(normals), dense(colors), f32(K), f32(T_cam_in_world)
+    ws_bytes = lib.mvsn_mesh_render_workspace_bytes(V, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_mesh_render(
+            _native.ptr(v_c), m, _native.ptr(f_c), f, _native.ptr(nor_c), _native.ptr(col_c), _native.ptr(K_c),
+            _native.ptr(T_c), V, H, W, float(lo), float(hi), _native.ptr(ws), ws_bytes, _native.ptr(out.depth),
+            _native.ptr(out.face), _native.ptr(out.weights), _native.ptr(out.normals), _native.ptr(out.colors),
+            _native.ptr(out.clipped), _native.stream()), "mvsn_mesh_render")
     return out

@@ -84,7 +84,12 @@ threshold of one voxel) and reports, as "mesh_metrics", M, F, the (cell, face) p
 per mesh.mesh_sample of MESH_SAMPLES points, per mesh.mesh_nearest of the N fused points against the mesh and per
 mesh_metrics, ms of fusion.cloud_nearest of the same N points against the mesh's vertices (for scale), the same distance by
 brute force from torch ops (fp64, every face against the first TORCH_QUERIES points, in chunks of faces) with the rows whose
-dist2 bits or face differ, and the scores next to cloud_metrics of the vertices."""
+dist2 bits or face differ, and the scores next to cloud_metrics of the vertices.
+--mesh-render: also renders the mesh of each scene's --tsdf volume into the scene's own views (mesh.mesh_render) and
+reports, as "mesh_render", M, F, ms per call with and without the normal and colour gathers, ms of fusion.cloud_render of
+the vertices and its share of pixels hit (for scale: the holes a vertex render leaves), the share of pixels hit, the sum
+of clipped, and against TSDFVolume.raycast at the same poses the share of pixels both hit and the median and the 99th
+percentile of |depth - raycast depth| over them, in voxels."""
 import argparse
 import json
 import os
@@ -100,7 +105,7 @@ from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_render, cloud_visibility, cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
-from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_sample  # noqa: E402
+from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_render, mesh_sample  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics, mesh_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
@@ -1099,8 +1104,39 @@ def run_mesh_metrics(sc, res, steps, warmup):
         "scores": scores, "vertices_as_a_cloud": cloud_metrics(v, truth, TSDF_VOXEL)}}
 
 
+def run_mesh_render(sc, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    V, _, H, W = depth.shape
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, 4 * TSDF_VOXEL, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    mesh = vol.extract_mesh()
+    v, f = mesh.vertices, mesh.faces
+    r, times = timed(lambda: mesh_render(v, f, K, T, (H, W)), steps, warmup)
+    full, gtimes = timed(lambda: mesh_render(v, f, K, T, (H, W), normals=mesh.normals, colors=mesh.colors), steps, warmup)
+    cloud, ctimes = timed(lambda: cloud_render(v, K, T, (H, W)), steps, warmup)
+    ray = vol.raycast(K, T, (H, W))
+    hit, rhit = r.depth > 0, ray.depth > 0
+    both = hit & rhit
+    diff = ((r.depth - ray.depth).abs()[both] / TSDF_VOXEL).double()
+    return {"mesh_render": {
+        "M": int(v.shape[0]), "F": int(f.shape[0]), "views": V, "pixels": V * H * W,
+        "workspace_bytes": int(_native.load().mvsn_mesh_render_workspace_bytes(V, H, W)),
+        "small_pixels": int(_native.load().mvsn_mesh_render_small_pixels()),
+        "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+        "with_gathers_ms_per_call_mean": float(np.mean(gtimes)), "with_gathers_ms_per_call_min": float(np.min(gtimes)),
+        "cloud_render_of_vertices_ms_per_call_mean": float(np.mean(ctimes)),
+        "cloud_render_of_vertices_hit_share": float((cloud.depth > 0).float().mean()),
+        "hit_share": float(hit.float().mean()), "clipped_sum": int(r.clipped.sum()),
+        "gathers_same_depth": bool(torch.equal(full.depth, r.depth)),
+        "raycast_hit_share": float(rhit.float().mean()), "both_hit_share": float(both.float().mean()),
+        "hit_mask_agreement": float((hit == rhit).float().mean()),
+        "abs_depth_minus_raycast_voxels_median": float(diff.median()) if diff.numel() else 0.0,
+        "abs_depth_minus_raycast_voxels_p99": float(torch.quantile(diff[:: max(1, diff.numel() // (1 << 22))], 0.99))
+        if diff.numel() else 0.0}}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False, mesh_render_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -1128,7 +1164,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     split = run_clusters(res, float(sc["K"][0, 0, 0]), steps, warmup) if clusters else {}
     drawn = run_render(sc, res, steps, warmup) if render else {}
     mesh_scored = run_mesh_metrics(sc, res, steps, warmup) if mesh_metrics_too else {}
-    return {**mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    rasterised = run_mesh_render(sc, steps, warmup) if mesh_render_too else {}
+    return {**rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -1172,12 +1209,15 @@ def main():
     ap.add_argument("--mesh-metrics", action="store_true",
                     help="also score the volume's mesh against the fused cloud (mesh_metrics) and time mesh_sample and "
                          "mesh_nearest, cloud_nearest against the vertices, and the torch brute force of the distance")
+    ap.add_argument("--mesh-render", action="store_true",
+                    help="also render the volume's mesh into the input views (mesh_render, with and without gathers), next "
+                         "to cloud_render of its vertices, and compare the depth with the volume's raycast")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
-                             a.render, a.mesh_metrics)), flush=True)
+                             a.render, a.mesh_metrics, a.mesh_render)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
