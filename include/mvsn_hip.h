@@ -1199,6 +1199,51 @@ int mvsn_mesh_render(const float *vertices, long n_vertices, const int64_t *face
                      int64_t *face, float *weights, float *out_normals, uint8_t *out_colors, int64_t *clipped,
                      mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Simplify a mesh by vertex clustering (multi_view_stereonet_amd/mesh.py: mesh_simplify; the semantics and every
+ * operation are DESIGN.md section 28; csrc/mvsn_mesh_simplify.hip).  The vertices of one cell of the grid (voxel_size,
+ * origin: mvsn_voxel_assign's cells, step for step) become one vertex; a face is remapped through the clustering and
+ * dropped when a corner lies outside [0, n_vertices), is a dropped (non-finite) vertex, or two of its corners share a
+ * cluster; of the faces whose remapped triples are equal up to rotation the one with the lowest row stays.
+ *   vertices (n_vertices,3) fp32, faces (n_faces,3) int64, normals (n_vertices,3) fp32 or NULL, colors (n_vertices,3) u8
+ *   or NULL; 1 <= n_vertices <= 2^31 - 1, 0 <= n_faces <= 2^31 - 1; voxel_size and inv_voxel_size as for the voxel merge
+ *   workspace: mvsn_mesh_simplify_workspace_bytes(n_vertices, n_faces) bytes (0 for sizes the entries refuse), 16-byte
+ *   aligned, handed from entry to entry unchanged: the voxel merge's workspace, 223 bytes per vertex for the clusters'
+ *   sums and rows, 4 bytes per face and per slot of the face table (a power of two >= 2 n_faces slots).
+ * mvsn_mesh_simplify_assign: mvsn_voxel_assign on the vertices.
+ *   -> result (2 int64): [0] the number of clusters C, [1] status bits (MVSN_VOXEL_STATUS_*; 0 = fine).  The first host read.
+ * mvsn_mesh_simplify_mark: clusters = C as read back (> 0).  The vertex side is mvsn_voxel_merge (and, with normals,
+ *   mvsn_voxel_normals) into the workspace.  placement 0 = the mean; 1 = the quadric: per face the unit normal n in fp64,
+ *   per corner u = (p - origin) / voxel_size - (cell + 0.5) and d = -n.u; n n^T, d n and 1 are quantised to 2^-30 and
+ *   summed per cluster with 64-bit integer atomics; x solves (A + lambda k I) x = -b + lambda k u_mean, lambda = 2^-10,
+ *   by the closed-form inverse, is clamped to |x| <= 0.5 - 2^-10 per axis, mapped back and rounded to fp32 once.  A
+ *   position that voxel_cell does not put into the cluster's own cell is replaced by the first member's position.
+ *   drop_unreferenced != 0: a cluster no surviving face uses is not output.
+ *   -> result (4 int64): [0] output vertices M', [1] output faces F', [2] status bits (MVSN_MESH_SIMPLIFY_STATUS_*),
+ *      [3] the clusters (output or not) whose position fell back to the first member's.  The second host read.
+ * mvsn_mesh_simplify_emit: out_vertices_n = M', out_faces_n = F' as read back; normals and colours are written where
+ *   the pointer is not NULL and mvsn_mesh_simplify_mark was given the input.
+ *   -> out_vertices (M',3) fp32  out_faces (F',3) int64: output rows in the input face's corner order
+ *      out_normals (M',3) fp32 or NULL  out_colors (M',3) u8 or NULL  count (M') int32  first (M') int64, ascending
+ *      inverse (n_vertices) int64: output row of every input vertex, -1 = none  face_rows (F') int64, ascending
+ * Integer atomics only (compare-and-swap on an empty slot, minima, sums): every output is a deterministic function of
+ * the inputs, whatever the order of the faces' arrival.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_MESH_SIMPLIFY_STATUS_TABLE 1   /* a probe sequence of the face set visited every slot without finding room
+                                               (cannot happen below 2^30 faces: the table is at most half full) */
+size_t mvsn_mesh_simplify_workspace_bytes(long n_vertices, long n_faces);
+int mvsn_mesh_simplify_assign(const float *vertices, long n_vertices, float voxel_size, float inv_voxel_size,
+                              float origin_x, float origin_y, float origin_z, int64_t *result, void *workspace,
+                              size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_simplify_mark(const float *vertices, const float *normals, const uint8_t *colors, long n_vertices,
+                            const int64_t *faces, long n_faces, float voxel_size, float inv_voxel_size, float origin_x,
+                            float origin_y, float origin_z, int placement, int drop_unreferenced, long clusters,
+                            int64_t *result, void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_simplify_emit(const int64_t *faces, long n_vertices, long n_faces, long clusters, const void *workspace,
+                            size_t workspace_bytes, long out_vertices_n, long out_faces_n, float *out_vertices,
+                            int64_t *out_faces, float *out_normals, uint8_t *out_colors, int *count, int64_t *first,
+                            int64_t *inverse, int64_t *face_rows, mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

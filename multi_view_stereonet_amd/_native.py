@@ -180,6 +180,12 @@ SIGNATURES = {
     "mvsn_mesh_render_small_pixels": (c_int, []),
     "mvsn_mesh_render": (c_int, [c_void_p, c_long, c_void_p, c_long] + [c_void_p] * 4 + [c_int] * 3 +
                          [ctypes.c_float] * 2 + [c_void_p, c_size_t] + [c_void_p] * 6 + [c_void_p]),
+    "mvsn_mesh_simplify_workspace_bytes": (c_size_t, [c_long] * 2),
+    "mvsn_mesh_simplify_assign": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_simplify_mark": (c_int, [c_void_p] * 3 + [c_long, c_void_p, c_long] + [ctypes.c_float] * 5 +
+                                [c_int, c_int, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_simplify_emit": (c_int, [c_void_p, c_long, c_long, c_long, c_void_p, c_size_t, c_long, c_long] +
+                                [c_void_p] * 8 + [c_void_p]),
     "mvsn_cloud_cluster_workspace_bytes": (c_size_t, [c_long]),
     "mvsn_cloud_cluster_label": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_long, c_void_p, c_size_t] +
                                  [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),

@@ -17,6 +17,10 @@ within a radius, the mesh counterpart of ``fusion.cloud_nearest``; ``metrics.mes
 Rendering a mesh (csrc/mvsn_mesh_render.hip): ``mesh_render`` rasterises the faces into posed
 cameras, the mesh counterpart of ``fusion.cloud_render`` without its holes: depth, face and barycentric maps, and the
 interpolated normals and colours.
+
+Making a mesh smaller (csrc/mvsn_mesh_simplify.hip): ``mesh_simplify`` clusters the vertices on
+``fusion.voxel_merge``'s grid, remaps the faces, drops the collapsed and the repeated ones, and places each new vertex
+by the quadric of the faces around it.
 """
 from typing import NamedTuple, Optional
 
@@ -454,4 +458,127 @@ def mesh_render(vertices: torch.Tensor, faces: torch.Tensor, K: torch.Tensor, T_
             _native.ptr(T_c), V, H, W, float(lo), float(hi), _native.ptr(ws), ws_bytes, _native.ptr(out.depth),
             _native.ptr(out.face), _native.ptr(out.weights), _native.ptr(out.normals), _native.ptr(out.colors),
             _native.ptr(out.clipped), _native.stream()), "mvsn_mesh_render")
+    return out
+
+
+# ---- a smaller mesh: vertex clustering with quadric placement ----------------------------------
+SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}
+SIMPLIFY_LAMBDA = 2.0 ** -10         # the quadric's pull towards the mean, per incidence
+MESH_SIMPLIFY_STATUS_TABLE = 1
+
+
+class SimplifiedMesh(NamedTuple):
+    vertices: torch.Tensor            # (M',3) fp32
+    faces: torch.Tensor               # (F',3) int64, rows of `vertices`, winding of the input face kept
+    normals: Optional[torch.Tensor]   # (M',3) fp32 or None
+    colors: Optional[torch.Tensor]    # (M',3) uint8 or None
+    count: torch.Tensor               # (M',) int32: input vertices merged into this one
+    first: torch.Tensor               # (M',) int64: lowest input vertex row of the cluster, strictly ascending
+    inverse: torch.Tensor             # (M,) int64: output row of every input vertex, -1 = none
+    face_rows: torch.Tensor           # (F',) int64: input row of every output face, strictly ascending
+
+
+def mesh_simplify(vertices: torch.Tensor, faces: torch.Tensor, voxel_size: float, *, origin=(0.0, 0.0, 0.0),
+                  placement: str = "quadric", normals: Optional[torch.Tensor] = None,
+                  colors: Optional[torch.Tensor] = None, drop_unreferenced: bool = True) -> SimplifiedMesh:
+    """The mesh ``vertices`` (M,3) fp32, ``faces`` (F,3) int64 simplified by vertex clustering on the grid
+    (``voxel_size``, ``origin``): the decimation step between ``filter_mesh`` and ``mesh_sample`` / ``mesh_render`` /
+    ``write_ply`` (csrc/mvsn_mesh_simplify.hip).
+
+    Two vertices become one output vertex exactly when ``fusion.voxel_merge`` puts them into one voxel: the cells are
+    its cells, step for step.  A vertex with a non-finite coordinate is dropped (``inverse`` -1); a finite vertex 2^20
+    cells or more from the origin raises ValueError.  Output vertices are ordered by ``first``, the lowest input row of
+    their cluster.  A face is remapped through the clustering and dropped when a corner lies outside [0, M), a corner
+    is a dropped vertex, or two of its remapped corners are equal.  Of the survivors, faces whose remapped triples are
+    equal up to rotation are one face, and the one with the lowest input row stays; the opposite winding of the same
+    three rows is a different face and is kept (a two-sided sheet stays two-sided).  Output faces keep the input order
+    and their own corner order, renumbered to output rows; ``face_rows`` names their input rows.  With
+    ``drop_unreferenced`` a cluster no surviving face uses is not output and its members' ``inverse`` is -1; without it
+    every cluster is output and, for ``placement="mean"``, ``vertices``, ``colors``, ``count``, ``first`` and
+    ``inverse`` are ``voxel_merge``'s bit for bit (wherever its mean lies in its own cell, below).
+
+    ``placement="mean"`` puts the vertex at ``voxel_merge``'s mean.  ``placement="quadric"`` puts it at the point that
+    minimises the summed squared distance to the planes of the input faces around the cluster's members, in cell-local
+    voxel units: per (face, corner) incidence the unit normal n (fp64) and d = -n.u give n n^T, d n and 1, each
+    quantised to 2^-30 and summed as integers; ``(A + lambda k I) x = -b + lambda k u_mean`` with lambda = 2^-10 is
+    solved in fp64 by the closed-form inverse, x is clamped to the cell and rounded to fp32 once.  A face without area,
+    with a non-finite corner or a corner out of range adds nothing; a cluster without incidences sits at its mean.
+    Whatever the placement, the output vertex lies in its cluster's cell by the grid's own fp32 arithmetic: where the
+    rounded position does not, the cluster's ``first`` member's position is taken instead.  So every vertex moves by
+    less than the cell's diagonal, and simplifying the result again on the same grid changes neither M' nor F'.
+
+    ``normals`` (M,3) fp32 give per output vertex the direction of ``voxel_normals``' integer sum over the members,
+    (0,0,0) where it is zero; ``colors`` (M,3) uint8 give ``voxel_merge``'s integer mean.  Clustering can create
+    non-manifold edges; ``mesh_components`` and ``filter_mesh`` take the result as any mesh.
+
+    Every output is a bitwise-reproducible function of the inputs, and the vertex outputs do not depend on the order of
+    the faces.  M = 0, or F = 0 with ``drop_unreferenced``, gives empties without a launch.  Everything is validated
+    here, before any launch; there are two host reads, (clusters, status) and (M', F', status), to size the outputs."""
+    from .fusion import VOXEL_CELL_LIMIT, VOXEL_STATUS_RANGE, _origin_f32, _positive_f32
+    m, f, dev = _check_surface(vertices, faces)
+    if not isinstance(placement, str) or placement not in SIMPLIFY_PLACEMENTS:
+        raise ValueError(f"placement must be 'mean' or 'quadric', got {placement!r}")
+    for name, t, dtype in (("normals", normals, torch.float32), ("colors", colors, torch.uint8)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (m, 3) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a ({m},3) {dtype} tensor, one row per vertex")
+        if t.device != dev:
+            raise ValueError(f"{name} are on {t.device}, vertices on {dev}")
+    v, inv, _ = _positive_f32(voxel_size, "voxel_size", inverse=True)
+    o = _origin_f32(origin)
+    drop = bool(drop_unreferenced)
+
+    def result(mo, fo):
+        return SimplifiedMesh(torch.empty((mo, 3), dtype=torch.float32, device=dev),
+                              torch.empty((fo, 3), dtype=torch.int64, device=dev),
+                              torch.empty((mo, 3), dtype=torch.float32, device=dev) if normals is not None else None,
+                              torch.empty((mo, 3), dtype=torch.uint8, device=dev) if colors is not None else None,
+                              torch.empty((mo,), dtype=torch.int32, device=dev),
+                              torch.empty((mo,), dtype=torch.int64, device=dev),
+                              torch.empty((m,), dtype=torch.int64, device=dev),
+                              torch.empty((fo,), dtype=torch.int64, device=dev))
+
+    def nothing():
+        out = result(0, 0)
+        out.inverse.fill_(-1)
+        return out
+    if m == 0 or (f == 0 and drop):    # no vertex, or no face to keep one: nothing to launch
+        return nothing()
+    if not vertices.is_cuda:
+        raise RuntimeError("mesh_simplify runs on HIP devices only: make the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    dense = lambda t: t.detach().contiguous() if t is not None else None   # noqa: E731
+    v_c, f_c, nor_c, col_c = dense(vertices), dense(faces), dense(normals), dense(colors)
+    scalars = (float(v), float(inv), float(o[0]), float(o[1]), float(o[2]))
+    ws_bytes = lib.mvsn_mesh_simplify_workspace_bytes(m, f)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_mesh_simplify_assign(_native.ptr(v_c), m, *scalars, _native.ptr(head), _native.ptr(ws),
+                                                    ws_bytes, st), "mvsn_mesh_simplify_assign")
+        clusters, status = head[:2].tolist()   # the first host read: the clusters, with the status word
+        if status & VOXEL_STATUS_RANGE:
+            raise ValueError(f"voxel_size too small for the mesh's extent: a vertex lies 2^20 = {VOXEL_CELL_LIMIT} "
+                             f"cells of {float(v):g} or more from the origin {tuple(float(x) for x in o)}")
+        if status:
+            raise RuntimeError(f"mesh_simplify: the hash grid overflowed (status {status})")
+        if clusters == 0:              # every vertex dropped
+            return nothing()
+        _native.check(lib.mvsn_mesh_simplify_mark(
+            _native.ptr(v_c), _native.ptr(nor_c), _native.ptr(col_c), m, _native.ptr(f_c) if f else None, f, *scalars,
+            SIMPLIFY_PLACEMENTS[placement], int(drop), clusters, _native.ptr(head), _native.ptr(ws), ws_bytes, st),
+            "mvsn_mesh_simplify_mark")
+        mo, fo, status, _ = head.tolist()      # the second host read: sizes the outputs
+        if status:
+            raise RuntimeError(f"mesh_simplify: the face set overflowed (status {status})")
+        out = result(mo, fo)
+        _native.check(lib.mvsn_mesh_simplify_emit(
+            _native.ptr(f_c) if f else None, m, f, clusters, _native.ptr(ws), ws_bytes, mo, fo,
+            _native.ptr(out.vertices) if mo else None, _native.ptr(out.faces) if fo else None,
+            _native.ptr(out.normals) if mo else None, _native.ptr(out.colors) if mo else None,
+            _native.ptr(out.count) if mo else None, _native.ptr(out.first) if mo else None, _native.ptr(out.inverse),
+            _native.ptr(out.face_rows) if fo else None, st), "mvsn_mesh_simplify_emit")
     return out

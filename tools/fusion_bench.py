@@ -89,7 +89,13 @@ dist2 bits or face differ, and the scores next to cloud_metrics of the vertices.
 reports, as "mesh_render", M, F, ms per call with and without the normal and colour gathers, ms of fusion.cloud_render of
 the vertices and its share of pixels hit (for scale: the holes a vertex render leaves), the share of pixels hit, the sum
 of clipped, and against TSDFVolume.raycast at the same poses the share of pixels both hit and the median and the 99th
-percentile of |depth - raycast depth| over them, in voxels."""
+percentile of |depth - raycast depth| over them, in voxels.
+--simplify: also simplifies the mesh of each scene's --tsdf volume (mesh.mesh_simplify on the volume's own grid, at
+SIMPLIFY_VOXELS volume voxels per cell, both placements, normals and colours carried) and reports, as "simplify", per
+cell size and placement M and F before and after, ms per call, the positions that fell back to a member's, and the
+one-sided distance of MESH_SAMPLES mesh_sample points of the simplified mesh to the original surface by mesh_nearest
+(mean and maximum, in volume voxels), next to the same clustering composed from torch ops (voxel_merge, an index through
+its inverse, torch.unique over the canonical triples, a renumbering) with its ms and whether it keeps as many faces."""
 import argparse
 import json
 import os
@@ -105,7 +111,7 @@ from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_render, cloud_visibility, cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
-from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_render, mesh_sample  # noqa: E402
+from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_render, mesh_sample, mesh_simplify  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics, mesh_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
@@ -1135,8 +1141,83 @@ def run_mesh_render(sc, steps, warmup):
         if diff.numel() else 0.0}}
 
 
+SIMPLIFY_VOXELS = (1, 2, 4)         # cell sizes of --simplify, in volume voxels
+
+
+def torch_mesh_simplify(v, f, voxel, origin):
+    """The clustering from torch ops: voxel_merge for the vertex side (the mean), the faces through its inverse, the
+    collapsed ones masked out, torch.unique over the canonical triples (which sorts them: the faces come out in triple
+    order, not in input order, and without their input rows), the used clusters renumbered."""
+    vc = voxel_merge(v, voxel, origin=origin)
+    g = vc.inverse[f]
+    g = g[(g[:, 0] != g[:, 1]) & (g[:, 1] != g[:, 2]) & (g[:, 0] != g[:, 2]) & (g >= 0).all(dim=1)]
+    k = g.argmin(dim=1, keepdim=True)
+    canon = torch.cat([g.gather(1, k), g.gather(1, (k + 1) % 3), g.gather(1, (k + 2) % 3)], dim=1)
+    faces = torch.unique(canon, dim=0)
+    used = torch.zeros(vc.points.shape[0], dtype=torch.bool, device=v.device)
+    used[faces.reshape(-1)] = True
+    row = torch.cumsum(used, 0) - 1
+    return vc.points[used], row[faces]
+
+
+def simplify_fallbacks(v, f, size, origin, placement):
+    """The fourth result word of mvsn_mesh_simplify_mark: the clusters whose position fell back to a member's."""
+    lib, m, nf = _native.load(), int(v.shape[0]), int(f.shape[0])
+    s = np.float32(size)
+    scalars = (float(s), float(np.float32(1) / s)) + tuple(float(np.float32(x)) for x in origin)
+    ws_bytes = lib.mvsn_mesh_simplify_workspace_bytes(m, nf)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device)
+    head = torch.empty(4, dtype=torch.int64, device=v.device)
+    _native.check(lib.mvsn_mesh_simplify_assign(_native.ptr(v), m, *scalars, _native.ptr(head), _native.ptr(ws), ws_bytes,
+                                                _native.stream()), "mvsn_mesh_simplify_assign")
+    clusters = int(head[0])
+    _native.check(lib.mvsn_mesh_simplify_mark(_native.ptr(v), None, None, m, _native.ptr(f), nf, *scalars,
+                                              {"mean": 0, "quadric": 1}[placement], 1, clusters, _native.ptr(head),
+                                              _native.ptr(ws), ws_bytes, _native.stream()), "mvsn_mesh_simplify_mark")
+    return int(head[3])
+
+
+def run_simplify(sc, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, 4 * TSDF_VOXEL, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    mesh = vol.extract_mesh()
+    v, f = mesh.vertices, mesh.faces
+    m, nf = int(v.shape[0]), int(f.shape[0])
+    lib = _native.load()
+    out = {"M": m, "F": nf, "samples": MESH_SAMPLES, "workspace_bytes": int(lib.mvsn_mesh_simplify_workspace_bytes(m, nf))}
+    for cells in SIMPLIFY_VOXELS:
+        size = cells * TSDF_VOXEL
+        diagonal = float(np.sqrt(3.0) * size)
+        row = {}
+        for placement in ("mean", "quadric"):
+            call = lambda: mesh_simplify(v, f, size, origin=TSDF_ORIGIN, placement=placement, normals=mesh.normals,  # noqa: E731
+                                         colors=mesh.colors)
+            small, times = timed(call, steps, warmup)
+            bare, btimes = timed(lambda: mesh_simplify(v, f, size, origin=TSDF_ORIGIN, placement=placement), steps, warmup)
+            pts = mesh_sample(small.vertices, small.faces, MESH_SAMPLES, seed=1).points
+            near = mesh_nearest(pts, v, f, diagonal)
+            d = near.dist2[torch.isfinite(near.dist2)].double().sqrt() / TSDF_VOXEL
+            row[placement] = {"M_out": int(small.vertices.shape[0]), "F_out": int(small.faces.shape[0]),
+                              "ms_per_call_mean": float(np.mean(times)), "ms_per_call_min": float(np.min(times)),
+                              "without_attributes_ms_per_call_mean": float(np.mean(btimes)),
+                              "same_mesh_without_attributes": bool(torch.equal(bare.vertices, small.vertices) and
+                                                                   torch.equal(bare.faces, small.faces)),
+                              "fallbacks": simplify_fallbacks(v, f, size, TSDF_ORIGIN, placement),
+                              "samples_within_the_cell_diagonal": float(torch.isfinite(near.dist2).float().mean()),
+                              "distance_voxels_mean": float(d.mean()), "distance_voxels_max": float(d.max())}
+        (tv, tf), ttimes = timed(lambda: torch_mesh_simplify(v, f, size, TSDF_ORIGIN), steps, warmup)
+        row["torch"] = {"M_out": int(tv.shape[0]), "F_out": int(tf.shape[0]), "ms_per_call_mean": float(np.mean(ttimes)),
+                        "ms_per_call_min": float(np.min(ttimes)),
+                        "same_counts_as_mean": bool(tv.shape[0] == row["mean"]["M_out"] and tf.shape[0] == row["mean"]["F_out"])}
+        row["device_call_beats_torch"] = bool(row["mean"]["without_attributes_ms_per_call_mean"] < row["torch"]["ms_per_call_mean"])
+        out["cells_%d" % cells] = row
+    return {"simplify": out}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
-        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False, mesh_render_too=False):
+        align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False, mesh_render_too=False,
+        simplify_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -1165,7 +1246,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     drawn = run_render(sc, res, steps, warmup) if render else {}
     mesh_scored = run_mesh_metrics(sc, res, steps, warmup) if mesh_metrics_too else {}
     rasterised = run_mesh_render(sc, steps, warmup) if mesh_render_too else {}
-    return {**rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    simplified = run_simplify(sc, steps, warmup) if simplify_too else {}
+    return {**simplified, **rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -1212,12 +1294,15 @@ def main():
     ap.add_argument("--mesh-render", action="store_true",
                     help="also render the volume's mesh into the input views (mesh_render, with and without gathers), next "
                          "to cloud_render of its vertices, and compare the depth with the volume's raycast")
+    ap.add_argument("--simplify", action="store_true",
+                    help="also simplify the volume's mesh (mesh_simplify at 1, 2 and 4 voxels per cell, both placements), "
+                         "measure how far the result is from the original surface, and the torch form of the clustering")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
-                             a.render, a.mesh_metrics, a.mesh_render)), flush=True)
+                             a.render, a.mesh_metrics, a.mesh_render, a.simplify)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
