@@ -551,7 +551,10 @@ int mvsn_depth_metrics(const float *idepth_est, const float *depth_true, const f
  * Depth-map fusion: the geometric-consistency filter that follows the network in an MVS pipeline, and the
  * back-projection of the kept pixels into one world-space point cloud (multi_view_stereonet_amd/fusion.py; the
  * semantics are DESIGN.md section 10).  Not part of the reference, which stops at the depth maps.
- *   depth (V,rows,cols) in world units, <= 0 = no depth   valid (V,rows,cols) u8 or NULL (every depth > 0 valid)
+ *   depth (V,rows,cols) in world units, <= 0 or NaN = no depth, as a candidate and as a tap.  +inf passes "> 0": as a
+ *   candidate it can never be confirmed (kept, as inf, only with min_consistent = 0; its point is not finite), as a tap
+ *   it makes its slot inconsistent for every pixel whose tap set holds it; a denormal is a depth like any other
+ *   valid (V,rows,cols) u8 or NULL (every depth > 0 valid); any non-zero byte is "valid"
  *   K (V,4,4): the top-left 3x3 is used, its bottom row must be (0,0,1) (not checked)   T_cam_in_world (V,4,4)
  *   ref_views (R) int32, neighbours (R,n_slots) int32 view indices or -1 (skip), 1 <= n_slots <= 32; both on the
  *   device and validated by the caller (out-of-range entries are skipped, never dereferenced)

@@ -135,9 +135,13 @@ def fuse_depthmaps(depth: torch.Tensor, K: torch.Tensor, T_cam_in_world: torch.T
     ``neighbours`` is a host (R,M) integer array, 1 <= M <= 32: row i lists the views that check ``ref_views[i]``
     (default ``range(V)``), -1 skips a slot.  A pixel of a reference view is kept when at least ``min_consistent``
     neighbours confirm it (reprojection error < ``max_reproj_px`` pixels and relative depth difference <
-    ``max_rel_depth``).  Points come ordered by position in ``ref_views``, then row-major pixel.  Everything is validated
-    here, before any launch; the one host synchronisation is the read of the number of kept pixels (to size the
-    outputs).
+    ``max_rel_depth``, both strictly).  A depth that is <= 0 or NaN is no depth, as a candidate and under a neighbour's
+    bilinear taps, where it fails the slot.  ``+inf`` passes "> 0": as a candidate it can never be confirmed, so it is
+    kept (as ``inf``, with a point that is not finite) only with ``min_consistent=0``; as a tap it makes its slot
+    inconsistent for every pixel whose four taps hold it.  No such value changes any other pixel.  In a uint8 ``valid``
+    every non-zero byte is "valid".  Points come ordered by position in ``ref_views``, then row-major pixel.  Everything
+    is validated here, before any launch; the one host synchronisation is the read of the number of kept pixels (to
+    size the outputs).
 
     ``confidence`` (V,1,H,W) fp32 with ``min_confidence``: the call is this function with ``valid`` and-ed with
     ``confidence >= min_confidence`` (formed on the device; a pixel at the threshold is kept, a NaN confidence is not).

@@ -1,11 +1,14 @@
 """Depth-map fusion on the device (csrc/mvsn_fusion.hip) against the float64 restatement (tests/fusion_reference.py),
-and reconstruct() against its own composition."""
+and reconstruct() against its own composition.  The scenes also go through the C ABI with their inputs in poisoned
+buffers and the workspace and every output between guard bands (`device_fuse`, `fuse_between_bands`); the exact
+scenes, the planted values and mvsn_fusion_gather are in tests/test_fusion_entries_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
 from fusion_reference import fuse_reference, nearest_neighbours
-from multi_view_stereonet_amd import synthetic
+from guarded_alloc import POISON_FINITE, POISON_NAN, Guard, bits_equal
+from multi_view_stereonet_amd import _native, synthetic
 from multi_view_stereonet_amd.fusion import FusionResult, frame_pair_poses, fuse_depthmaps, reconstruct
 
 pytestmark = pytest.mark.gpu
@@ -44,12 +47,78 @@ def _compare(got: FusionResult, ref, images, T_cam_in_world, views, max_margin):
     # within 1e-5 of the point's distance from its camera (= depth times the ray's length: the fused depth's 1e-5)
     centres = np.stack([cam[:3, 3] for cam in T_cam_in_world.double().numpy()])[ref["view"][ir]]
     err = np.linalg.norm(pts - ref["points"][ir], axis=1) / np.linalg.norm(ref["points"][ir] - centres, axis=1)
+    print(f"fusion against the restatement: {len(shared)} shared points, {int(margin.sum())} margin pixels of "
+          f"{margin.size}, {int(diff.sum())} counts differ, fused depth error / 1e-5 max {rel.max() / 1e-5:.3f}, "
+          f"point error / 1e-5 max {err.max() / 1e-5:.3f}")
     assert err.max() < 1e-5, err.max()
     if images is not None:
         np.testing.assert_array_equal(got.colors.cpu().numpy()[ig], ref["colors"][ir])
     else:
         assert got.colors is None
     return len(shared)
+
+
+def _alloc(shape, dtype, device):
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def device_fuse(depth, K, T_cam_in_world, neighbours, *, images=None, valid=None, ref_views=None, max_reproj_px=1.0,
+                max_rel_depth=0.01, min_consistent=2, fill=POISON_NAN):
+    """mvsn_fusion_consistency then mvsn_fusion_emit through the C ABI: every input in a poisoned buffer of its own
+    (16-byte aligned only), the workspace, `total` and every output carved between guard bands, the bands checked after
+    the emit.  Arguments as fuse_depthmaps' (tensors or arrays, on the host); a FusionResult of device tensors."""
+    depth = torch.as_tensor(depth)
+    V, _, H, W = depth.shape
+    nb = np.asarray(neighbours, np.int64)
+    R, M = nb.shape
+    refs = np.arange(V) if ref_views is None else np.asarray(ref_views, np.int64)
+    assert refs.shape == (R,) and 1 <= M <= 32 and ((0 <= refs) & (refs < V)).all() and ((-1 <= nb) & (nb < V)).all()
+    guard = Guard(_alloc, fill)
+    put = lambda a, dtype: guard.poisoned(torch.as_tensor(a).to(dtype).contiguous().to(DEV))   # noqa: E731
+    d, k, t = put(depth, torch.float32), put(K, torch.float32), put(T_cam_in_world, torch.float32)
+    m = put(valid, torch.uint8) if valid is not None else None
+    im = put(images, torch.float32) if images is not None else None
+    rv, nbd = put(refs, torch.int32), put(nb, torch.int32)
+    lib = _native.load()
+    ws_bytes = lib.mvsn_fusion_workspace_bytes(R, M, H, W)
+    assert ws_bytes > 0
+    ws = guard.empty((ws_bytes,), torch.uint8, DEV)
+    fused, count = guard.empty((R, 1, H, W), torch.float32, DEV), guard.empty((R, 1, H, W), torch.uint8, DEV)
+    total = guard.empty((1,), torch.int64, DEV)
+    with torch.cuda.device(DEV):
+        st = _native.stream()
+        _native.check(lib.mvsn_fusion_consistency(
+            _native.ptr(d), _native.ptr(m), _native.ptr(k), _native.ptr(t), _native.ptr(rv), _native.ptr(nbd), V, R, M, H,
+            W, float(max_reproj_px), float(max_rel_depth), int(min_consistent), _native.ptr(fused), _native.ptr(count),
+            _native.ptr(total), _native.ptr(ws), ws_bytes, st), "mvsn_fusion_consistency")
+        n = int(total.item())
+        assert 0 <= n <= R * H * W, n
+        points = guard.empty((n, 3), torch.float32, DEV)
+        colors = guard.empty((n, 3), torch.uint8, DEV) if images is not None else None
+        view, pixel = guard.empty((n,), torch.int32, DEV), guard.empty((n,), torch.int32, DEV)
+        _native.check(lib.mvsn_fusion_emit(
+            _native.ptr(fused), _native.ptr(im), _native.ptr(rv), R, H, W, M, _native.ptr(ws), ws_bytes, n,
+            _native.ptr(points), _native.ptr(colors), _native.ptr(view), _native.ptr(pixel), st), "mvsn_fusion_emit")
+    torch.cuda.synchronize()
+    guard.check()
+    return FusionResult(points, colors, view, pixel, fused, count)
+
+
+def same_bits(a: FusionResult, b: FusionResult):
+    for name, x, y in zip(FusionResult._fields, a, b):
+        assert (x is None and y is None) or bits_equal(x, y), name
+
+
+def fuse_between_bands(*args, **kwargs):
+    """device_fuse under both poisons (an element nobody writes, or a read of foreign memory that reaches a result,
+    differs between them) and the Python entry on the same inputs: one result, the same bits three times."""
+    a = device_fuse(*args, fill=POISON_NAN, **kwargs)
+    same_bits(a, device_fuse(*args, fill=POISON_FINITE, **kwargs))
+    dev = lambda x: None if x is None else torch.as_tensor(x).to(DEV)   # noqa: E731
+    depth, K, T, nb = args
+    py = {k: (dev(v) if k in ("images", "valid") else v) for k, v in kwargs.items()}
+    same_bits(a, fuse_depthmaps(dev(depth).float(), dev(K).float(), dev(T).float(), nb, **py))
+    return a
 
 
 def test_fusion_matches_the_restatement_on_the_analytic_scene():
@@ -60,6 +129,8 @@ def test_fusion_matches_the_restatement_on_the_analytic_scene():
                          images=sc["images"].to(DEV))
     # (59 margin pixels of 73728 here: projections within 1e-4 * u of an integer column next to the image edge)
     assert _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3) > 0.8 * 6 * 96 * 128
+    banded = fuse_between_bands(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    _compare(banded, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3)
 
 
 def anisotropic_scene(V=6, H=90, W=150, device="cpu"):
@@ -85,6 +156,8 @@ def test_fusion_with_anisotropic_off_centre_cameras_matches_the_restatement():
     print(f"anisotropic fusion: {shared} shared points, {int(ref['margin'].sum())} margin pixels of {ref['margin'].size}, "
           f"{int((got.count.cpu().numpy() != ref['count']).sum())} counts differ")
     assert shared > 0.6 * 6 * 90 * 150
+    banded = fuse_between_bands(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    _compare(banded, ref, sc["images"], sc["T_cam_in_world"], range(6), 1e-3)
 
 
 def test_fusion_odd_size_padding_valid_mask_and_ref_subset():
@@ -107,6 +180,9 @@ def test_fusion_odd_size_padding_valid_mask_and_ref_subset():
     bare = fuse_depthmaps(depth.to(DEV), sc["K"].to(DEV), sc["T_cam_in_world"].to(DEV), nb, valid=valid.to(DEV),
                           ref_views=refs)
     assert bare.colors is None and torch.equal(bare.points, got.points)
+    for images in (sc["images"], None):
+        banded = fuse_between_bands(depth, sc["K"], sc["T_cam_in_world"], nb, images=images, valid=valid, ref_views=refs)
+        _compare(banded, ref, images, sc["T_cam_in_world"], refs, 0.02)
 
 
 def test_fusion_more_workgroup_counts_than_scan_threads():
@@ -128,6 +204,8 @@ def test_fusion_more_workgroup_counts_than_scan_threads():
     shared = _compare(got, ref, sc["images"], sc["T_cam_in_world"], range(V), 1e-3)
     print(f"1056 counts: {shared} shared points of {got.points.shape[0]}, {int(ref['margin'].sum())} margin pixels")
     assert shared > 0.8 * V * H * W
+    banded = fuse_between_bands(sc["depth"], sc["K"], sc["T_cam_in_world"], nb, images=sc["images"])
+    _compare(banded, ref, sc["images"], sc["T_cam_in_world"], range(V), 1e-3)
 
 
 def test_fusion_is_deterministic():

@@ -100,12 +100,17 @@ def test_empty_cloud_on_the_device():
     assert vc.points.device.type == "cuda"
 
 
-def test_many_voxels_uniform_random():
-    # 20 000 points in 400^3 cells: nearly every point its own voxel, so the table (65 536 slots) takes ~20 000 keys:
-    # collisions, probe sequences, and sequences that run over the table's end
+def _uniform_cloud():
     rng = np.random.default_rng(3)
     pts = rng.uniform(-2.0, 2.0, (20000, 3)).astype(np.float32)
     cols = rng.integers(0, 256, (20000, 3)).astype(np.uint8)
+    return pts, cols
+
+
+def test_many_voxels_uniform_random():
+    # 20 000 points in 400^3 cells: nearly every point its own voxel, so the table (65 536 slots) takes ~20 000 keys:
+    # collisions, probe sequences, and sequences that run over the table's end
+    pts, cols = _uniform_cloud()
     ref = voxel_reference(pts, 0.01, colors=cols)
     assert len(ref["first"]) > 0.99 * 20000
     _check(_merge(pts, 0.01, cols), ref)
@@ -123,23 +128,33 @@ def test_more_workgroup_counts_than_scan_threads():
     _check(_merge(pts, 0.05, cols), ref)
 
 
-def test_many_voxels_on_a_line_of_consecutive_cells():
-    # clustered keys: 4096 consecutive cells along x (then along z: the key's low bits), one point each, shuffled
+def _line_cloud(axis):
     rng = np.random.default_rng(4)
     k = rng.permutation(4096).astype(np.float32) - 2048.0
+    pts = np.full((4096, 3), 0.05, np.float32)
+    pts[:, axis] = (k + np.float32(0.5)) * np.float32(0.1)
+    return pts
+
+
+def test_many_voxels_on_a_line_of_consecutive_cells():
+    # clustered keys: 4096 consecutive cells along x (then along z: the key's low bits), one point each, shuffled
     for axis in (0, 2):
-        pts = np.full((4096, 3), 0.05, np.float32)
-        pts[:, axis] = (k + np.float32(0.5)) * np.float32(0.1)
+        pts = _line_cloud(axis)
         ref = voxel_reference(pts, 0.1)
         assert len(ref["first"]) == 4096
         _check(_merge(pts, 0.1), ref)
 
 
-def test_one_voxel_5000_points():
-    # maximal contention: every point adds into one accumulator row
+def _one_voxel_cloud():
     rng = np.random.default_rng(5)
     pts = (rng.uniform(0.0, 1.0, (5000, 3)) * 0.999 + np.array([4.0, -7.0, 1.0])).astype(np.float32)
     cols = rng.integers(0, 256, (5000, 3)).astype(np.uint8)
+    return pts, cols
+
+
+def test_one_voxel_5000_points():
+    # maximal contention: every point adds into one accumulator row
+    pts, cols = _one_voxel_cloud()
     ref = voxel_reference(pts, 1.0, colors=cols)
     assert ref["count"].tolist() == [5000]
     got = _merge(pts, 1.0, cols)
@@ -148,7 +163,7 @@ def test_one_voxel_5000_points():
     _check(got, ref)
 
 
-def test_dropped_points():
+def _dropped_cloud():
     rng = np.random.default_rng(6)
     clean = rng.uniform(-1.0, 1.0, (3000, 3)).astype(np.float32)
     cols = rng.integers(0, 256, (3000, 3)).astype(np.uint8)
@@ -159,6 +174,11 @@ def test_dropped_points():
     for j, i in enumerate(bad):
         pts[i, j % 3] = values[(j // 3) % 3]
     pts[bad[5]] = np.nan                                                # a whole row
+    return pts, cols, clean, bad
+
+
+def test_dropped_points():
+    pts, cols, clean, bad = _dropped_cloud()
     got = _merge(pts, 0.2, cols)
     _check(got, voxel_reference(pts, 0.2, colors=cols))
     inverse = got.inverse.cpu().numpy()
