@@ -1247,6 +1247,65 @@ int mvsn_mesh_simplify_emit(const int64_t *faces, long n_vertices, long n_faces,
                             int64_t *out_faces, float *out_normals, uint8_t *out_colors, int *count, int64_t *first,
                             int64_t *inverse, int64_t *face_rows, mvsn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The unique edges of a mesh, smoothing over them, and normals (multi_view_stereonet_amd/mesh.py: mesh_edges,
+ * mesh_smooth, mesh_normals; the semantics and every operation are DESIGN.md section 29; csrc/mvsn_mesh_edges.hip,
+ * csrc/mvsn_mesh_smooth.hip).
+ *
+ * Edges.  Side s of face r = (v0, v1, v2) runs from v_s to v_(s+1)%3 and has the index 3 r + s.  A face with an index
+ * outside [0, n_vertices) takes no part, nor does a side with equal ends.  An edge is the unordered pair of a side's ends.
+ *   faces (n_faces,3) int64; 1 <= n_vertices <= 2^31 - 1, 1 <= n_faces <= (2^31 - 1) / 3 (a side index is an int32)
+ *   workspace: mvsn_mesh_edges_workspace_bytes(n_vertices, n_faces) bytes (0 for sizes the entries refuse), 16-byte
+ *   aligned, handed from mark to emit unchanged: 24 bytes per slot of the edge table (a power of two >= 6 n_faces
+ *   slots, 1024 at least) and 12 bytes per face.
+ * mvsn_mesh_edges_mark: every side into the set of packed keys (low << 32) | high; beside the slot the minimum side
+ *   index, the count and the winding sum.
+ *   -> result (2 int64): [0] the number of edges E, [1] status bits (MVSN_MESH_EDGES_STATUS_*).  The one host read.
+ * mvsn_mesh_edges_emit: n_edges = E as read back.
+ *   -> edges (E,2) int64 (low, high), in order of first  first (E) int64: the lowest side index that carries the edge
+ *      face_count (E) int32: the sides that carry it  winding (E) int32: sides low -> high minus sides high -> low
+ *      face_edge (n_faces,3) int64: the edge row of every side, -1 for a side that takes no part
+ *      vertex_degree (n_vertices) int32: distinct edges at the vertex
+ *      vertex_boundary (n_vertices) u8: 1 where the vertex lies on an edge with face_count 1, else 0
+ *
+ * mvsn_mesh_smooth: `iterations` steps x <- x + lam L(x) (method 0, laplacian) or pairs of steps with lam, then mu
+ * (method 1, taubin), L the uniform Laplacian over `edges` (n_edges,2) int64, in fp64 working positions.  0 < lam <= 1,
+ * -2 <= mu < 0, 0 <= iterations <= 10000.  pinned (n_vertices) u8 or NULL: non-zero = the vertex keeps its bits; a
+ * vertex with a non-finite coordinate keeps its bits too and its edges contribute to neither end, as do edges with an
+ * end outside [0, n_vertices) or with equal ends.  The degree of a vertex is the number of its contributing edges.
+ * With span = the largest per-axis extent of the finite vertices = m 2^k, m in [0.5, 1): per edge (a, b) and axis
+ * q = rint((x_b - x_a) 2^(30-k)) clamped to +-2^31 goes with 64-bit integer atomics into a's sum and, negated, b's;
+ * per free vertex with a degree mean = ((double)sum 2^(k-30)) / (double)degree, x = x + f mean.  Without a finite
+ * vertex, or with span 0, out_vertices is the input's bits.  No host read; the steps are launched back to back.
+ *   workspace: mvsn_mesh_smooth_workspace_bytes(n_vertices) bytes, 16-byte aligned: 56 bytes per vertex.
+ *   -> out_vertices (n_vertices,3) fp32: (float)x, rounded once
+ *
+ * mvsn_mesh_normals: per face c = (p1 - p0) x (p2 - p0) in fp64 with the lowest row rotated to the front,
+ * face_normals = c / |c| and face_area = |c| / 2, zeros for a face with a corner outside [0, n_vertices), a non-finite
+ * corner or no area.  Per vertex the direction of the sum of c over its valid faces, summed as integers: with the
+ * vertex's largest |component of c| = m 2^e, every face adds rint(c 2^(31-e)); zeros where the sum is zero.
+ *   workspace: mvsn_mesh_normals_workspace_bytes(n_vertices) bytes, 16-byte aligned: 32 bytes per vertex.
+ *   -> face_normals (n_faces,3) fp32  face_area (n_faces) fp32  vertex_normals (n_vertices,3) fp32
+ * Integer atomics only (compare-and-swap on an empty slot, minima, maxima, sums): every output is a deterministic
+ * function of the inputs, whatever the order of arrival.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSN_MESH_EDGES_STATUS_TABLE 1      /* a probe sequence of the edge set visited every slot without finding room
+                                               (cannot happen: the table holds at least 3 n_faces slots) */
+size_t mvsn_mesh_edges_workspace_bytes(long n_vertices, long n_faces);
+int mvsn_mesh_edges_mark(const int64_t *faces, long n_vertices, long n_faces, int64_t *result, void *workspace,
+                         size_t workspace_bytes, mvsn_stream_t stream);
+int mvsn_mesh_edges_emit(long n_vertices, long n_faces, void *workspace, size_t workspace_bytes, long n_edges,
+                         int64_t *edges, int64_t *first, int *face_count, int *winding, int64_t *face_edge,
+                         int *vertex_degree, uint8_t *vertex_boundary, mvsn_stream_t stream);
+size_t mvsn_mesh_smooth_workspace_bytes(long n_vertices);
+int mvsn_mesh_smooth(const float *vertices, long n_vertices, const int64_t *edges, long n_edges, const uint8_t *pinned,
+                     int method, long iterations, double lam, double mu, void *workspace, size_t workspace_bytes,
+                     float *out_vertices, mvsn_stream_t stream);
+size_t mvsn_mesh_normals_workspace_bytes(long n_vertices);
+int mvsn_mesh_normals(const float *vertices, long n_vertices, const int64_t *faces, long n_faces, void *workspace,
+                      size_t workspace_bytes, float *face_normals, float *face_area, float *vertex_normals,
+                      mvsn_stream_t stream);
+
 /* Tensor plumbing of the forward as library calls (so that a whole forward is a replayable list of C calls and nothing
  * else): a device-to-device copy on the stream (the torch.cat / repeat of poses, intrinsics and coarse source images,
  * multi_view_stereonet.py:553,:587-592) and dst[i] = src[i * stride] (the focal lengths K[:, 0, 0], :607). */

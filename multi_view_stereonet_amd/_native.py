@@ -186,6 +186,14 @@ SIGNATURES = {
                                 [c_int, c_int, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_mesh_simplify_emit": (c_int, [c_void_p, c_long, c_long, c_long, c_void_p, c_size_t, c_long, c_long] +
                                 [c_void_p] * 8 + [c_void_p]),
+    "mvsn_mesh_edges_workspace_bytes": (c_size_t, [c_long] * 2),
+    "mvsn_mesh_edges_mark": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mvsn_mesh_edges_emit": (c_int, [c_long, c_long, c_void_p, c_size_t, c_long] + [c_void_p] * 7 + [c_void_p]),
+    "mvsn_mesh_smooth_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_mesh_smooth": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_long, ctypes.c_double,
+                                 ctypes.c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mvsn_mesh_normals_workspace_bytes": (c_size_t, [c_long]),
+    "mvsn_mesh_normals": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_size_t] + [c_void_p] * 3 + [c_void_p]),
     "mvsn_cloud_cluster_workspace_bytes": (c_size_t, [c_long]),
     "mvsn_cloud_cluster_label": (c_int, [c_void_p, c_long] + [ctypes.c_float] * 2 + [c_long, c_void_p, c_size_t] +
                                  [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),

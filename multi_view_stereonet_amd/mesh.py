@@ -21,6 +21,10 @@ interpolated normals and colours.
 Making a mesh smaller (csrc/mvsn_mesh_simplify.hip): ``mesh_simplify`` clusters the vertices on
 ``fusion.voxel_merge``'s grid, remaps the faces, drops the collapsed and the repeated ones, and places each new vertex
 by the quadric of the faces around it.
+
+Edges, smoothing and normals (csrc/mvsn_mesh_edges.hip, csrc/mvsn_mesh_smooth.hip): ``mesh_edges``
+is the unique edge set with its border, non-manifold and winding flags, ``mesh_smooth`` Taubin or Laplacian smoothing
+over it with integer sums, ``mesh_normals`` the face normals, areas and area-weighted vertex normals of any mesh.
 """
 from typing import NamedTuple, Optional
 
@@ -581,4 +585,200 @@ def mesh_simplify(vertices: torch.Tensor, faces: torch.Tensor, voxel_size: float
             _native.ptr(out.normals) if mo else None, _native.ptr(out.colors) if mo else None,
             _native.ptr(out.count) if mo else None, _native.ptr(out.first) if mo else None, _native.ptr(out.inverse),
             _native.ptr(out.face_rows) if fo else None, st), "mvsn_mesh_simplify_emit")
+    return out
+
+
+MAX_EDGE_FACES = (2 ** 31 - 1) // 3   # a side index 3 r + s is an int32 on the device
+MESH_EDGES_STATUS_TABLE = 1
+SMOOTH_METHODS = {"laplacian": 0, "taubin": 1}
+SMOOTH_MAX_ITERATIONS = 10000
+
+
+class MeshEdges(NamedTuple):
+    edges: torch.Tensor               # (E,2) int64: the distinct unordered pairs, (low, high), in order of `first`
+    first: torch.Tensor               # (E,) int64: the lowest side index 3 r + s that carries the edge, ascending
+    face_count: torch.Tensor          # (E,) int32: sides that carry it: 1 border, 2 manifold interior, > 2 non-manifold
+    winding: torch.Tensor             # (E,) int32: sides low -> high minus sides high -> low
+    face_edge: torch.Tensor           # (F,3) int64: the edge row of every side, -1 for a side that takes no part
+    vertex_degree: torch.Tensor       # (M,) int32: distinct edges at the vertex
+    vertex_boundary: torch.Tensor     # (M,) bool: the vertex lies on an edge with face_count 1
+
+
+class SmoothedMesh(NamedTuple):
+    vertices: torch.Tensor            # (M,3) fp32
+    edges: MeshEdges                  # of the mesh (the faces are the input's)
+
+
+class MeshNormals(NamedTuple):
+    face_normals: torch.Tensor        # (F,3) fp32 unit normals by the winding, zeros for a face without one
+    face_area: torch.Tensor           # (F,) fp32
+    vertex_normals: torch.Tensor      # (M,3) fp32 area-weighted unit normals, zeros for a vertex without one
+
+
+def mesh_edges(faces: torch.Tensor, num_vertices: int) -> MeshEdges:
+    """The unique edges of the mesh ``faces`` (F,3) int64 over ``num_vertices`` = M vertex rows (DESIGN.md section 29,
+    csrc/mvsn_mesh_edges.hip): what a watertightness check, hole statistics or smoothing with a held border start from.
+
+    Side s of face r = (v0, v1, v2) runs from v_s to v_(s+1)%3 and has the side index 3 r + s.  A face with any index
+    outside [0, M) takes no part; a side with equal ends takes no part while the other sides of its face still do.  An
+    edge is the unordered pair of a side's ends: ``edges`` holds the distinct ones as (low, high), ordered by ``first``,
+    the lowest side index that carries the edge.  ``face_count`` is the number of sides that carry it (1: a border, 2: a
+    manifold interior edge, more: non-manifold; the same face twice counts twice), ``winding`` the sides running
+    low -> high minus those running high -> low (0 on a consistently wound interior edge), ``face_edge`` the edge row of
+    every side (-1 for a side that takes no part), ``vertex_degree`` the number of distinct edges at a vertex and
+    ``vertex_boundary`` whether it lies on an edge with ``face_count`` 1.
+
+    Every output is a bitwise-reproducible function of ``faces``.  F = 0 or M = 0 gives E = 0 without a launch.  At most
+    (2^31 - 1) / 3 faces.  The one host synchronisation is the read of (E, status) that sizes the outputs."""
+    m, f = _check_faces(faces, num_vertices)
+    if f > MAX_EDGE_FACES:
+        raise ValueError(f"at most (2^31 - 1) / 3 = {MAX_EDGE_FACES} faces, got {f}")
+    dev = faces.device
+
+    def result(e):
+        return MeshEdges(torch.empty((e, 2), dtype=torch.int64, device=dev), torch.empty((e,), dtype=torch.int64, device=dev),
+                         torch.empty((e,), dtype=torch.int32, device=dev), torch.empty((e,), dtype=torch.int32, device=dev),
+                         torch.empty((f, 3), dtype=torch.int64, device=dev), torch.empty((m,), dtype=torch.int32, device=dev),
+                         torch.empty((m,), dtype=torch.bool, device=dev))
+    if f == 0 or m == 0:               # no side takes part: nothing to launch
+        out = result(0)
+        out.face_edge.fill_(-1)
+        out.vertex_degree.zero_()
+        out.vertex_boundary.zero_()
+        return out
+    if not faces.is_cuda:
+        raise RuntimeError("mesh_edges runs on HIP devices only: make the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    fc = faces.detach().contiguous()
+    ws_bytes = lib.mvsn_mesh_edges_workspace_bytes(m, f)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    head = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        _native.check(lib.mvsn_mesh_edges_mark(_native.ptr(fc), m, f, _native.ptr(head), _native.ptr(ws), ws_bytes, st),
+                      "mvsn_mesh_edges_mark")
+        e, status = head.tolist()      # the one host synchronisation: sizes the outputs
+        if status != 0 or not 0 <= e <= 3 * f:
+            raise RuntimeError(f"mesh_edges: the edge set overflowed (status {status}, {e} edges of {f} faces)")
+        out = result(e)
+        _native.check(lib.mvsn_mesh_edges_emit(
+            m, f, _native.ptr(ws), ws_bytes, e, _native.ptr(out.edges) if e else None, _native.ptr(out.first) if e else None,
+            _native.ptr(out.face_count) if e else None, _native.ptr(out.winding) if e else None, _native.ptr(out.face_edge),
+            _native.ptr(out.vertex_degree), _native.ptr(out.vertex_boundary), st), "mvsn_mesh_edges_emit")
+    return out
+
+
+def _check_edges(edges, m, f, dev):
+    if not isinstance(edges, tuple) or len(edges) != 7:
+        raise ValueError("edges must be a MeshEdges")
+    e = int(edges[0].shape[0]) if torch.is_tensor(edges[0]) and edges[0].dim() == 2 else -1
+    for name, t, shape, dtype in zip(MeshEdges._fields, edges, ((e, 2), (e,), (e,), (e,), (f, 3), (m,), (m,)),
+                                     (torch.int64, torch.int64, torch.int32, torch.int32, torch.int64, torch.int32,
+                                      torch.bool)):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype:
+            raise ValueError(f"edges.{name} must be a {tuple(max(s, 0) for s in shape)} {dtype} tensor of this mesh")
+        if t.device != dev:
+            raise ValueError(f"edges.{name} is on {t.device}, the mesh on {dev}")
+    return e
+
+
+def _real(value, name, ok, rule):
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not ok(float(value)):
+        raise ValueError(f"{name} must be a number with {rule}, got {value!r}")
+    return float(value)
+
+
+def mesh_smooth(vertices: torch.Tensor, faces: torch.Tensor, iterations: int = 10, *, method: str = "taubin",
+                lam: float = 0.5, mu: float = -0.53, fix_boundary: bool = False, pinned: Optional[torch.Tensor] = None,
+                edges: Optional[MeshEdges] = None) -> SmoothedMesh:
+    """The mesh ``vertices`` (M,3) fp32, ``faces`` (F,3) int64 smoothed with the uniform (umbrella) Laplacian over its
+    unique edges: the step between ``filter_mesh`` and ``mesh_simplify`` that takes the voxel-pitch bumps of depth noise
+    out of an extracted mesh (csrc/mvsn_mesh_smooth.hip).  The faces do not change.
+
+    ``method="laplacian"`` takes ``iterations`` steps x <- x + lam L(x), L(x)_i the mean of x_j - x_i over the edges at
+    i; ``method="taubin"`` takes ``iterations`` pairs of steps, with ``lam`` and then with ``mu`` (Taubin's lambda|mu
+    filter: the second, negative step undoes the shrinkage of the first).  0 < lam <= 1, -2 <= mu < 0,
+    0 <= iterations <= 10000.  ``edges`` takes the ``MeshEdges`` of this mesh to reuse; without it ``mesh_edges`` is
+    called.  A vertex with a non-finite coordinate keeps its bits and its edges contribute to neither end; with
+    ``fix_boundary`` every ``vertex_boundary`` vertex keeps its bits, and ``pinned`` (M,) bool adds the caller's own.  The
+    degree that the mean divides by is the number of the vertex's edges that contribute; a vertex without one stays.
+
+    The working positions are fp64.  With span, the largest per-axis extent of the finite vertices, written m 2^k with
+    m in [0.5, 1), every edge (a, b) adds q = rint((x_b - x_a) 2^(30-k)), clamped to +-2^31, to a's integer sum and -q
+    to b's; a vertex moves by f ((double)sum 2^(k-30)) / (double)degree; at the end the positions are rounded to fp32
+    once.  The sums are integers, so the result is a bitwise-reproducible function of the inputs that does not depend on
+    the order of the faces or of a face's corners.  Without a finite vertex, or with span 0, the result is the input's
+    bits.  The steps are launched back to back: ``mesh_smooth`` itself reads nothing back (``mesh_edges`` reads once).
+    M = 0, E = 0 or ``iterations`` = 0 gives a copy of the vertices without a launch of its own."""
+    m, f, dev = _check_surface(vertices, faces)
+    if not isinstance(method, str) or method not in SMOOTH_METHODS:
+        raise ValueError(f"method must be 'laplacian' or 'taubin', got {method!r}")
+    lam = _real(lam, "lam", lambda x: 0.0 < x <= 1.0, "0 < lam <= 1")
+    mu = _real(mu, "mu", lambda x: -2.0 <= x < 0.0, "-2 <= mu < 0")
+    iterations = _integer(iterations, "iterations", 0, SMOOTH_MAX_ITERATIONS)
+    if not isinstance(fix_boundary, bool):
+        raise ValueError(f"fix_boundary must be a bool, got {fix_boundary!r}")
+    if pinned is not None:
+        if not torch.is_tensor(pinned) or tuple(pinned.shape) != (m,) or pinned.dtype != torch.bool:
+            raise ValueError(f"pinned must be a ({m},) bool tensor, one flag per vertex")
+        if pinned.device != dev:
+            raise ValueError(f"pinned is on {pinned.device}, vertices on {dev}")
+    if edges is not None:
+        _check_edges(edges, m, f, dev)
+    else:
+        edges = mesh_edges(faces, m)
+    e = int(edges.edges.shape[0])
+    if m == 0 or e == 0 or iterations == 0:    # nothing moves: nothing to launch
+        return SmoothedMesh(vertices.detach().clone(memory_format=torch.contiguous_format), edges)
+    if not vertices.is_cuda:
+        raise RuntimeError("mesh_smooth runs on HIP devices only: make the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    held = pinned.detach() if pinned is not None else None
+    if fix_boundary:
+        held = edges.vertex_boundary if held is None else held | edges.vertex_boundary
+    held = held.contiguous() if held is not None else None
+    v_c, e_c = vertices.detach().contiguous(), edges.edges.detach().contiguous()
+    out = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    ws_bytes = lib.mvsn_mesh_smooth_workspace_bytes(m)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_mesh_smooth(_native.ptr(v_c), m, _native.ptr(e_c), e, _native.ptr(held),
+                                           SMOOTH_METHODS[method], iterations, lam, mu, _native.ptr(ws), ws_bytes,
+                                           _native.ptr(out), _native.stream()), "mvsn_mesh_smooth")
+    return SmoothedMesh(out, edges)
+
+
+def mesh_normals(vertices: torch.Tensor, faces: torch.Tensor) -> MeshNormals:
+    """Face normals, face areas and area-weighted vertex normals of the mesh ``vertices`` (M,3) fp32, ``faces`` (F,3)
+    int64: the normals that ``write_ply``, ``mesh_sample`` and ``mesh_render`` take, for a mesh whose own have gone stale
+    (after ``mesh_smooth`` or ``mesh_simplify``) or that never had any (csrc/mvsn_mesh_smooth.hip).
+
+    Per face c = (p1 - p0) x (p2 - p0) in fp64 from the fp32 vertices, with the lowest row rotated to the front so that
+    the bits do not depend on the corner the face starts with: ``face_normals`` = c / |c|, by the winding, and
+    ``face_area`` = |c| / 2, both zeros for a face with an index outside [0, M), a non-finite corner or no area.
+    ``vertex_normals`` is the direction of the sum of c over the valid faces at the vertex, summed as exact integers (c
+    quantised to 2^-31 of the largest component at that vertex), rounded to fp32 once; (0,0,0) where the sum is zero or
+    no valid face uses the vertex.  Bitwise reproducible and independent of the order of the faces.  M = 0 gives zeros
+    without a launch; there is no host read."""
+    m, f, dev = _check_surface(vertices, faces)
+    out = MeshNormals(torch.empty((f, 3), dtype=torch.float32, device=dev), torch.empty((f,), dtype=torch.float32, device=dev),
+                      torch.empty((m, 3), dtype=torch.float32, device=dev))
+    if m == 0:                         # no vertex, no valid face: nothing to launch
+        out.face_normals.zero_()
+        out.face_area.zero_()
+        return out
+    if not vertices.is_cuda:
+        raise RuntimeError("mesh_normals runs on HIP devices only: make the mesh on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    v_c, f_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    ws_bytes = lib.mvsn_mesh_normals_workspace_bytes(m)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(lib.mvsn_mesh_normals(_native.ptr(v_c), m, _native.ptr(f_c) if f else None, f, _native.ptr(ws), ws_bytes,
+                                            _native.ptr(out.face_normals) if f else None,
+                                            _native.ptr(out.face_area) if f else None, _native.ptr(out.vertex_normals),
+                                            _native.stream()), "mvsn_mesh_normals")
     return out

@@ -95,7 +95,13 @@ SIMPLIFY_VOXELS volume voxels per cell, both placements, normals and colours car
 cell size and placement M and F before and after, ms per call, the positions that fell back to a member's, and the
 one-sided distance of MESH_SAMPLES mesh_sample points of the simplified mesh to the original surface by mesh_nearest
 (mean and maximum, in volume voxels), next to the same clustering composed from torch ops (voxel_merge, an index through
-its inverse, torch.unique over the canonical triples, a renumbering) with its ms and whether it keeps as many faces."""
+its inverse, torch.unique over the canonical triples, a renumbering) with its ms and whether it keeps as many faces.
+--smooth: also finds the edges of the mesh of each scene's --tsdf volume (mesh.mesh_edges), smooths it (mesh.mesh_smooth,
+Taubin, SMOOTH_ITERATIONS iterations, the edges reused) and recomputes its normals (mesh.mesh_normals), and reports, as
+"smooth", M, F, E and the border and non-manifold edge counts, ms per mesh_edges, ms per smoothing call and per step
+(a call takes 2 SMOOTH_ITERATIONS steps), ms per mesh_normals, and next to them the same smoothing composed from torch
+ops (torch.unique over the sorted pairs of the sides, then per step index_add_ of the neighbour differences in fp64) with
+its ms for the edges, per call and per step, and how far its vertices are from the device's."""
 import argparse
 import json
 import os
@@ -111,7 +117,7 @@ from multi_view_stereonet_amd import _native, synthetic  # noqa: E402
 from multi_view_stereonet_amd.fusion import (cloud_render, cloud_visibility, cloud_clusters, cloud_knn, cloud_nearest, cloud_normals, cloud_radius_scalars,  # noqa: E402
                                              cloud_fpfh, cloud_ransac, cloud_register_global, feature_nearest,
                                              cloud_register, statistical_outlier_mask, depth_normals, fuse_depthmaps, point_normals, voxel_merge, voxel_normals)
-from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_nearest, mesh_render, mesh_sample, mesh_simplify  # noqa: E402
+from multi_view_stereonet_amd.mesh import filter_mesh, mesh_components, mesh_edges, mesh_nearest, mesh_normals, mesh_render, mesh_sample, mesh_simplify, mesh_smooth  # noqa: E402
 from multi_view_stereonet_amd.metrics import cloud_metrics, mesh_metrics  # noqa: E402
 from multi_view_stereonet_amd.tsdf import TSDFVolume  # noqa: E402
 
@@ -1215,9 +1221,83 @@ def run_simplify(sc, steps, warmup):
     return {"simplify": out}
 
 
+SMOOTH_ITERATIONS = 10               # Taubin iterations of --smooth: 20 steps per call
+
+
+def torch_mesh_edges(f, m):
+    """The distinct unordered pairs of the sides from torch ops: sorted pairs packed into one int64, torch.unique (which
+    sorts them: the edges come out in pair order, without first, counts per side or windings)."""
+    sides = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    sides = sides[((f >= 0) & (f < m)).all(dim=1).repeat(3) & (sides[:, 0] != sides[:, 1])]
+    key = torch.unique((sides.min(dim=1).values << 32) | sides.max(dim=1).values)
+    return torch.stack([key >> 32, key & 0xffffffff], dim=1)
+
+
+def torch_mesh_smooth(v, edges, iterations, lam, mu):
+    """Taubin smoothing over `edges` from torch ops, in fp64 (float sums: the result depends on the order index_add_
+    happens to add in)."""
+    a, b = edges[:, 0], edges[:, 1]
+    x = v.double()
+    degree = torch.zeros(v.shape[0], dtype=torch.float64, device=v.device)
+    degree.index_add_(0, a, torch.ones_like(a, dtype=torch.float64))
+    degree.index_add_(0, b, torch.ones_like(b, dtype=torch.float64))
+    degree = degree.clamp_(min=1.0)[:, None]
+    for _ in range(iterations):
+        for factor in (lam, mu):
+            d = x[b] - x[a]
+            total = torch.zeros_like(x)
+            total.index_add_(0, a, d)
+            total.index_add_(0, b, -d)
+            x = x + factor * (total / degree)
+    return x.float()
+
+
+def run_smooth(sc, steps, warmup):
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, 4 * TSDF_VOXEL, device=depth.device, color=True)
+    vol.integrate(depth, K, T, images=images)
+    mesh = vol.extract_mesh()
+    v, f = mesh.vertices, mesh.faces
+    m, nf = int(v.shape[0]), int(f.shape[0])
+    lib = _native.load()
+    edges, etimes = timed(lambda: mesh_edges(f, m), steps, warmup)
+    smooth, stimes = timed(lambda: mesh_smooth(v, f, SMOOTH_ITERATIONS, edges=edges), steps, warmup)
+    _, wtimes = timed(lambda: mesh_smooth(v, f, SMOOTH_ITERATIONS), steps, warmup)
+    normals, ntimes = timed(lambda: mesh_normals(smooth.vertices, f), steps, warmup)
+    tedges, tetimes = timed(lambda: torch_mesh_edges(f, m), steps, warmup)
+    tsmooth, tstimes = timed(lambda: torch_mesh_smooth(v, tedges, SMOOTH_ITERATIONS, 0.5, -0.53), steps, warmup)
+    finite = torch.isfinite(v).all(dim=1)
+    moved = (smooth.vertices - v)[finite].double().norm(dim=1) / TSDF_VOXEL
+    apart = (smooth.vertices - tsmooth)[finite].double().norm(dim=1) / TSDF_VOXEL
+    outwards = (normals.vertex_normals * mesh.normals).sum(dim=1)
+    n_steps = 2 * SMOOTH_ITERATIONS
+    return {"smooth": {
+        "M": m, "F": nf, "E": int(edges.edges.shape[0]), "iterations": SMOOTH_ITERATIONS, "steps_per_call": n_steps,
+        "border_edges": int((edges.face_count == 1).sum()), "non_manifold_edges": int((edges.face_count > 2).sum()),
+        "inconsistent_interior_edges": int(((edges.face_count == 2) & (edges.winding != 0)).sum()),
+        "border_vertices": int(edges.vertex_boundary.sum()),
+        "workspace_bytes": {"edges": int(lib.mvsn_mesh_edges_workspace_bytes(m, nf)) if nf else 0,
+                            "smooth": int(lib.mvsn_mesh_smooth_workspace_bytes(m)),
+                            "normals": int(lib.mvsn_mesh_normals_workspace_bytes(m))},
+        "edges_ms_per_call_mean": float(np.mean(etimes)), "edges_ms_per_call_min": float(np.min(etimes)),
+        "smooth_ms_per_call_mean": float(np.mean(stimes)), "smooth_ms_per_call_min": float(np.min(stimes)),
+        "smooth_ms_per_step_mean": float(np.mean(stimes)) / n_steps,
+        "smooth_with_its_own_edges_ms_per_call_mean": float(np.mean(wtimes)),
+        "normals_ms_per_call_mean": float(np.mean(ntimes)), "normals_ms_per_call_min": float(np.min(ntimes)),
+        "moved_voxels_mean": float(moved.mean()) if m else 0.0, "moved_voxels_max": float(moved.max()) if m else 0.0,
+        "vertex_normals_along_the_tsdf_gradient": float((outwards > 0).float().mean()) if m else 0.0,
+        "torch": {"E": int(tedges.shape[0]), "edges_ms_per_call_mean": float(np.mean(tetimes)),
+                  "smooth_ms_per_call_mean": float(np.mean(tstimes)), "smooth_ms_per_call_min": float(np.min(tstimes)),
+                  "smooth_ms_per_step_mean": float(np.mean(tstimes)) / n_steps,
+                  "same_edge_count": bool(tedges.shape[0] == edges.edges.shape[0]),
+                  "vertices_apart_voxels_max": float(apart.max()) if m else 0.0},
+        "device_edges_beat_torch": bool(np.mean(etimes) < np.mean(tetimes)),
+        "device_smooth_beats_torch": bool(np.mean(stimes) < np.mean(tstimes))}}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
         align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False, mesh_render_too=False,
-        simplify_too=False):
+        simplify_too=False, smooth_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -1247,7 +1327,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     mesh_scored = run_mesh_metrics(sc, res, steps, warmup) if mesh_metrics_too else {}
     rasterised = run_mesh_render(sc, steps, warmup) if mesh_render_too else {}
     simplified = run_simplify(sc, steps, warmup) if simplify_too else {}
-    return {**simplified, **rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    smoothed = run_smooth(sc, steps, warmup) if smooth_too else {}
+    return {**smoothed, **simplified, **rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -1297,12 +1378,15 @@ def main():
     ap.add_argument("--simplify", action="store_true",
                     help="also simplify the volume's mesh (mesh_simplify at 1, 2 and 4 voxels per cell, both placements), "
                          "measure how far the result is from the original surface, and the torch form of the clustering")
+    ap.add_argument("--smooth", action="store_true",
+                    help="also find the edges of the volume's mesh (mesh_edges), smooth it (mesh_smooth, Taubin) and recompute "
+                         "its normals (mesh_normals), and the torch form of the edges and of the smoothing")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
-                             a.render, a.mesh_metrics, a.mesh_render, a.simplify)), flush=True)
+                             a.render, a.mesh_metrics, a.mesh_render, a.simplify, a.smooth)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
