@@ -18,7 +18,7 @@ def hipcc() -> str:
 
 
 MANIFEST = LIB + ".sources"
-HEADERS = ["mvsn_common.h", "mvsn_conv_bf16x3.h", "mvsn_chain.h", "mvsn_conv_wino.h", "mvsn_resident.h", "mvsn_voxel.h", "mvsn_geom.h", "mvsn_tsdf_sample.h", "mvsn_cloud.h", "mvsn_pose.h", "mvsn_unionfind.h", "mvsn_camera.h"]
+HEADERS = ["mvsn_common.h", "mvsn_conv_bf16x3.h", "mvsn_chain.h", "mvsn_conv_wino.h", "mvsn_resident.h", "mvsn_voxel.h", "mvsn_geom.h", "mvsn_tsdf_sample.h", "mvsn_cloud.h", "mvsn_pose.h", "mvsn_unionfind.h", "mvsn_camera.h", "mvsn_mesh.h"]
 # -fno-slp-vectorize: packed f32 VALU (v_pk_add_f32 ...) next to MFMAs costs more issue time than the two
 # scalar ops it replaces (measured: +1.3 % end to end, +3-4 % on the Winograd kernels)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize"]

@@ -74,15 +74,11 @@ inline CloudIndex cloud_index(const void *workspace, const Layout &l, const Reco
   return {(const unsigned long long *)(ws + l.keys), (const int *)(ws + l.pop), (const int *)(ws + l.start), l.slots};
 }
 
-// The two requirements on the workspace of an index of n points, `what` its noun in the entry's message ("workspace",
-// "index workspace"); 0 and the layout in `l`, or the error code.
+// workspace_check (mvsn_geom.h) on the workspace of an index of n points; 0 and the layout in `l`, or the error code.
 inline int cloud_index_check(const char *who, const char *what, const void *workspace, size_t workspace_bytes, long n,
                              CloudLayout *l) {
   *l = cloud_layout(n);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l->bytes, MVSN_E_WORKSPACE, "%s: %s of %zu bytes, %zu needed", who, what,
-               workspace_bytes, l->bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  return 0;
+  return workspace_check(who, what, workspace, workspace_bytes, l->bytes);
 }
 
 // defined in mvsn_cloud.hip, launched by the mesh's pair index too: the table init, the per-workgroup population sums

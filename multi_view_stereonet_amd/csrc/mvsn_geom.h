@@ -13,7 +13,15 @@ namespace mvsn {
 // every section of a workspace starts on a 256-byte boundary
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-constexpr int GEOM_SCAN_THREADS = 1024;                 // the one workgroup of geom_scan_kernel
+// The two requirements on a workspace of `needed` bytes, `what` its noun in the entry's message ("workspace", "index
+// workspace"): MVSN_E_WORKSPACE for a null or short one, MVSN_E_BADARG for one that is not 16-byte aligned.
+inline int workspace_check(const char *who, const char *what, const void *workspace, size_t bytes, size_t needed) {
+  MVSN_REQUIRE(workspace && bytes >= needed, MVSN_E_WORKSPACE, "%s: %s of %zu bytes, %zu needed", who, what, bytes, needed);
+  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
+  return 0;
+}
+
+constexpr int GEOM_SCAN_THREADS = 1024;                // the one workgroup of geom_scan_kernel
 
 // Defined in mvsn_voxel.hip; launch with one workgroup of GEOM_SCAN_THREADS threads: the exclusive prefix of n
 // per-workgroup counts in index order, and *total = their sum where total is not null.  Every thread owns a run of

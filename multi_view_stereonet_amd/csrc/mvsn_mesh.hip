@@ -28,12 +28,12 @@
 // stops and sets MVSN_MESH_STATUS_WORKSPACE in the head.
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 #include "mvsn_unionfind.h"
 
 namespace mvsn {
 
 constexpr int MS_THREADS = 256;                         // one vertex or one face per thread
-constexpr long MS_MAX = 0x7fffffffL;                    // vertices, and faces: a row is an int32
 
 // byte offsets of the workspace sections (each 256-byte aligned)
 struct MeshLayout {
@@ -54,7 +54,7 @@ inline MeshLayout mesh_layout(long m, long f) {
   return l;
 }
 
-inline bool mesh_sizes_ok(long m, long f) { return m > 0 && m <= MS_MAX && f >= 0 && f <= MS_MAX; }
+inline bool mesh_sizes_ok(long m, long f) { return m > 0 && m <= MESH_MAX_ROWS && f >= 0 && f <= MESH_MAX_ROWS; }
 
 __global__ __launch_bounds__(MS_THREADS) void mesh_init_kernel(int *__restrict__ parent, long m,
                                                                unsigned long long *__restrict__ head) {
@@ -63,11 +63,11 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_init_kernel(int *__restrict__
   if (v == 0) head[0] = 0, head[1] = 0;
 }
 
-// the three rows of face i, read straight from the int64 tensor; false when one lies outside [0, m)
+// face_rows narrowed to int; zeros, and false, when a row lies outside [0, m)
 __device__ __forceinline__ bool mesh_face(const int64_t *__restrict__ faces, long i, long m, int *r) {
-  const int64_t a = faces[i * 3], b = faces[i * 3 + 1], c = faces[i * 3 + 2];
-  const bool ok = a >= 0 && a < m && b >= 0 && b < m && c >= 0 && c < m;
-  r[0] = ok ? (int)a : 0, r[1] = ok ? (int)b : 0, r[2] = ok ? (int)c : 0;
+  int64_t v[3];
+  const bool ok = face_rows(faces, i, m, v);
+  r[0] = ok ? (int)v[0] : 0, r[1] = ok ? (int)v[1] : 0, r[2] = ok ? (int)v[2] : 0;
   return ok;
 }
 
@@ -241,13 +241,10 @@ static int mesh_check(const char *who, long n_vertices, long n_faces, const void
                       mvsn::MeshLayout *l) {
   using namespace mvsn;
   MVSN_REQUIRE(n_vertices > 0 && n_faces >= 0, MVSN_E_BADARG, "%s: %ld vertices and %ld faces", who, n_vertices, n_faces);
-  MVSN_REQUIRE(n_vertices <= MS_MAX && n_faces <= MS_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(n_vertices <= MESH_MAX_ROWS && n_faces <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "%s: %ld vertices and %ld faces (at most 2^31 - 1 each)", who, n_vertices, n_faces);
   *l = mesh_layout(n_vertices, n_faces);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l->bytes, MVSN_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-               workspace_bytes, l->bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  return 0;
+  return workspace_check(who, "workspace", workspace, workspace_bytes, l->bytes);
 }
 
 extern "C" int mvsn_mesh_components_label(const int64_t *faces, long n_vertices, long n_faces, int64_t *result,

@@ -21,12 +21,12 @@
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 #include "mvsn_voxel.h"
 
 namespace mvsn {
 
 constexpr int ME_THREADS = 256;                         // one side, slot or vertex per thread
-constexpr long ME_MAX_VERTICES = 0x7fffffffL;
 constexpr long ME_MAX_FACES = 0x7fffffffL / 3;          // a side index is an int32
 constexpr size_t ME_MIN_SLOTS = 1024;
 constexpr int ME_NO_SIDE = 0x7fffffff;
@@ -75,9 +75,10 @@ __device__ __forceinline__ bool edges_side(const int64_t *__restrict__ faces, lo
                                            bool *up) {
   const long r = i / 3;
   const int s = (int)(i - r * 3);
-  const int64_t v[3] = {faces[r * 3], faces[r * 3 + 1], faces[r * 3 + 2]};
-  if (!(v[0] >= 0 && v[0] < m && v[1] >= 0 && v[1] < m && v[2] >= 0 && v[2] < m)) return false;
-  const int64_t a = v[s], b = v[s == 2 ? 0 : s + 1];
+  int64_t v[3];
+  if (!face_rows(faces, r, m, v)) return false;
+  // (selects, not v[s]: an array indexed by a variable would be placed in LDS)
+  const int64_t a = s == 0 ? v[0] : s == 1 ? v[1] : v[2], b = s == 0 ? v[1] : s == 1 ? v[2] : v[0];
   if (a == b) return false;
   *up = a < b;
   *lo = *up ? a : b;
@@ -178,8 +179,19 @@ inline unsigned edges_blocks(long n) { return (unsigned)((n + ME_THREADS - 1) / 
 }  // namespace mvsn
 
 extern "C" size_t mvsn_mesh_edges_workspace_bytes(long n_vertices, long n_faces) {
-  if (n_vertices <= 0 || n_vertices > mvsn::ME_MAX_VERTICES || n_faces <= 0 || n_faces > mvsn::ME_MAX_FACES) return 0;
+  if (n_vertices <= 0 || n_vertices > mvsn::MESH_MAX_ROWS || n_faces <= 0 || n_faces > mvsn::ME_MAX_FACES) return 0;
   return mvsn::edges_layout(n_faces).bytes;
+}
+
+// the checks of the counts and of the workspace that the two entries share (each has rejected its null pointers, and
+// emit its edge count, before); `l` is filled when they pass
+static int edges_check(const char *who, long m, long f, const void *workspace, size_t workspace_bytes,
+                       mvsn::EdgesLayout *l) {
+  using namespace mvsn;
+  MVSN_REQUIRE(m <= MESH_MAX_ROWS && f <= ME_MAX_FACES, MVSN_E_TOOLARGE,
+               "%s: %ld vertices, %ld faces (at most 2^31 - 1 vertices and (2^31 - 1) / 3 faces)", who, m, f);
+  *l = edges_layout(f);
+  return workspace_check(who, "workspace", workspace, workspace_bytes, l->bytes);
 }
 
 extern "C" int mvsn_mesh_edges_mark(const int64_t *faces, long n_vertices, long n_faces, int64_t *result, void *workspace,
@@ -188,12 +200,8 @@ extern "C" int mvsn_mesh_edges_mark(const int64_t *faces, long n_vertices, long 
   const long m = n_vertices, f = n_faces;
   MVSN_REQUIRE(faces && result && workspace, MVSN_E_BADARG, "mvsn_mesh_edges_mark: null pointer");
   MVSN_REQUIRE(m > 0 && f > 0, MVSN_E_BADARG, "mvsn_mesh_edges_mark: %ld vertices, %ld faces", m, f);
-  MVSN_REQUIRE(m <= ME_MAX_VERTICES && f <= ME_MAX_FACES, MVSN_E_TOOLARGE,
-               "mvsn_mesh_edges_mark: %ld vertices, %ld faces (at most 2^31 - 1 vertices and (2^31 - 1) / 3 faces)", m, f);
-  const EdgesLayout l = edges_layout(f);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_edges_mark: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "mvsn_mesh_edges_mark: workspace not 16-byte aligned");
+  EdgesLayout l;
+  if (int e = edges_check("mvsn_mesh_edges_mark", m, f, workspace, workspace_bytes, &l)) return e;
   char *ws = (char *)workspace;
   unsigned long long *keys = (unsigned long long *)(ws + l.keys);
   int *minside = (int *)(ws + l.minside), *count = (int *)(ws + l.count), *wind = (int *)(ws + l.wind);
@@ -223,13 +231,10 @@ extern "C" int mvsn_mesh_edges_emit(long n_vertices, long n_faces, void *workspa
                "mvsn_mesh_edges_emit: null pointer");
   MVSN_REQUIRE(m > 0 && f > 0 && n_edges >= 0 && (f > ME_MAX_FACES || n_edges <= 3 * f), MVSN_E_BADARG,
                "mvsn_mesh_edges_emit: %ld vertices, %ld faces, %ld edges", m, f, n_edges);
-  MVSN_REQUIRE(m <= ME_MAX_VERTICES && f <= ME_MAX_FACES, MVSN_E_TOOLARGE,
-               "mvsn_mesh_edges_emit: %ld vertices, %ld faces (at most 2^31 - 1 vertices and (2^31 - 1) / 3 faces)", m, f);
   MVSN_REQUIRE(n_edges == 0 || (edges && first && face_count && winding), MVSN_E_BADARG,
                "mvsn_mesh_edges_emit: null edge output");
-  const EdgesLayout l = edges_layout(f);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_edges_emit: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
+  EdgesLayout l;
+  if (int e = edges_check("mvsn_mesh_edges_emit", m, f, workspace, workspace_bytes, &l)) return e;
   char *ws = (char *)workspace;                          // (row, a section of it, is written here)
   const int *sslot = (const int *)(ws + l.sslot);
   int *slot_row = (int *)(ws + l.row);

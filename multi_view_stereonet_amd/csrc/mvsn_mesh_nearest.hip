@@ -26,11 +26,11 @@
 // atomics only; fp64 with + - x / and compares, contraction off for the whole file; no scratch; every loop bounded.
 #pragma clang fp contract(off)
 #include "mvsn_cloud.h"
+#include "mvsn_mesh.h"
 
 namespace mvsn {
 
 constexpr int MN_THREADS = 256;                         // one face, or one query, per thread
-constexpr long MN_MAX = 0x7fffffffL;                    // vertices, faces, queries, pairs: a row is an int32
 constexpr unsigned long long MN_BOX_CELLS = MVSN_MESH_NEAREST_BOX_CELLS;
 enum { MN_NO_PART = 0, MN_BOXED = 1, MN_OUT_OF_RANGE = 2 };
 
@@ -58,7 +58,7 @@ inline NearestLayout nearest_layout(long pairs, long large) {
   return l;
 }
 
-inline bool nearest_sizes_ok(long pairs, long large) { return pairs >= 0 && pairs <= MN_MAX && large >= 0 && large <= MN_MAX; }
+inline bool nearest_sizes_ok(long pairs, long large) { return pairs >= 0 && pairs <= MESH_MAX_ROWS && large >= 0 && large <= MESH_MAX_ROWS; }
 
 // The vertices of face i and its box of cells, every step one fp32 operation: lo = floor(min inv), hi = floor(max inv)
 // per axis.  MN_NO_PART (nothing dereferenced) when an index lies outside [0, m) or a coordinate is not finite;
@@ -66,12 +66,12 @@ inline bool nearest_sizes_ok(long pairs, long large) { return pairs >= 0 && pair
 __device__ __forceinline__ int nearest_face_box(const float *__restrict__ vertices, long m,
                                                 const int64_t *__restrict__ faces, long i, float inv, float (*p)[3],
                                                 int *lo, int *hi) {
-  const int64_t ia = faces[i * 3], ib = faces[i * 3 + 1], ic = faces[i * 3 + 2];
-  if (!(ia >= 0 && ia < m && ib >= 0 && ib < m && ic >= 0 && ic < m)) return MN_NO_PART;
+  int64_t r[3];
+  if (!face_rows(faces, i, m, r)) return MN_NO_PART;
   bool finite = true, inside = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const float a = vertices[ia * 3 + k], b = vertices[ib * 3 + k], c = vertices[ic * 3 + k];
+    const float a = vertices[r[0] * 3 + k], b = vertices[r[1] * 3 + k], c = vertices[r[2] * 3 + k];
     p[0][k] = a, p[1][k] = b, p[2][k] = c;
     finite = finite && isfinite(a) && isfinite(b) && isfinite(c);
     float mn = b < a ? b : a, mx = b > a ? b : a;
@@ -319,7 +319,7 @@ static int nearest_check_mesh(const char *who, const float *vertices, long n_ver
   using namespace mvsn;
   MVSN_REQUIRE(vertices && faces, MVSN_E_BADARG, "%s: null pointer", who);
   MVSN_REQUIRE(n_vertices > 0 && n_faces > 0, MVSN_E_BADARG, "%s: %ld vertices and %ld faces", who, n_vertices, n_faces);
-  MVSN_REQUIRE(n_vertices <= MN_MAX && n_faces <= MN_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(n_vertices <= MESH_MAX_ROWS && n_faces <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "%s: %ld vertices and %ld faces (at most 2^31 - 1 each)", who, n_vertices, n_faces);
   MVSN_REQUIRE(inv_cell > 0.0f && inv_cell <= 3.0e38f, MVSN_E_BADARG,
                "%s: inverse cell size %g is not a positive finite number", who, (double)inv_cell);
@@ -330,13 +330,10 @@ static int nearest_check_workspace(const char *who, long n_pairs, long n_large, 
                                    size_t workspace_bytes, mvsn::NearestLayout *l) {
   using namespace mvsn;
   MVSN_REQUIRE(n_pairs >= 0 && n_large >= 0, MVSN_E_BADARG, "%s: %ld pairs and %ld large faces", who, n_pairs, n_large);
-  MVSN_REQUIRE(n_pairs <= MN_MAX && n_large <= MN_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(n_pairs <= MESH_MAX_ROWS && n_large <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "%s: %ld pairs and %ld large faces (at most 2^31 - 1 each)", who, n_pairs, n_large);
   *l = nearest_layout(n_pairs, n_large);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l->bytes, MVSN_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-               workspace_bytes, l->bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  return 0;
+  return workspace_check(who, "workspace", workspace, workspace_bytes, l->bytes);
 }
 
 extern "C" int mvsn_mesh_nearest_count(const float *vertices, long n_vertices, const int64_t *faces, long n_faces,
@@ -393,7 +390,7 @@ extern "C" int mvsn_mesh_nearest(const float *query, long nq, const float *verti
   using namespace mvsn;
   MVSN_REQUIRE(query && dist2 && face && point && weights && within, MVSN_E_BADARG, "mvsn_mesh_nearest: null pointer");
   MVSN_REQUIRE(nq > 0, MVSN_E_BADARG, "mvsn_mesh_nearest: %ld queries", nq);
-  MVSN_REQUIRE(nq <= MN_MAX, MVSN_E_TOOLARGE, "mvsn_mesh_nearest: %ld queries (at most 2^31 - 1)", nq);
+  MVSN_REQUIRE(nq <= MESH_MAX_ROWS, MVSN_E_TOOLARGE, "mvsn_mesh_nearest: %ld queries (at most 2^31 - 1)", nq);
   if (int e = nearest_check_mesh("mvsn_mesh_nearest", vertices, n_vertices, faces, n_faces, inv_cell)) return e;
   MVSN_REQUIRE(r2 > 0.0f && r2 <= 3.0e38f, MVSN_E_BADARG,
                "mvsn_mesh_nearest: squared radius %g is not a positive finite number", (double)r2);

@@ -27,42 +27,9 @@
 #include "mvsn_common.h"
 #include "mvsn_camera.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 
 namespace mvsn {
-
-// The interpolation of vertex normals and colours is sample_draw_kernel's (mvsn_mesh_sample.hip, section 26), restated
-// operation for operation: moved into a shared header it changed that kernel's register allocation, and a sample there
-// has rows of three outputs where a pixel here has planes.
-//
-// the weighted sum of the three vertex normals in fp64, left to right, divided by its length; (0,0,0) where the length is
-// 0 or not finite, and where !ok (nothing is dereferenced then)
-__device__ __forceinline__ void mr_normal(const float *__restrict__ normals, const long *r, const double *w, bool ok,
-                                          float *out) {
-  double s[3] = {0.0, 0.0, 0.0};
-  if (ok) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      s[k] = (w[0] * (double)normals[r[0] * 3 + k] + w[1] * (double)normals[r[1] * 3 + k]) +
-             w[2] * (double)normals[r[2] * 3 + k];
-  }
-  const double len = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
-  const bool defined = ok && len > 0.0 && isfinite(len);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) out[k] = defined ? (float)(s[k] / len) : 0.0f;
-}
-
-// the weighted sum of the three vertex colours, floor(x + 0.5), clamped to 0..255; (0,0,0) where !ok
-__device__ __forceinline__ void mr_color(const uint8_t *__restrict__ colors, const long *r, const double *w, bool ok,
-                                         uint8_t *out) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double x = 0.0;
-    if (ok)
-      x = (w[0] * (double)colors[r[0] * 3 + k] + w[1] * (double)colors[r[1] * 3 + k]) + w[2] * (double)colors[r[2] * 3 + k];
-    const double y = floor(x + 0.5);
-    out[k] = (uint8_t)(y > 0.0 ? (y < 255.0 ? y : 255.0) : 0.0);
-  }
-}
 
 constexpr int MR_THREADS = 256;
 constexpr int MR_CAM_BATCH = 32;                        // cameras staged in LDS at once
@@ -71,29 +38,8 @@ constexpr float MR_FLT_MAX = 3.4028234e38f;
 constexpr float MR_GUARD = 65536.0f;                    // |u|, |v| up to here: 2^24 once snapped
 constexpr float MR_SUBPIXEL = 256.0f;                   // 8 sub-pixel bits
 constexpr int MR_MAX_EXTENT = 1 << 15;                  // rows and cols up to here: the guard band is at least a map wide
-constexpr long MR_MAX_ROWS = 0x7fffffffL;               // a face row is the low word of a key
 constexpr unsigned MR_MAX_BLOCKS = 1u << 20;            // of the two per-pixel kernels, which stride over the rest
 constexpr unsigned long long MR_EMPTY = ~0ull;          // never a real key: z is finite, so its bits are below 0x7f800000
-
-// the three vertices of face i as fp32 (p[3 j + k] = coordinate k of vertex j) and their rows; false (nothing
-// dereferenced) when i is past the end, an index lies outside [0, m) or a coordinate is not finite
-__device__ __forceinline__ bool mr_load_face(const float *__restrict__ vertices, long m, const int64_t *__restrict__ faces,
-                                             long f, long i, long *r, float *p) {
-  if (i >= f) return false;
-  const int64_t a = faces[i * 3], b = faces[i * 3 + 1], c = faces[i * 3 + 2];
-  if (!(a >= 0 && a < m && b >= 0 && b < m && c >= 0 && c < m)) return false;
-  r[0] = (long)a, r[1] = (long)b, r[2] = (long)c;
-  bool finite = true;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float x = vertices[r[j] * 3 + k];
-      finite = finite && fabsf(x) <= MR_FLT_MAX;
-      p[j * 3 + k] = x;
-    }
-  return finite;
-}
 
 // a face in one view, in its own vertex order
 struct MrSnap {
@@ -105,13 +51,13 @@ struct MrSnap {
 
 // section 25's projection of the three vertices (three nested fmaf per row, two divisions), the limit compared as floats
 // before any conversion (a NaN fails), the snap
-__device__ __forceinline__ MrSnap mr_snap(const float *Pm, const float *p, bool valid, float min_depth) {
+__device__ __forceinline__ MrSnap mr_snap(const float *Pm, const float (*p)[3], bool valid, float min_depth) {
   MrSnap s;
   float u[3], v[3];
   bool all = valid, any = false;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const float x = p[j * 3], y = p[j * 3 + 1], zw = p[j * 3 + 2];
+    const float x = p[j][0], y = p[j][1], zw = p[j][2];
     const float a0 = fmaf(Pm[0], x, fmaf(Pm[1], y, fmaf(Pm[2], zw, Pm[3])));
     const float a1 = fmaf(Pm[4], x, fmaf(Pm[5], y, fmaf(Pm[6], zw, Pm[7])));
     s.zc[j] = fmaf(Pm[8], x, fmaf(Pm[9], y, fmaf(Pm[10], zw, Pm[11])));
@@ -224,10 +170,10 @@ __global__ __launch_bounds__(MR_THREADS) void mesh_raster_kernel(
   __shared__ float scam[MR_CAM_BATCH * TS_CAM];
   const long i = (long)blockIdx.x * MR_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  long r3[3];
-  float p[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  int64_t r3[3];
+  float p[3][3] = {};
   // (a thread past the end, and a face that takes no part, stay: every lane of a wave reaches the cooperative loop)
-  const bool valid = mr_load_face(vertices, m, faces, f, i, r3, p);
+  const bool valid = i < f && face_load(vertices, m, faces, i, r3, p);
   const size_t P = (size_t)rows * cols;
 
   for (int base = 0; base < n_views; base += MR_CAM_BATCH) {        // bounded: ceil(V / MR_CAM_BATCH) rounds
@@ -294,12 +240,12 @@ __global__ __launch_bounds__(MR_THREADS) void mesh_resolve_kernel(
   for (size_t pix = (size_t)blockIdx.x * MR_THREADS + threadIdx.x; pix < P; pix += stride) {
     const unsigned long long key = keys[v * P + pix];
     const long row = (long)(key & 0xffffffffull);
-    long r3[3] = {0, 0, 0};
+    int64_t r3[3] = {0, 0, 0};
     double w[3] = {0.0, 0.0, 0.0};
     bool hit = false;
     if (key != MR_EMPTY) {                                          // (a key the raster wrote always names a covering face)
-      float p[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      const bool valid = mr_load_face(vertices, m, faces, f, row, r3, p);
+      float p[3][3] = {};
+      const bool valid = row < f && face_load(vertices, m, faces, row, r3, p);
       const MrSnap s = mr_snap(scam, p, valid, min_depth);
       if (s.part) {
         const MrTri t = mr_tri(s.X, s.Y, s.zc);
@@ -318,13 +264,13 @@ __global__ __launch_bounds__(MR_THREADS) void mesh_resolve_kernel(
     for (int k = 0; k < 3; ++k) weights[(v * 3 + k) * P + pix] = hit ? (float)w[k] : 0.0f;
     if (NORMAL) {
       float n[3];
-      mr_normal(normals, r3, w, hit, n);
+      face_normal(normals, r3, w, hit, n);
 #pragma unroll
       for (int k = 0; k < 3; ++k) out_normals[(v * 3 + k) * P + pix] = n[k];
     }
     if (COLOR) {
       uint8_t c[3];
-      mr_color(colors, r3, w, hit, c);
+      face_color(colors, r3, w, hit, c);
 #pragma unroll
       for (int k = 0; k < 3; ++k) out_colors[(v * 3 + k) * P + pix] = c[k];
     }
@@ -358,7 +304,7 @@ extern "C" int mvsn_mesh_render(const float *vertices, long n_vertices, const in
                "%s: null pointer", who);
   MVSN_REQUIRE(!normals == !out_normals && !colors == !out_colors, MVSN_E_BADARG,
                "%s: normals and out_normals go together, and colors and out_colors", who);
-  MVSN_REQUIRE(n_vertices >= 1 && n_vertices <= MR_MAX_ROWS && n_faces >= 1 && n_faces <= MR_MAX_ROWS, MVSN_E_BADARG,
+  MVSN_REQUIRE(n_vertices >= 1 && n_vertices <= MESH_MAX_ROWS && n_faces >= 1 && n_faces <= MESH_MAX_ROWS, MVSN_E_BADARG,
                "%s: %ld vertices and %ld faces (1 to 2^31 - 1 each)", who, n_vertices, n_faces);
   MVSN_REQUIRE(n_views >= 1 && n_views <= 65535, MVSN_E_BADARG, "%s: %d views (1 to 65535)", who, n_views);
   MVSN_REQUIRE(mesh_render_sizes_ok(n_views, rows, cols), MVSN_E_BADARG,
@@ -369,9 +315,7 @@ extern "C" int mvsn_mesh_render(const float *vertices, long n_vertices, const in
   MVSN_REQUIRE(max_depth > 0.0f, MVSN_E_BADARG, "%s: max_depth %g is not a number > 0 (+inf: no limit)", who,
                (double)max_depth);
   const size_t need = mesh_render_bytes(n_views, rows, cols);
-  MVSN_REQUIRE(workspace && workspace_bytes >= need, MVSN_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-               workspace_bytes, need);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
+  if (int e = workspace_check(who, "workspace", workspace, workspace_bytes, need)) return e;
   const size_t P = (size_t)rows * cols, total = (size_t)n_views * P;
   unsigned long long *keys = (unsigned long long *)workspace, *lost = keys + total;
   const hipStream_t st = (hipStream_t)stream;

@@ -23,11 +23,11 @@
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 
 namespace mvsn {
 
 constexpr int SM_THREADS = 256;                         // one face, or one sample, per thread
-constexpr long SM_MAX = 0x7fffffffL;                    // vertices, faces and samples: a row is an int32
 
 // byte offsets of the workspace sections (each 256-byte aligned)
 struct SampleLayout {
@@ -46,25 +46,6 @@ inline SampleLayout sample_layout(long f) {
   return l;
 }
 
-// the three vertices of face i in fp64; false (nothing dereferenced) when an index lies outside [0, m) or a coordinate
-// is not finite
-__device__ __forceinline__ bool sample_face(const float *__restrict__ vertices, long m, const int64_t *__restrict__ faces,
-                                            long i, long *r, double (*p)[3]) {
-  const int64_t a = faces[i * 3], b = faces[i * 3 + 1], c = faces[i * 3 + 2];
-  if (!(a >= 0 && a < m && b >= 0 && b < m && c >= 0 && c < m)) return false;
-  r[0] = (long)a, r[1] = (long)b, r[2] = (long)c;
-  bool finite = true;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float x = vertices[r[j] * 3 + k];
-      finite = finite && isfinite(x);
-      p[j][k] = (double)x;
-    }
-  return finite;
-}
-
 __global__ __launch_bounds__(SM_THREADS) void sample_area_kernel(const float *__restrict__ vertices, long m,
                                                                  const int64_t *__restrict__ faces, long f,
                                                                  double *__restrict__ area,
@@ -72,16 +53,11 @@ __global__ __launch_bounds__(SM_THREADS) void sample_area_kernel(const float *__
   const long i = (long)blockIdx.x * SM_THREADS + threadIdx.x;
   double mine = 0.0;
   if (i < f) {
-    long r[3];
-    double p[3][3];
-    if (sample_face(vertices, m, faces, i, r, p)) {
-      const double ab[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-      const double ac[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-      const double nx = ab[1] * ac[2] - ab[2] * ac[1];
-      const double ny = ab[2] * ac[0] - ab[0] * ac[2];
-      const double nz = ab[0] * ac[1] - ab[1] * ac[0];
-      const double nn = (nx * nx + ny * ny) + nz * nz;
-      mine = 0.5 * sqrt(nn);
+    int64_t r[3];
+    double p[3][3], c[3];
+    if (face_load(vertices, m, faces, i, r, p)) {
+      face_cross(p, c);
+      mine = 0.5 * sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
     }
     area[i] = mine;
   }
@@ -193,10 +169,10 @@ __global__ __launch_bounds__(SM_THREADS) void sample_draw_kernel(
     if (prefix[mid] > pick) hi = mid;
     else lo = mid + 1;
   }
-  long r[3] = {0, 0, 0};
+  int64_t r[3] = {0, 0, 0};
   double p[3][3] = {};
   // (a chosen face has q > 0, so it takes part: anything else is a workspace that is not this mesh's)
-  const bool ok = lo < f && sample_face(vertices, m, faces, lo, r, p);
+  const bool ok = lo < f && face_load(vertices, m, faces, lo, r, p);
   double u = (double)(z2 >> 11) * 0x1p-53, v = (double)(z3 >> 11) * 0x1p-53;
   if (u + v > 1.0) u = 1.0 - u, v = 1.0 - v;
   const double w[3] = {(1.0 - u) - v, u, v};
@@ -209,34 +185,23 @@ __global__ __launch_bounds__(SM_THREADS) void sample_draw_kernel(
     weights[i * 3 + k] = ok ? (float)w[k] : 0.0f;
   }
   if (out_normals) {
-    double s[3] = {0.0, 0.0, 0.0};
-    if (ok) {
+    float nrm[3];
+    face_normal(normals, r, w, ok, nrm);
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-        s[k] = (w[0] * (double)normals[r[0] * 3 + k] + w[1] * (double)normals[r[1] * 3 + k]) +
-               w[2] * (double)normals[r[2] * 3 + k];
-    }
-    const double len = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
-    const bool defined = ok && len > 0.0 && isfinite(len);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out_normals[i * 3 + k] = defined ? (float)(s[k] / len) : 0.0f;
+    for (int k = 0; k < 3; ++k) out_normals[i * 3 + k] = nrm[k];
   }
   if (out_colors) {
+    uint8_t col[3];
+    face_color(colors, r, w, ok, col);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      double x = 0.0;
-      if (ok)
-        x = (w[0] * (double)colors[r[0] * 3 + k] + w[1] * (double)colors[r[1] * 3 + k]) + w[2] * (double)colors[r[2] * 3 + k];
-      const double y = floor(x + 0.5);
-      out_colors[i * 3 + k] = (uint8_t)(y > 0.0 ? (y < 255.0 ? y : 255.0) : 0.0);
-    }
+    for (int k = 0; k < 3; ++k) out_colors[i * 3 + k] = col[k];
   }
 }
 
 }  // namespace mvsn
 
 extern "C" size_t mvsn_mesh_sample_workspace_bytes(long n_faces) {
-  if (n_faces <= 0 || n_faces > mvsn::SM_MAX) return 0;
+  if (n_faces <= 0 || n_faces > mvsn::MESH_MAX_ROWS) return 0;
   return mvsn::sample_layout(n_faces).bytes;
 }
 
@@ -245,13 +210,10 @@ static int sample_check(const char *who, const float *vertices, long n_vertices,
   using namespace mvsn;
   MVSN_REQUIRE(vertices && faces, MVSN_E_BADARG, "%s: null pointer", who);
   MVSN_REQUIRE(n_vertices > 0 && n_faces > 0, MVSN_E_BADARG, "%s: %ld vertices and %ld faces", who, n_vertices, n_faces);
-  MVSN_REQUIRE(n_vertices <= SM_MAX && n_faces <= SM_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(n_vertices <= MESH_MAX_ROWS && n_faces <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "%s: %ld vertices and %ld faces (at most 2^31 - 1 each)", who, n_vertices, n_faces);
   *l = sample_layout(n_faces);
-  MVSN_REQUIRE(workspace && workspace_bytes >= l->bytes, MVSN_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-               workspace_bytes, l->bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "%s: workspace not 16-byte aligned", who);
-  return 0;
+  return workspace_check(who, "workspace", workspace, workspace_bytes, l->bytes);
 }
 
 extern "C" int mvsn_mesh_sample_prefix(const float *vertices, long n_vertices, const int64_t *faces, long n_faces,
@@ -292,7 +254,7 @@ extern "C" int mvsn_mesh_sample_draw(const float *vertices, long n_vertices, con
   if (int e = sample_check("mvsn_mesh_sample_draw", vertices, n_vertices, faces, n_faces, workspace, workspace_bytes, &l))
     return e;
   MVSN_REQUIRE(n > 0, MVSN_E_BADARG, "mvsn_mesh_sample_draw: %ld samples", n);
-  MVSN_REQUIRE(n <= SM_MAX, MVSN_E_TOOLARGE, "mvsn_mesh_sample_draw: %ld samples (at most 2^31 - 1)", n);
+  MVSN_REQUIRE(n <= MESH_MAX_ROWS, MVSN_E_TOOLARGE, "mvsn_mesh_sample_draw: %ld samples (at most 2^31 - 1)", n);
   MVSN_REQUIRE(points && face && weights, MVSN_E_BADARG, "mvsn_mesh_sample_draw: null output");
   MVSN_REQUIRE(!normals == !out_normals && !colors == !out_colors, MVSN_E_BADARG,
                "mvsn_mesh_sample_draw: normals in and out go together, and colours");

@@ -29,12 +29,12 @@
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 #include "mvsn_voxel.h"
 
 namespace mvsn {
 
 constexpr int MS_THREADS = 256;                         // one vertex, cluster or face per thread
-constexpr long MS_MAX = 0x7fffffffL;                    // vertices and faces: a row is an int32
 constexpr size_t MS_MIN_SLOTS = 1024;
 constexpr int MS_QUAD_WORDS = 10;                       // xx xy xz yy yz zz, dx dy dz, k
 constexpr int MS_VOXEL_ROW_WORDS = 8;                   // mvsn_voxel.hip's accumulator row: sum qx qy qz, r g b, count, key
@@ -96,20 +96,12 @@ __global__ __launch_bounds__(MS_THREADS) void simplify_init_kernel(unsigned long
 __device__ __forceinline__ bool simplify_face_clusters(const int64_t *__restrict__ faces,
                                                        const int64_t *__restrict__ cid, long m, long clusters, long r,
                                                        int *g) {
-  const int64_t a = faces[r * 3], b = faces[r * 3 + 1], c = faces[r * 3 + 2];
-  if (!(a >= 0 && a < m && b >= 0 && b < m && c >= 0 && c < m)) return false;
-  const int64_t ga = cid[a], gb = cid[b], gc = cid[c];
+  int64_t v[3];
+  if (!face_rows(faces, r, m, v)) return false;
+  const int64_t ga = cid[v[0]], gb = cid[v[1]], gc = cid[v[2]];
   if (!(ga >= 0 && ga < clusters && gb >= 0 && gb < clusters && gc >= 0 && gc < clusters)) return false;
   g[0] = (int)ga, g[1] = (int)gb, g[2] = (int)gc;
   return true;
-}
-
-// three distinct rows with the lowest rotated to the front: the winding stays
-__device__ __forceinline__ void simplify_canonical(const int *g, int *t) {
-  const bool first = g[0] < g[1] && g[0] < g[2], second = !first && g[1] < g[2];
-  t[0] = first ? g[0] : second ? g[1] : g[2];
-  t[1] = first ? g[1] : second ? g[2] : g[0];
-  t[2] = first ? g[2] : second ? g[0] : g[1];
 }
 
 __device__ __forceinline__ unsigned long long simplify_hash(const int *t) {
@@ -129,25 +121,16 @@ __global__ __launch_bounds__(MS_THREADS) void simplify_quadric_kernel(const floa
                                                                       float oz, unsigned long long *__restrict__ quad) {
   const long r = (long)blockIdx.x * MS_THREADS + threadIdx.x;
   if (r >= f) return;
-  const int64_t in[3] = {faces[r * 3], faces[r * 3 + 1], faces[r * 3 + 2]};
-  if (!(in[0] >= 0 && in[0] < m && in[1] >= 0 && in[1] < m && in[2] >= 0 && in[2] < m)) return;
-  // the lowest row to the front: the normal's bits do not depend on which corner the face happens to start with (a
-  // face with two equal rows has a cross product of exactly zero whichever way it is turned)
-  const bool lead0 = in[0] <= in[1] && in[0] <= in[2], lead1 = !lead0 && in[1] <= in[2];
-  const int64_t row[3] = {lead0 ? in[0] : lead1 ? in[1] : in[2], lead0 ? in[1] : lead1 ? in[2] : in[0],
-                          lead0 ? in[2] : lead1 ? in[0] : in[1]};
+  int64_t in[3], row[3];
+  if (!face_rows(faces, r, m, in)) return;
+  face_lead(in, row);                                    // the normal's bits do not depend on the corner the face starts with
   float pf[3][3];
+  if (!face_points(vertices, row, pf)) return;
   double p[3][3];
-  bool finite = true;
 #pragma unroll
   for (int j = 0; j < 3; ++j)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      pf[j][k] = vertices[row[j] * 3 + k];
-      finite = finite && isfinite(pf[j][k]);
-      p[j][k] = (double)pf[j][k];
-    }
-  if (!finite) return;
+    for (int k = 0; k < 3; ++k) p[j][k] = (double)pf[j][k];
   int g[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -155,14 +138,11 @@ __global__ __launch_bounds__(MS_THREADS) void simplify_quadric_kernel(const floa
     if (c < 0 || c >= clusters) return;                  // (a finite vertex always has a cluster once the status is clear)
     g[j] = (int)c;
   }
-  const double ab[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-  const double ac[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-  const double cx = ab[1] * ac[2] - ab[2] * ac[1];
-  const double cy = ab[2] * ac[0] - ab[0] * ac[2];
-  const double cz = ab[0] * ac[1] - ab[1] * ac[0];
-  const double len = sqrt((cx * cx + cy * cy) + cz * cz);
+  double cr[3];
+  face_cross(p, cr);
+  const double len = sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
   if (!(len > 0.0 && len <= 1.7e308)) return;            // no area (or no finite normal): adds nothing
-  const double n[3] = {cx / len, cy / len, cz / len};
+  const double n[3] = {cr[0] / len, cr[1] / len, cr[2] / len};
   const long long qa[6] = {simplify_quantise(n[0] * n[0]), simplify_quantise(n[0] * n[1]), simplify_quantise(n[0] * n[2]),
                            simplify_quantise(n[1] * n[1]), simplify_quantise(n[1] * n[2]), simplify_quantise(n[2] * n[2])};
   const float o[3] = {ox, oy, oz};
@@ -272,7 +252,7 @@ __global__ __launch_bounds__(MS_THREADS) void simplify_insert_kernel(const int64
   int g[3], mine[3];
   int found = -1;
   if (simplify_face_clusters(faces, cid, m, clusters, r, g) && g[0] != g[1] && g[1] != g[2] && g[0] != g[2]) {
-    simplify_canonical(g, mine);
+    face_lead(g, mine);                                  // the canonical triple: three distinct ids, the winding stays
     const size_t mask = fslots - 1;
     size_t h = (size_t)simplify_hash(mine) & mask;
     for (size_t probe = 0; probe < fslots; ++probe) {
@@ -285,7 +265,7 @@ __global__ __launch_bounds__(MS_THREADS) void simplify_insert_kernel(const int64
       // occupied, perhaps since the swap just failed: the same slot is examined.  Its row may fall, its class cannot.
       int og[3], theirs[3];
       simplify_face_clusters(faces, cid, m, clusters, (long)seen, og);   // (an inserted face: always true)
-      simplify_canonical(og, theirs);
+      face_lead(og, theirs);
       if (theirs[0] == mine[0] && theirs[1] == mine[1] && theirs[2] == mine[2]) {
         atomicMin(ftable + h, (int)r);
         found = (int)h;
@@ -384,7 +364,7 @@ inline unsigned simplify_blocks(long n) { return (unsigned)((n + MS_THREADS - 1)
 }  // namespace mvsn
 
 extern "C" size_t mvsn_mesh_simplify_workspace_bytes(long n_vertices, long n_faces) {
-  if (n_vertices <= 0 || n_vertices > mvsn::MS_MAX || n_faces < 0 || n_faces > mvsn::MS_MAX) return 0;
+  if (n_vertices <= 0 || n_vertices > mvsn::MESH_MAX_ROWS || n_faces < 0 || n_faces > mvsn::MESH_MAX_ROWS) return 0;
   return mvsn::simplify_layout(n_vertices, n_faces).bytes;
 }
 
@@ -394,11 +374,10 @@ extern "C" int mvsn_mesh_simplify_assign(const float *vertices, long n_vertices,
   using namespace mvsn;
   MVSN_REQUIRE(vertices && result, MVSN_E_BADARG, "mvsn_mesh_simplify_assign: null pointer");
   MVSN_REQUIRE(n_vertices > 0, MVSN_E_BADARG, "mvsn_mesh_simplify_assign: %ld vertices", n_vertices);
-  MVSN_REQUIRE(n_vertices <= MS_MAX, MVSN_E_TOOLARGE, "mvsn_mesh_simplify_assign: %ld vertices (at most 2^31 - 1)",
+  MVSN_REQUIRE(n_vertices <= MESH_MAX_ROWS, MVSN_E_TOOLARGE, "mvsn_mesh_simplify_assign: %ld vertices (at most 2^31 - 1)",
                n_vertices);
   const size_t need = mvsn_voxel_workspace_bytes(n_vertices);
-  MVSN_REQUIRE(workspace && workspace_bytes >= need, MVSN_E_WORKSPACE,
-               "mvsn_mesh_simplify_assign: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  if (int e = workspace_check("mvsn_mesh_simplify_assign", "workspace", workspace, workspace_bytes, need)) return e;
   return mvsn_voxel_assign(vertices, n_vertices, voxel_size, inv_voxel_size, origin_x, origin_y, origin_z, result,
                            workspace, need, stream);
 }
@@ -413,14 +392,12 @@ extern "C" int mvsn_mesh_simplify_mark(const float *vertices, const float *norma
   MVSN_REQUIRE(vertices && result && workspace, MVSN_E_BADARG, "mvsn_mesh_simplify_mark: null pointer");
   MVSN_REQUIRE(m > 0 && f >= 0 && clusters > 0 && clusters <= m && (f == 0 || faces), MVSN_E_BADARG,
                "mvsn_mesh_simplify_mark: %ld clusters of %ld vertices, %ld faces", clusters, m, f);
-  MVSN_REQUIRE(m <= MS_MAX && f <= MS_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(m <= MESH_MAX_ROWS && f <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "mvsn_mesh_simplify_mark: %ld vertices, %ld faces (at most 2^31 - 1 of either)", m, f);
   MVSN_REQUIRE(placement == MS_MEAN || placement == MS_QUADRIC, MVSN_E_BADARG,
                "mvsn_mesh_simplify_mark: placement %d (0 = mean, 1 = quadric)", placement);
   const SimplifyLayout l = simplify_layout(m, f);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_simplify_mark: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "mvsn_mesh_simplify_mark: workspace not 16-byte aligned");
+  if (int e = workspace_check("mvsn_mesh_simplify_mark", "workspace", workspace, workspace_bytes, l.bytes)) return e;
   char *ws = (char *)workspace;
   unsigned long long *accum = (unsigned long long *)(ws + l.accum), *quad = (unsigned long long *)(ws + l.quad);
   float *cpoints = (float *)(ws + l.cpoints), *cnormals = (float *)(ws + l.cnormals);
@@ -484,15 +461,14 @@ extern "C" int mvsn_mesh_simplify_emit(const int64_t *faces, long n_vertices, lo
                    out_faces_n >= 0 && out_faces_n <= f,
                MVSN_E_BADARG, "mvsn_mesh_simplify_emit: %ld of %ld clusters of %ld vertices, %ld of %ld faces",
                out_vertices_n, clusters, m, out_faces_n, f);
-  MVSN_REQUIRE(m <= MS_MAX && f <= MS_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(m <= MESH_MAX_ROWS && f <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "mvsn_mesh_simplify_emit: %ld vertices, %ld faces (at most 2^31 - 1 of either)", m, f);
   MVSN_REQUIRE(out_vertices_n == 0 || (out_vertices && count && first), MVSN_E_BADARG,
                "mvsn_mesh_simplify_emit: null vertex output");
   MVSN_REQUIRE(out_faces_n == 0 || (faces && out_faces && face_rows), MVSN_E_BADARG,
                "mvsn_mesh_simplify_emit: null face output");
   const SimplifyLayout l = simplify_layout(m, f);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_simplify_emit: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
+  if (int e = workspace_check("mvsn_mesh_simplify_emit", "workspace", workspace, workspace_bytes, l.bytes)) return e;
   char *ws = (char *)workspace;                          // (crow, a section of it, is written here)
   const hipStream_t st = (hipStream_t)stream;
   const int64_t *cid = (const int64_t *)(ws + l.cid);

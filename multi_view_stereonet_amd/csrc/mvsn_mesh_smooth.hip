@@ -28,12 +28,11 @@
 #pragma clang fp contract(off)
 #include "mvsn_common.h"
 #include "mvsn_geom.h"
+#include "mvsn_mesh.h"
 
 namespace mvsn {
 
 constexpr int SM_THREADS = 256;                         // one vertex, edge or face per thread
-constexpr long SM_MAX = 0x7fffffffL;                    // vertices and faces
-constexpr long SM_MAX_EDGES = 0x7fffffffL;              // (at most 3 faces' worth of a mesh mvsn_mesh_edges takes)
 constexpr long SM_MAX_ITERATIONS = 10000;
 constexpr double SM_CLAMP = 2147483648.0;               // 2^31
 constexpr int SM_NONFINITE = 2, SM_PINNED = 1;          // the flags of a vertex
@@ -226,28 +225,12 @@ inline NormalsLayout normals_layout(long m) {
 __device__ __forceinline__ bool normals_cross(const float *__restrict__ vertices, long m,
                                               const int64_t *__restrict__ faces, long r, int64_t *row, double *c,
                                               double *len) {
-  const int64_t in[3] = {faces[r * 3], faces[r * 3 + 1], faces[r * 3 + 2]};
-  if (!(in[0] >= 0 && in[0] < m && in[1] >= 0 && in[1] < m && in[2] >= 0 && in[2] < m)) return false;
-  const bool lead0 = in[0] <= in[1] && in[0] <= in[2], lead1 = !lead0 && in[1] <= in[2];
-  row[0] = lead0 ? in[0] : lead1 ? in[1] : in[2];
-  row[1] = lead0 ? in[1] : lead1 ? in[2] : in[0];
-  row[2] = lead0 ? in[2] : lead1 ? in[0] : in[1];
+  int64_t in[3];
+  if (!face_rows(faces, r, m, in)) return false;
+  face_lead(in, row);
   double p[3][3];
-  bool finite = true;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float v = vertices[row[j] * 3 + k];
-      finite = finite && isfinite(v);
-      p[j][k] = (double)v;
-    }
-  if (!finite) return false;
-  const double ab[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-  const double ac[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-  c[0] = ab[1] * ac[2] - ab[2] * ac[1];
-  c[1] = ab[2] * ac[0] - ab[0] * ac[2];
-  c[2] = ab[0] * ac[1] - ab[1] * ac[0];
+  if (!face_points(vertices, row, p)) return false;
+  face_cross(p, c);
   *len = sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
   return *len > 0.0 && *len <= 1.7e308;
 }
@@ -323,7 +306,7 @@ inline unsigned smooth_blocks(long n) { return (unsigned)((n + SM_THREADS - 1) /
 }  // namespace mvsn
 
 extern "C" size_t mvsn_mesh_smooth_workspace_bytes(long n_vertices) {
-  if (n_vertices <= 0 || n_vertices > mvsn::SM_MAX) return 0;
+  if (n_vertices <= 0 || n_vertices > mvsn::MESH_MAX_ROWS) return 0;
   return mvsn::smooth_layout(n_vertices).bytes;
 }
 
@@ -334,7 +317,7 @@ extern "C" int mvsn_mesh_smooth(const float *vertices, long n_vertices, const in
   const long m = n_vertices, e = n_edges;
   MVSN_REQUIRE(vertices && out_vertices && workspace, MVSN_E_BADARG, "mvsn_mesh_smooth: null pointer");
   MVSN_REQUIRE(m > 0 && e >= 0 && (e == 0 || edges), MVSN_E_BADARG, "mvsn_mesh_smooth: %ld vertices, %ld edges", m, e);
-  MVSN_REQUIRE(m <= SM_MAX && e <= SM_MAX_EDGES, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(m <= MESH_MAX_ROWS && e <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,   // (mvsn_mesh_edges emits fewer: 3 per face)
                "mvsn_mesh_smooth: %ld vertices, %ld edges (at most 2^31 - 1 of either)", m, e);
   MVSN_REQUIRE(method == SM_LAPLACIAN || method == SM_TAUBIN, MVSN_E_BADARG,
                "mvsn_mesh_smooth: method %d (0 = laplacian, 1 = taubin)", method);
@@ -343,9 +326,7 @@ extern "C" int mvsn_mesh_smooth(const float *vertices, long n_vertices, const in
   MVSN_REQUIRE(lam > 0.0 && lam <= 1.0 && mu >= -2.0 && mu < 0.0, MVSN_E_BADARG,
                "mvsn_mesh_smooth: lam %g (0 < lam <= 1), mu %g (-2 <= mu < 0)", lam, mu);
   const SmoothLayout l = smooth_layout(m);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_smooth: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "mvsn_mesh_smooth: workspace not 16-byte aligned");
+  if (int err = workspace_check("mvsn_mesh_smooth", "workspace", workspace, workspace_bytes, l.bytes)) return err;
   char *ws = (char *)workspace;
   SmoothParams *params = (SmoothParams *)(ws + l.params);
   double *x = (double *)(ws + l.x);
@@ -380,7 +361,7 @@ extern "C" int mvsn_mesh_smooth(const float *vertices, long n_vertices, const in
 }
 
 extern "C" size_t mvsn_mesh_normals_workspace_bytes(long n_vertices) {
-  if (n_vertices <= 0 || n_vertices > mvsn::SM_MAX) return 0;
+  if (n_vertices <= 0 || n_vertices > mvsn::MESH_MAX_ROWS) return 0;
   return mvsn::normals_layout(n_vertices).bytes;
 }
 
@@ -392,12 +373,10 @@ extern "C" int mvsn_mesh_normals(const float *vertices, long n_vertices, const i
   MVSN_REQUIRE(vertices && vertex_normals && workspace, MVSN_E_BADARG, "mvsn_mesh_normals: null pointer");
   MVSN_REQUIRE(m > 0 && f >= 0 && (f == 0 || (faces && face_normals && face_area)), MVSN_E_BADARG,
                "mvsn_mesh_normals: %ld vertices, %ld faces", m, f);
-  MVSN_REQUIRE(m <= SM_MAX && f <= SM_MAX, MVSN_E_TOOLARGE,
+  MVSN_REQUIRE(m <= MESH_MAX_ROWS && f <= MESH_MAX_ROWS, MVSN_E_TOOLARGE,
                "mvsn_mesh_normals: %ld vertices, %ld faces (at most 2^31 - 1 of either)", m, f);
   const NormalsLayout l = normals_layout(m);
-  MVSN_REQUIRE(workspace_bytes >= l.bytes, MVSN_E_WORKSPACE, "mvsn_mesh_normals: workspace of %zu bytes, %zu needed",
-               workspace_bytes, l.bytes);
-  MVSN_REQUIRE(((uintptr_t)workspace & 15) == 0, MVSN_E_BADARG, "mvsn_mesh_normals: workspace not 16-byte aligned");
+  if (int e = workspace_check("mvsn_mesh_normals", "workspace", workspace, workspace_bytes, l.bytes)) return e;
   char *ws = (char *)workspace;
   unsigned long long *vmax = (unsigned long long *)(ws + l.vmax), *nsum = (unsigned long long *)(ws + l.nsum);
   const hipStream_t st = (hipStream_t)stream;

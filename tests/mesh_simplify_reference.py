@@ -259,6 +259,9 @@ def _bad_faces():
     f[20] = (-1, 2, 3)
     f[21] = (2, m, 3)
     f[22] = (1, 2, m + 5)
+    f[30] = (2 ** 40, 2, 3)                 # rows whose low 32 bits are a valid row, or a negative int32: the compare
+    f[31] = (1, -2 ** 40, 3)                # has to be on the int64
+    f[32] = (1, 2, 2 ** 31)
     f[59] = (0, 1, -7)
     return _case(v, f, 0.7)
 

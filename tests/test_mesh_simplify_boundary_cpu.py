@@ -99,7 +99,7 @@ def test_entries_in_header_binding_build_and_binary():
     assert build.SOURCES.count("mvsn_mesh_simplify.hip") == 1
     with open(os.path.join(build.CSRC, "mvsn_mesh_simplify.hip")) as f:
         included = set(re.findall(r'#include "(mvsn_\w+\.h)"', f.read()))
-    assert included == {"mvsn_common.h", "mvsn_geom.h", "mvsn_voxel.h"} and included <= set(build.HEADERS)
+    assert included == {"mvsn_common.h", "mvsn_geom.h", "mvsn_mesh.h", "mvsn_voxel.h"} and included <= set(build.HEADERS)
     assert _native.ABI_VERSION == 7 and "#define MVSN_ABI_VERSION 7" in header.replace("  ", " ")
     for name in ENTRIES:
         assert re.search(r"\b%s\(" % name, header), name

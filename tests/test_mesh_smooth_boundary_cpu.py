@@ -163,8 +163,8 @@ def test_answers_that_need_no_launch(no_launch):
 def test_entries_in_header_binding_build_and_binary():
     with open(os.path.join(ROOT, "include", "mvsn_hip.h")) as f:
         header = f.read()
-    for source, headers in (("mvsn_mesh_edges.hip", {"mvsn_common.h", "mvsn_geom.h", "mvsn_voxel.h"}),
-                            ("mvsn_mesh_smooth.hip", {"mvsn_common.h", "mvsn_geom.h"})):
+    for source, headers in (("mvsn_mesh_edges.hip", {"mvsn_common.h", "mvsn_geom.h", "mvsn_mesh.h", "mvsn_voxel.h"}),
+                            ("mvsn_mesh_smooth.hip", {"mvsn_common.h", "mvsn_geom.h", "mvsn_mesh.h"})):
         assert build.SOURCES.count(source) == 1
         with open(os.path.join(build.CSRC, source)) as f:
             text = f.read()
