@@ -878,6 +878,31 @@ int mvsn_tsdf_extract(const float *sdf_sum, const float *weight, const float *co
                       float *normals, uint8_t *colors, int64_t *faces, int64_t *cell, mvsn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Oriented points into the TSDF volume (tsdf.TSDFVolume.integrate_cloud; the semantics and every step are DESIGN.md
+ * section 31): the implicit moving-least-squares distance of the cloud, Hoppe's weighted tangent planes, added to the
+ * state of mvsn_tsdf_integrate.  points, normals (n,3) fp32 (normals outwards, used as given), weights (n) fp32 or NULL
+ * (1), colors (n,3) u8 with color_sum, or both NULL.  index_workspace is what mvsn_cloud_index_build made over points
+ * with cell; inv_cell = 1 / cell and r2 = cell * cell, each formed once in fp32.
+ *   Per voxel centre x = origin + (float)i * voxel_size (a multiply, then an add) and every row p within reach, d2 =
+ *   (dx dx + dy dy) + dz dz <= r2 of the fp32 differences dx = x - p (mvsn_cloud_nearest's relation), whose point is
+ *   finite, whose normal is finite and not (0,0,0) and whose weight w is finite and in (0, 256]:
+ *     q = d2 / r2, a = 1 - q, phi = a a, A = rint((phi w) 2^16); s = (dx nx + dy ny) + dz nz,
+ *     t = fmin(fmax(s, -trunc), trunc), T = rint((t / trunc) 2^20); every step one fp32 operation.
+ *   Exact 64-bit sums per voxel: the count, sum A, sum A T, sum A c per channel.  A voxel with sum A > 0 and at most
+ *   2^19 - 1 accepted rows gets, each number formed in fp64 and rounded once: weight += sum A 2^-16, sdf_sum +=
+ *   sum A T (trunc 2^-36), color_sum_c += (sum A c 2^-16) / 127.5 - sum A 2^-16; any other voxel keeps its bits.
+ *   No byte of the state depends on the order of the rows.  A memset and two launches, no atomics.
+ *   workspace: mvsn_tsdf_cloud_workspace_bytes(nx, ny, nz) bytes (0: dims outside the limits), 16-byte aligned: one
+ *   flag byte per brick of 8 x 8 x 8 voxels.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsn_tsdf_cloud_workspace_bytes(int nx, int ny, int nz);
+int mvsn_tsdf_cloud_integrate(const float *points, const float *normals, const float *weights, const uint8_t *colors,
+                              long n, const void *index_workspace, size_t index_workspace_bytes, float cell,
+                              float inv_cell, float r2, int nx, int ny, int nz, float voxel_size, float origin_x,
+                              float origin_y, float origin_z, float trunc, float *sdf_sum, float *weight,
+                              float *color_sum, void *workspace, size_t workspace_bytes, mvsn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ray-cast of the TSDF volume: the surface as cameras (K, T_cam_in_world) see it (tsdf.TSDFVolume.raycast; the
  * semantics, every fp32 step and the error bounds are DESIGN.md section 16).  The state is mvsn_tsdf_integrate's, dims of
  * at least 2 each; K, T_cam_in_world (V,4,4), K's bottom row taken to be (0,0,1); 1 <= V <= 65535, rows, cols <= 2^24,

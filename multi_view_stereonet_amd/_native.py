@@ -159,6 +159,9 @@ SIGNATURES = {
                                [ctypes.c_float] * 2 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
     "mvsn_tsdf_align": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_float] * 4 + [c_void_p] * 5 + [c_int] * 4 +
                         [ctypes.c_float] * 2 + [c_int, c_long, ctypes.c_double, c_void_p, c_size_t] + [c_void_p] * 4 + [c_void_p]),
+    "mvsn_tsdf_cloud_workspace_bytes": (c_size_t, [c_int] * 3),
+    "mvsn_tsdf_cloud_integrate": (c_int, [c_void_p] * 4 + [c_long, c_void_p, c_size_t] + [ctypes.c_float] * 3 + [c_int] * 3 +
+                                  [ctypes.c_float] * 5 + [c_void_p] * 3 + [c_void_p, c_size_t] + [c_void_p]),
     "mvsn_mesh_workspace_bytes": (c_size_t, [c_long] * 2),
     "mvsn_mesh_components_label": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mvsn_mesh_components_emit": (c_int, [c_void_p, c_long, c_long, c_void_p, c_size_t, c_long] + [c_void_p] * 5 + [c_void_p]),

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvsn_hip.so")
-SOURCES = ["mvsn_error.hip", "mvsn_setup.hip", "mvsn_warp.hip", "mvsn_chain.hip", "mvsn_chain_wino.hip", "mvsn_chain_band.hip", "mvsn_chain_slab.hip", "mvsn_chain_steps.hip", "mvsn_conv.hip", "mvsn_groupnorm.hip", "mvsn_conv_bf16x3.hip", "mvsn_conv_wino.hip", "mvsn_conv_to1.hip", "mvsn_misc.hip", "mvsn_consistency.hip", "mvsn_prepare.hip", "mvsn_metrics.hip", "mvsn_tower.hip", "mvsn_fusion.hip", "mvsn_voxel.hip", "mvsn_normals.hip", "mvsn_cloud.hip", "mvsn_cloud_register.hip", "mvsn_cloud_normals.hip", "mvsn_cloud_knn.hip", "mvsn_cloud_cluster.hip", "mvsn_cloud_fpfh.hip", "mvsn_cloud_match.hip", "mvsn_cloud_ransac.hip", "mvsn_cloud_render.hip", "mvsn_tsdf.hip", "mvsn_tsdf_raycast.hip", "mvsn_tsdf_align.hip", "mvsn_mesh.hip", "mvsn_mesh_sample.hip", "mvsn_mesh_nearest.hip", "mvsn_mesh_render.hip", "mvsn_mesh_simplify.hip", "mvsn_mesh_edges.hip", "mvsn_mesh_smooth.hip"]
+SOURCES = ["mvsn_error.hip", "mvsn_setup.hip", "mvsn_warp.hip", "mvsn_chain.hip", "mvsn_chain_wino.hip", "mvsn_chain_band.hip", "mvsn_chain_slab.hip", "mvsn_chain_steps.hip", "mvsn_conv.hip", "mvsn_groupnorm.hip", "mvsn_conv_bf16x3.hip", "mvsn_conv_wino.hip", "mvsn_conv_to1.hip", "mvsn_misc.hip", "mvsn_consistency.hip", "mvsn_prepare.hip", "mvsn_metrics.hip", "mvsn_tower.hip", "mvsn_fusion.hip", "mvsn_voxel.hip", "mvsn_normals.hip", "mvsn_cloud.hip", "mvsn_cloud_register.hip", "mvsn_cloud_normals.hip", "mvsn_cloud_knn.hip", "mvsn_cloud_cluster.hip", "mvsn_cloud_fpfh.hip", "mvsn_cloud_match.hip", "mvsn_cloud_ransac.hip", "mvsn_cloud_render.hip", "mvsn_tsdf.hip", "mvsn_tsdf_raycast.hip", "mvsn_tsdf_align.hip", "mvsn_tsdf_cloud.hip", "mvsn_mesh.hip", "mvsn_mesh_sample.hip", "mvsn_mesh_nearest.hip", "mvsn_mesh_render.hip", "mvsn_mesh_simplify.hip", "mvsn_mesh_edges.hip", "mvsn_mesh_smooth.hip"]
 
 
 def hipcc() -> str:

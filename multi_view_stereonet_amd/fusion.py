@@ -26,7 +26,9 @@ point by its FPFH histogram, ``feature_nearest`` (csrc/mvsn_cloud_match.hip) mat
 ``cloud_render`` (csrc/mvsn_cloud_render.hip) renders a cloud into posed cameras, the nearest point
 per pixel; ``cloud_visibility`` tests every point against depth maps for occlusion and reads per-view maps at the points
 that are seen, and ``cloud_colorize`` colours a bare cloud that way.  A dense TSDF volume that integrates the same
-depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh.
+depth maps and a mesh from it are in ``tsdf``; ``write_ply(faces=)`` writes such a mesh and
+``read_ply`` reads back what ``write_ply`` wrote, or an ASCII cloud from elsewhere, for ``tsdf.integrate_cloud``
+ to turn into a surface.
 
 Conventions: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world`` (V,4,4) maps camera
 coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel centres.
@@ -1674,3 +1676,147 @@ def write_ply(path: str, points, colors=None, confidence=None, normals=None, fac
             frec = np.empty(tri.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
             frec["n"], frec["v"] = 3, tri
             f.write(frec.tobytes())
+
+
+class PlyData(NamedTuple):
+    points: torch.Tensor             # (N,3) fp32
+    normals: Optional[torch.Tensor]  # (N,3) fp32, or None where the file has no nx, ny, nz
+    colors: Optional[torch.Tensor]   # (N,3) uint8, or None where the file has no red, green, blue
+    confidence: Optional[torch.Tensor]   # (N,) fp32, or None where the file has no confidence
+    faces: Optional[torch.Tensor]    # (F,3) int64, or None where the file has no face element
+
+
+_PLY_FLOATS = ("x", "y", "z", "nx", "ny", "nz", "confidence")
+_PLY_BYTES = ("red", "green", "blue")
+
+
+def _ply_header(data, path):
+    """(format, vertex count, vertex property names, face count or None, face index type or None, offset of the body)."""
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' line or no 'end_header' line)")
+    try:
+        lines = data[:end].decode("ascii").split("\n")[1:]
+    except UnicodeDecodeError:
+        raise ValueError(f"{path}: the header is not ASCII") from None
+    fmt, n, names, nf, face_type, element = None, None, [], None, None, None
+    for line in lines:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            if tok[1:] not in (["binary_little_endian", "1.0"], ["ascii", "1.0"]):
+                raise ValueError(f"{path}: format {' '.join(tok[1:])!r} is not understood (binary_little_endian 1.0 or "
+                                 "ascii 1.0)")
+            fmt = tok[1]
+        elif tok[0] == "element":
+            if len(tok) != 3 or not tok[2].isdigit():
+                raise ValueError(f"{path}: header line {line!r} is not understood")
+            element = tok[1]
+            if element == "vertex" and n is None and nf is None:
+                n = int(tok[2])
+            elif element == "face" and n is not None and nf is None:
+                nf = int(tok[2])
+            else:
+                raise ValueError(f"{path}: element {element!r} is not understood (one 'vertex', then at most one 'face')")
+        elif tok[0] == "property" and element == "vertex":
+            if len(tok) != 3 or (tok[2] in _PLY_FLOATS and tok[1] not in ("float", "float32")) or \
+                    (tok[2] in _PLY_BYTES and tok[1] not in ("uchar", "uint8")) or tok[2] not in _PLY_FLOATS + _PLY_BYTES:
+                raise ValueError(f"{path}: vertex property {' '.join(tok[1:])!r} is not understood (float x y z nx ny nz "
+                                 "confidence, uchar red green blue)")
+            if tok[2] in names:
+                raise ValueError(f"{path}: vertex property {tok[2]!r} appears twice")
+            names.append(tok[2])
+        elif tok[0] == "property" and element == "face":
+            if len(tok) != 5 or tok[1] != "list" or tok[2] not in ("uchar", "uint8") or \
+                    tok[3] not in ("int", "int32", "uint", "uint32") or tok[4] not in ("vertex_indices", "vertex_index") or \
+                    face_type is not None:
+                raise ValueError(f"{path}: face property {' '.join(tok[1:])!r} is not understood (list uchar int|uint "
+                                 "vertex_indices)")
+            face_type = "<u4" if tok[3].startswith("u") else "<i4"
+        else:
+            raise ValueError(f"{path}: header line {line!r} is not understood")
+    if fmt is None or n is None:
+        raise ValueError(f"{path}: the header has no format line or no vertex element")
+    for group in (("x", "y", "z"), ("nx", "ny", "nz"), _PLY_BYTES):
+        have = [g in names for g in group]
+        if any(have) != all(have) or (group[0] == "x" and not all(have)):
+            raise ValueError(f"{path}: vertex properties {names} are not understood: {', '.join(group)} go together"
+                             + (" and are required" if group[0] == "x" else ""))
+    if nf is not None and face_type is None:
+        raise ValueError(f"{path}: the face element has no vertex_indices property")
+    return fmt, n, names, nf, face_type, end + len(b"end_header\n")
+
+
+def read_ply(path: str) -> PlyData:
+    """Read what ``write_ply`` writes, as CPU tensors: ``format binary_little_endian 1.0``; per vertex float ``x y z``,
+    optionally float ``nx ny nz``, uchar ``red green blue`` and float ``confidence``, in any order; optionally an
+    ``element face`` with ``property list uchar int|uint vertex_indices`` whose faces are all triangles.  ``format ascii
+    1.0`` with the same properties is read too (ground-truth clouds are often ASCII).  Anything else raises ValueError
+    with a message that names what was not understood: other elements, other properties or property types, big-endian
+    data, a face that is no triangle, an index outside the vertices, a file that ends early or goes on after its last
+    element.  Host only, pure numpy."""
+    with open(path, "rb") as f:
+        data = f.read()
+    fmt, n, names, nf, face_type, at = _ply_header(data, path)
+    dtype = np.dtype([(name, "u1" if name in _PLY_BYTES else "<f4") for name in names])
+    tri = None
+    if fmt == "ascii":
+        tok = data[at:].split()
+        need = n * len(names)
+        if len(tok) < need:
+            raise ValueError(f"{path}: truncated: {len(tok)} numbers, the {n} vertices need {need}")
+        try:
+            table = np.array(tok[:need], dtype=np.float64).reshape(n, len(names))
+        except ValueError:
+            raise ValueError(f"{path}: a vertex value is not a number") from None
+        rec = np.empty(n, dtype=dtype)
+        for c, name in enumerate(names):
+            col = table[:, c]
+            if name in _PLY_BYTES and not ((col >= 0) & (col <= 255) & (col == np.floor(col))).all():
+                raise ValueError(f"{path}: a {name} value is not an integer in [0, 255]")
+            with np.errstate(all="ignore"):
+                rec[name] = col
+        rest = tok[need:]
+        if nf is not None:
+            if len(rest) < 4 * nf:
+                raise ValueError(f"{path}: truncated: {len(rest)} numbers, the {nf} faces need {4 * nf}")
+            try:
+                ftab = np.array(rest[:4 * nf], dtype=np.int64).reshape(nf, 4)
+            except (ValueError, OverflowError):
+                raise ValueError(f"{path}: a face value is not an integer") from None
+            if (ftab[:, 0] != 3).any():
+                raise ValueError(f"{path}: face {int(np.argmax(ftab[:, 0] != 3))} has {int(ftab[np.argmax(ftab[:, 0] != 3), 0])} "
+                                 "vertices: only triangles are understood")
+            tri, rest = ftab[:, 1:], rest[4 * nf:]
+        if rest:
+            raise ValueError(f"{path}: {len(rest)} numbers after the last element")
+    else:
+        body = n * dtype.itemsize
+        if len(data) < at + body:
+            raise ValueError(f"{path}: truncated: {len(data) - at} bytes, the {n} vertices need {body}")
+        rec = np.frombuffer(data, dtype=dtype, count=n, offset=at)
+        at += body
+        if nf is not None:
+            fdtype = np.dtype([("n", "u1"), ("v", face_type, (3,))])
+            got = np.frombuffer(data, dtype=fdtype, count=min(nf, (len(data) - at) // fdtype.itemsize), offset=at)
+            if (got["n"] != 3).any():
+                bad = int(np.argmax(got["n"] != 3))
+                raise ValueError(f"{path}: face {bad} has {int(got['n'][bad])} vertices: only triangles are understood")
+            if len(got) < nf:
+                raise ValueError(f"{path}: truncated: {len(data) - at} bytes, the {nf} faces need {nf * fdtype.itemsize}")
+            tri = got["v"].astype(np.int64)
+            at += nf * fdtype.itemsize
+        if at != len(data):
+            raise ValueError(f"{path}: {len(data) - at} bytes after the last element")
+    if tri is not None and tri.size and (tri.min() < 0 or tri.max() >= n):
+        raise ValueError(f"{path}: a face indexes outside the {n} vertices")
+
+    def columns(group):
+        if group[0] not in names:
+            return None
+        return torch.from_numpy(np.stack([rec[g] for g in group], axis=1).copy() if n else
+                                np.zeros((0, len(group)), rec.dtype[group[0]]))
+    conf = torch.from_numpy(rec["confidence"].copy()) if "confidence" in names else None
+    return PlyData(columns(("x", "y", "z")), columns(("nx", "ny", "nz")), columns(_PLY_BYTES), conf,
+                   torch.from_numpy(np.ascontiguousarray(tri).reshape(-1, 3)) if tri is not None else None)

@@ -8,7 +8,9 @@ truncated signed distances the views saw at it, so a surface that k views saw is
 carved, and the gaps between pixels are filled.  ``TSDFVolume.integrate`` adds views, ``extract_mesh`` gives vertices
 with normals and colours and the triangles between them, ``fusion.write_ply(..., faces=)`` saves them, ``raycast``
 renders the surface as a camera sees it, and ``align`` refines the poses of depth maps against it (section 17,
-csrc/mvsn_tsdf_align.hip).
+csrc/mvsn_tsdf_align.hip).  ``integrate_cloud`` is the other way into the volume: oriented points instead of posed depth
+maps (section 31, csrc/mvsn_tsdf_cloud.hip), so a cloud that was merged, cleaned, registered or read from a file becomes
+a surface too, and ``TSDFVolume.around`` makes the volume that holds a cloud.
 
 Conventions are ``fusion``'s: ``K`` (V,4,4) with the top-left 3x3 used and a bottom row of (0,0,1); ``T_cam_in_world``
 (V,4,4) maps camera coordinates to world coordinates; pixel (x, y) = (column, row) with integer values at pixel
@@ -20,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .fusion import _check_frames, _check_views, _origin_f32, _positive_f32
+from .fusion import (_check_frames, _check_views, _cloud_index_build, _origin_f32, _positive_f32,
+                     _raise_cloud_status, check_cloud, cloud_radius_scalars)
 
 MAX_VOXELS = 2 ** 31 - 1
 MAX_EXTENT = 2 ** 24                 # voxels along an axis, rows and columns of a map: every index is an exact float32
@@ -140,6 +143,60 @@ class TSDFVolume:
                 _native.ptr(f32(T_cam_in_world)), V, H, W, nx, ny, nz, float(self.voxel_size), float(self.origin[0]),
                 float(self.origin[1]), float(self.origin[2]), float(self.trunc), float(md), _native.ptr(self.sdf_sum),
                 _native.ptr(self.weight), _native.ptr(self.color_sum), _native.stream()), "mvsn_tsdf_integrate")
+
+    @classmethod
+    def around(cls, points: torch.Tensor, voxel_size: float, trunc: float, *, padding: Optional[float] = None,
+               color: bool = False) -> "TSDFVolume":
+        """The smallest volume on the ``voxel_size`` lattice (voxel centres at integer multiples of ``voxel_size``) that
+        holds the finite rows of ``points`` (N,3) fp32 plus ``padding`` (a finite number >= 0; None: ``trunc``) on every
+        side, on the points' device.  The origin is rounded once to fp32.  One host read: the bounding box.  ValueError
+        where no row is finite or the box exceeds the volume's limits (2^31 - 1 voxels, 2^24 along an axis)."""
+        check_cloud("points", points)
+        v = _positive_f32(voxel_size, "voxel_size")[0]
+        tr = _positive_f32(trunc, "trunc")[0]
+        with np.errstate(all="ignore"):
+            try:
+                pad = np.float32(tr if padding is None else padding)
+            except (TypeError, ValueError):
+                raise ValueError(f"padding must be a finite number >= 0, got {padding!r}") from None
+        if not (np.isfinite(pad) and pad >= 0):
+            raise ValueError(f"padding must be a finite number >= 0, got {padding!r}")
+        box = None
+        if int(points.shape[0]) > 0:
+            p = points.detach()
+            finite = torch.isfinite(p).all(dim=1, keepdim=True)
+            lo = torch.where(finite, p, torch.full_like(p, float("inf"))).amin(dim=0)
+            hi = torch.where(finite, p, torch.full_like(p, float("-inf"))).amax(dim=0)
+            box = torch.stack([lo, hi]).to(torch.float64).cpu().numpy()     # the one host read
+        if box is None or not np.isfinite(box).all():
+            raise ValueError("points hold no finite row: there is nothing to put a volume around")
+        vs, pd = float(v), float(pad)
+        first = np.floor((box[0] - pd) / vs)
+        last = np.ceil((box[1] + pd) / vs)
+        with np.errstate(all="ignore"):
+            origin = (first * vs).astype(np.float32)
+        if not np.isfinite(origin).all() or not (np.abs(first) < 2.0 ** 52).all() or not (np.abs(last) < 2.0 ** 52).all():
+            raise ValueError(f"the box of the points, {box[0]} to {box[1]}, has no lattice of voxel_size {vs:g}")
+        # (the rounding of the origin to fp32 may have moved it past the box: one more voxel on that side)
+        first = first - (origin.astype(np.float64) > box[0] - pd)
+        with np.errstate(all="ignore"):
+            origin = (first * vs).astype(np.float32)
+        dims = last - first + 1.0
+        dims = dims + (origin.astype(np.float64) + (dims - 1.0) * vs < box[1] + pd)
+        if (dims > MAX_EXTENT).any() or float(dims[0]) * float(dims[1]) * float(dims[2]) > MAX_VOXELS:
+            raise ValueError(f"the box of the points plus padding needs {int(dims[0])} x {int(dims[1])} x {int(dims[2])} "
+                             f"voxels of {vs:g}: at most 2^31 - 1 voxels and 2^24 along an axis")
+        return cls(tuple(int(d) for d in dims), v, origin, tr, device=points.device, color=color)
+
+    def integrate_cloud(self, points: torch.Tensor, normals: torch.Tensor, radius: float, *,
+                        weights: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None) -> None:
+        """Add the oriented cloud ``points`` (N,3) fp32 with ``normals`` (N,3) fp32 to the volume: the implicit
+        moving-least-squares distance (Hoppe's weighted tangent planes), so a cloud that ``voxel_merge`` merged, a filter
+        cleaned, ``cloud_register`` moved or ``read_ply`` read becomes a surface that ``extract_mesh``, ``raycast`` and
+        ``align`` work on.  ``integrate_cloud`` (module level) states every step; DESIGN.md section 31 has the rest.
+        The call adds to whatever the volume holds: depth maps and clouds can go into one volume."""
+        integrate_cloud(self.sdf_sum, self.weight, self.color_sum, self.voxel_size, self.origin, self.trunc, points,
+                        normals, radius, weights=weights, colors=colors)
 
     def extract_mesh(self, min_weight: float = 1.0) -> TSDFMesh:
         """The surface of the volume by Surface Nets, a pure function of the state tensors.  A voxel is observed when
@@ -451,3 +508,82 @@ def align(sdf_sum: torch.Tensor, weight: torch.Tensor, voxel_size: float, origin
             pv, _native.ptr(ws), ws_bytes, _native.ptr(out.T_cam_in_world), _native.ptr(out.history),
             _native.ptr(out.status), _native.ptr(out.information), _native.stream()), "mvsn_tsdf_align")
     return out
+
+
+def integrate_cloud(sdf_sum: torch.Tensor, weight: torch.Tensor, color_sum: Optional[torch.Tensor], voxel_size: float,
+                    origin: Sequence[float], trunc: float, points: torch.Tensor, normals: torch.Tensor, radius: float, *,
+                    weights: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None) -> None:
+    """``TSDFVolume.integrate_cloud`` on state tensors of any origin, updated in place (they must be contiguous).
+
+    ``normals`` point outwards, are expected to be unit length and are used as given; the volume is positive towards
+    the cameras, so ``n . (x - p)`` is positive outside.  ``weights`` (N,) fp32 (1 without), ``colors`` (N,3) uint8
+    (which need ``color_sum``, and the reverse, as ``images`` in ``integrate``).  A row takes part when its point is
+    finite, its normal is finite and not (0,0,0) (this project's "no normal") and its weight is finite and in (0, 256];
+    any other row is skipped.  With h = float32(radius), r2 = h*h and the voxel centre ``x = origin + float32(i) *
+    voxel_size`` (a multiply, then an add), a row reaches the voxel when ``d2 = (dx*dx + dy*dy) + dz*dz <= r2`` for the
+    fp32 differences ``dx = x - p``: ``cloud_nearest``'s relation.  Per accepted row, every step one fp32 operation:
+    ``phi = (1 - d2/r2)^2``, ``A = rint(phi*w * 2^16)``, ``s = (dx*nx + dy*ny) + dz*nz``, ``t = min(max(s, -trunc),
+    trunc)``, ``T = rint(t/trunc * 2^20)``.  The count, sum A, sum A*T and sum A*c per colour channel are exact 64-bit
+    integers, so no byte of the state depends on the order of the rows, and the call is bitwise reproducible.  A voxel
+    with sum A > 0 gets, each number formed in fp64 and rounded once to fp32: ``weight += sum A * 2^-16``, ``sdf_sum +=
+    sum A*T * trunc * 2^-36`` and ``color_sum += (sum A*c * 2^-16) / 127.5 - sum A * 2^-16``; every other voxel keeps its
+    bits, and so does a voxel with more than 2^19 - 1 accepted rows (the sums could overflow).  Because each call rounds
+    the state once, two calls are not bit-identical to one call on the concatenated clouds.  Two sheets of points closer
+    than ``radius`` blend into one.
+
+    The points go on ``cloud_nearest``'s grid with cell = ``radius``: the time grows with (rows per cell) x (cells
+    visited, 27 almost always) per voxel near the cloud, voxels in bricks of 8 x 8 x 8 far from every row cost a byte,
+    and a finite point more than 2^20 cells of ``radius`` from the origin raises ValueError.  Everything is validated
+    here, before any launch; the one host synchronisation is the read of the index build's status word, after
+    everything is enqueued."""
+    nx, ny, nz, dev = _check_state(sdf_sum, weight, color_sum)
+    for name, t in (("sdf_sum", sdf_sum), ("weight", weight), ("color_sum", color_sum)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: it is updated in place")
+    v = _positive_f32(voxel_size, "voxel_size")[0]
+    tr = _positive_f32(trunc, "trunc")[0]
+    o = _origin_f32(origin)
+    check_cloud("points", points)
+    N = int(points.shape[0])
+    if points.device != dev:
+        raise ValueError(f"points is on {points.device}, the volume on {dev}")
+    if not torch.is_tensor(normals) or tuple(normals.shape) != (N, 3) or normals.dtype != torch.float32:
+        raise ValueError(f"normals must be a ({N},3) float32 tensor like points")
+    if normals.device != dev:
+        raise ValueError(f"normals is on {normals.device}, the volume on {dev}")
+    h, inv, r2 = cloud_radius_scalars(radius, "radius")
+    if weights is not None:
+        if not torch.is_tensor(weights) or tuple(weights.shape) != (N,) or weights.dtype != torch.float32:
+            raise ValueError(f"weights must be a ({N},) float32 tensor, one per point")
+        if weights.device != dev:
+            raise ValueError(f"weights is on {weights.device}, the volume on {dev}")
+    if (colors is not None) != (color_sum is not None):
+        raise ValueError("colors need a volume made with color=True, and such a volume needs colors")
+    if colors is not None:
+        if not torch.is_tensor(colors) or tuple(colors.shape) != (N, 3) or colors.dtype != torch.uint8:
+            raise ValueError(f"colors must be a ({N},3) uint8 tensor like points")
+        if colors.device != dev:
+            raise ValueError(f"colors is on {colors.device}, the volume on {dev}")
+    if N == 0:                         # nothing to add, nothing to launch
+        return
+    if not points.is_cuda:
+        raise RuntimeError("integrate_cloud runs on HIP devices only: make the volume and the cloud on 'cuda' "
+                           "(there is no CPU implementation)")
+    lib = _native.load()
+    # (held in names until the launches are queued: a copy must not be freed and its block handed out again)
+    p, nr = points.detach().contiguous(), normals.detach().contiguous()
+    w = weights.detach().contiguous() if weights is not None else None
+    c = colors.detach().contiguous() if colors is not None else None
+    flag_bytes = lib.mvsn_tsdf_cloud_workspace_bytes(nx, ny, nz)
+    flags = torch.empty(flag_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.stream()
+        ws, ws_bytes, status = _cloud_index_build(lib, p, N, h, inv, dev, st)
+        _native.check(lib.mvsn_tsdf_cloud_integrate(
+            _native.ptr(p), _native.ptr(nr), _native.ptr(w), _native.ptr(c), N, _native.ptr(ws), ws_bytes, float(h),
+            float(inv), float(r2), nx, ny, nz, float(v), float(o[0]), float(o[1]), float(o[2]), float(tr),
+            _native.ptr(sdf_sum.detach()), _native.ptr(weight.detach()),
+            _native.ptr(color_sum.detach() if color_sum is not None else None), _native.ptr(flags), flag_bytes, st),
+            "mvsn_tsdf_cloud_integrate")
+        bits = int(status.item())      # the one host synchronisation, after everything is enqueued
+    _raise_cloud_status(bits, h, "integrate_cloud")   # (cloud_nearest's errors: the points are the index's target, radius its max_dist)

@@ -101,7 +101,14 @@ Taubin, SMOOTH_ITERATIONS iterations, the edges reused) and recomputes its norma
 "smooth", M, F, E and the border and non-manifold edge counts, ms per mesh_edges, ms per smoothing call and per step
 (a call takes 2 SMOOTH_ITERATIONS steps), ms per mesh_normals, and next to them the same smoothing composed from torch
 ops (torch.unique over the sorted pairs of the sides, then per step index_add_ of the neighbour differences in fp64) with
-its ms for the edges, per call and per step, and how far its vertices are from the device's."""
+its ms for the edges, per call and per step, and how far its vertices are from the device's.
+--cloud-volume: also meshes the cloud: the fused cloud merged by voxel_merge, its normals by voxel_normals, added by
+tsdf.TSDFVolume.integrate_cloud to the --tsdf volume with a radius of CLOUD_VOLUME_RADIUS_VOXELS voxels, then
+extract_mesh; reports, as "cloud_volume", N, the flagged bricks out of all bricks, ms per call (and of the entry alone,
+on a built index), M and F of the mesh, metrics.mesh_metrics of that mesh against the fused cloud next to those of the
+mesh of the same views through integrate, and the same sums composed from torch ops (chunks of the cloud through
+torch.cdist) at TORCH_VOXELS of the updated voxels with its ms, its extrapolation to the voxels of the flagged bricks and
+its largest difference from the device's state.  Nothing asserts a time."""
 import argparse
 import json
 import os
@@ -1295,9 +1302,91 @@ def run_smooth(sc, steps, warmup):
         "device_smooth_beats_torch": bool(np.mean(stimes) < np.mean(tstimes))}}
 
 
+CLOUD_VOLUME_RADIUS_VOXELS, TORCH_VOXELS, TORCH_POINT_CHUNK = 3, 1024, 1 << 16
+
+
+def torch_integrate_cloud(centres, points, normals, radius, trunc):
+    """The sums of integrate_cloud at the voxel centres `centres` (Q,3) from torch ops: chunks of the cloud through
+    torch.cdist (its own arithmetic, so a row at the edge of the reach may fall on the other side), the weights
+    (1 - d2 / r2)^2 and the clamped plane distances as (Q, chunk) tensors in HBM, float sums in arrival order (what a
+    caller had to write without the kernel): (weight (Q,), sdf_sum (Q,))."""
+    w = torch.zeros(centres.shape[0], dtype=torch.float32, device=centres.device)
+    s = torch.zeros_like(w)
+    r2 = radius * radius
+    for a in range(0, points.shape[0], TORCH_POINT_CHUNK):
+        p, n = points[a:a + TORCH_POINT_CHUNK], normals[a:a + TORCH_POINT_CHUNK]
+        d2 = torch.cdist(centres, p) ** 2
+        ok = (d2 <= r2) & (n != 0).any(1)[None, :]
+        phi = torch.where(ok, (1 - d2 / r2) ** 2, torch.zeros_like(d2))
+        dist = (centres[:, None, :] - p[None, :, :]).mul(n[None, :, :]).sum(2).clamp(-trunc, trunc)
+        w += phi.sum(1)
+        s += (phi * dist).sum(1)
+    return w, s
+
+
+def run_cloud_volume(sc, res, steps, warmup):
+    steps, warmup = min(steps, 5), min(warmup, 1)           # (the calls are long: milliseconds)
+    depth, K, T, images = sc["depth"], sc["K"], sc["T_cam_in_world"], sc["images"]
+    dev = depth.device
+    trunc, radius = 4 * TSDF_VOXEL, CLOUD_VOLUME_RADIUS_VOXELS * TSDF_VOXEL
+    maps = depth_normals(depth, K, T_cam_in_world=T)
+    vc = voxel_merge(res.points, float(np.float32(float(res.depth[res.depth > 0].median()) / float(K[0, 0, 0]))), colors=res.colors)
+    vn = voxel_normals(vc, point_normals(res, maps))
+    pts = vc.points.contiguous()
+    n = int(pts.shape[0])
+    vol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, trunc, device=dev)
+    _, times = timed(lambda: vol.integrate_cloud(pts, vn, radius), steps, warmup)
+    vol.reset()
+    vol.integrate_cloud(pts, vn, radius)
+    mesh, etimes = timed(lambda: vol.extract_mesh(), steps, warmup)
+    # the brick flags of one more call, through the entries, into a scratch state
+    lib = _native.load()
+    h, inv, r2 = cloud_radius_scalars(radius)
+    nx, ny, nz = TSDF_DIMS
+    flag_bytes = lib.mvsn_tsdf_cloud_workspace_bytes(nx, ny, nz)
+    flags = torch.empty(flag_bytes, dtype=torch.uint8, device=dev)
+    scratch = (torch.zeros_like(vol.sdf_sum), torch.zeros_like(vol.weight))
+    ws_bytes = lib.mvsn_cloud_workspace_bytes(n)
+    ws, status = torch.empty(ws_bytes, dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+    st = _native.stream()
+    _native.check(lib.mvsn_cloud_index_build(_native.ptr(pts), n, float(h), float(inv), _native.ptr(status), _native.ptr(ws),
+                                             ws_bytes, st), "mvsn_cloud_index_build")
+    _, itimes = timed(lambda: _native.check(lib.mvsn_tsdf_cloud_integrate(
+        _native.ptr(pts), _native.ptr(vn), None, None, n, _native.ptr(ws), ws_bytes, float(h), float(inv), float(r2), nx, ny, nz,
+        float(vol.voxel_size), *(float(o) for o in vol.origin), float(vol.trunc), _native.ptr(scratch[0]), _native.ptr(scratch[1]),
+        None, _native.ptr(flags), flag_bytes, st), "mvsn_tsdf_cloud_integrate"), steps, warmup)
+    bricks = -(-nx // 8) * -(-ny // 8) * -(-nz // 8)
+    flagged = int(flags[:bricks].sum())
+    # the torch composition at a sample of the voxels the device updated
+    seen = torch.nonzero(vol.weight.reshape(-1) > 0)[:, 0]
+    pick = seen[torch.randperm(seen.shape[0], generator=torch.Generator().manual_seed(0))[:TORCH_VOXELS].to(dev)]
+    k, j, i = pick // (nx * ny), (pick // nx) % ny, pick % nx
+    centres = torch.stack([i, j, k], 1).to(torch.float32) * float(vol.voxel_size) + torch.tensor(vol.origin, device=dev)
+    (tw, ts), ttimes = timed(lambda: torch_integrate_cloud(centres, pts, vn, float(h), float(vol.trunc)), 2, 1)
+    dw, dsum = vol.weight.reshape(-1)[pick], vol.sdf_sum.reshape(-1)[pick]
+    strong = dw >= 1
+    # the same views through integrate, for the scores next to each other
+    dvol = TSDFVolume(TSDF_DIMS, TSDF_VOXEL, TSDF_ORIGIN, trunc, device=dev)
+    dvol.integrate(depth, K, T)
+    dmesh = dvol.extract_mesh()
+    score = lambda m: mesh_metrics(m.vertices, m.faces, res.points, TSDF_VOXEL, samples=MESH_SAMPLES)   # noqa: E731
+    return {"cloud_volume": {
+        "N": n, "radius": radius, "trunc": trunc, "bricks": bricks, "flagged_bricks": flagged,
+        "voxels_updated": int(seen.shape[0]), "ms_per_call_median": float(np.median(times)),
+        "ms_per_call_min": float(np.min(times)), "entry_only_ms_per_call_median": float(np.median(itimes)),
+        "extract_ms_per_call_median": float(np.median(etimes)), "M": int(mesh.vertices.shape[0]), "F": int(mesh.faces.shape[0]),
+        "scores": score(mesh), "scores_of_the_depth_map_volume": score(dmesh),
+        "M_of_the_depth_map_volume": int(dmesh.vertices.shape[0]), "F_of_the_depth_map_volume": int(dmesh.faces.shape[0]),
+        "torch_voxels": int(pick.shape[0]), "torch_ms_per_call_mean": float(np.mean(ttimes)),
+        "torch_extrapolated_ms_all_flagged_voxels": float(np.mean(ttimes)) * flagged * 512 / max(int(pick.shape[0]), 1),
+        "torch_max_abs_weight_difference": float((tw - dw).abs().max()),
+        "torch_max_abs_value_difference_where_weight_at_least_1":
+            float((ts[strong] / tw[strong] - dsum[strong] / dw[strong]).abs().max()) if bool(strong.any()) else 0.0}}
+
+
 def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False, cloud=False, tsdf=False, raycast=False,
         align=False, mesh=False, register=False, cloud_normals_too=False, knn=False, clusters=False, render=False, mesh_metrics_too=False, mesh_render_too=False,
-        simplify_too=False, smooth_too=False):
+        simplify_too=False, smooth_too=False, cloud_volume_too=False):
     dev = torch.device("cuda:0")
     sc = synthetic.fusion_scene(V, H, W, arc=0.02 * (V - 1), device=dev)
     nb = neighbours(V, M)
@@ -1328,7 +1417,8 @@ def run(V, H, W, M, steps, warmup, confidence=False, voxel=False, normals=False,
     rasterised = run_mesh_render(sc, steps, warmup) if mesh_render_too else {}
     simplified = run_simplify(sc, steps, warmup) if simplify_too else {}
     smoothed = run_smooth(sc, steps, warmup) if smooth_too else {}
-    return {**smoothed, **simplified, **rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
+    meshed = run_cloud_volume(sc, res, steps, warmup) if cloud_volume_too else {}
+    return {**meshed, **smoothed, **simplified, **rasterised, **mesh_scored, **drawn, **split, **gated, **merged, **oriented, **scored, **volume, **rendered, **aligned, **cleaned, **registered, **estimated, **searched, "scene": f"V{V}_{W}x{H}_M{M}", "ms_per_call_median": float(np.median(times)),
             "ms_per_call_min": float(np.min(times)), "steps": steps, "points": N,
             "kept_fraction": N / (V * P),
             "bytes": {"consistency_ref_depth_read": 4 * V * P, "consistency_maps_written": 5 * V * P,
@@ -1381,12 +1471,15 @@ def main():
     ap.add_argument("--smooth", action="store_true",
                     help="also find the edges of the volume's mesh (mesh_edges), smooth it (mesh_smooth, Taubin) and recompute "
                          "its normals (mesh_normals), and the torch form of the edges and of the smoothing")
+    ap.add_argument("--cloud-volume", action="store_true",
+                    help="also mesh the merged fused cloud through integrate_cloud and extract_mesh, score it next to the "
+                         "mesh of the depth-map volume, and the torch form of the sums at a sample of the voxels")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     for V, H, W, M in SCENES:
         print(json.dumps(run(V, H, W, M, a.steps, a.warmup, a.confidence, a.voxel, a.normals, a.cloud_metrics,
                              a.tsdf, a.raycast, a.align, a.mesh, a.register, a.cloud_normals, a.knn, a.clusters,
-                             a.render, a.mesh_metrics, a.mesh_render, a.simplify, a.smooth)), flush=True)
+                             a.render, a.mesh_metrics, a.mesh_render, a.simplify, a.smooth, a.cloud_volume)), flush=True)
     if a.global_too:
         print(json.dumps(run_global(a.steps, a.warmup)), flush=True)
 
